@@ -13,7 +13,13 @@ gap-walk sampler + syndrome kernel) before the timed region.  There is no collec
 decode step (syndromes are independent); at N > 1 the RCCL gather of every rank's records to
 rank 0 is timed separately, as its own component and end to end (decode + gather per step).
 
-Prints one JSON line (rank 0).  Extra objects:
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints one JSON
+line (rank 0) with the headline figure, `ms_per_step` and the roofline objects that cost no run of their
+own.  `--dump-outputs DIR` also writes what the last timed step computed (dump_outputs below).  Every
+other measurement or check (the objects after roofline_hbm_alg below, and the N > 1 gather) runs only
+with `--full`.
+
+Objects of the JSON line:
   roofline        the dominant kernel (the decode) against its real bound, VALU issue:
                   SQ_INSTS_VALU per launch (rocprofv3 PMC, profiles/pmc_<code>.json, per syndrome
                   x the batch) x 2 cycles / (1024 SIMDs x 2.4 GHz x step time); step time = the GPU
@@ -160,8 +166,18 @@ def main():
                     help="time the step as a replay of one captured HIP graph of it (same kernels, no per-launch "
                          "host work or inter-launch gaps); without it the replay is reported in `graph`")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the timed steps (profiling runs: no full-arithmetic / phase / sustained re-timings)")
+                    help="with --full: no full-arithmetic / phase / sustained re-timings")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement and check: re-timings (full "
+                         "arithmetic, other input, reference stop, sustained, graph replay), phase counts, the "
+                         "published blocks, the CPU baseline and, at N > 1, the gather (narrowed by --no-extras, "
+                         "--no-cpu, --no-gather)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step produced to DIR/<name>.npy (float32; a fixed seeded "
+                         "sample of rows where they exceed 48 MB)")
     args = ap.parse_args()
+    extras = args.full and not args.no_extras
+    cpu = args.full and not args.no_cpu
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -275,6 +291,9 @@ def main():
     total = B * world * steps if scaling == "weak" else global_batch * steps
     value = total / elapsed
     ms_per_step = elapsed / steps * 1e3
+    if args.dump_outputs:  # before anything below runs the step again
+        names = ("records", "iters") if packed else ("eX", "eZ", "flags", "iters")
+        dump_outputs(args.dump_outputs, names, outs, rank, world)
 
     # executed iterations of the timed batch (fixed: == iters)
     it_np = its.cpu().numpy()
@@ -329,7 +348,7 @@ def main():
                                "note": "SURVEY 8(d) HBM-resident flooding schedule; the engine keeps messages in "
                                        "VGPRs, so this is not its bound when frac > 1"}
 
-    if not args.no_extras:
+    if extras:
         if args.hard_paths:
             full = retime(dec, step, stream, B, outs, {"hard_paths": 0}, world=world)
             # whole job: every rank's shard at the slowest rank's kernel time
@@ -355,11 +374,11 @@ def main():
         if pl:
             out["executed_iteration_fraction"] = round(pl["sector_iterations_executed"] / pl["sector_iterations_nominal"], 4)
         if args.stop == "fixed" and packed:
-            out["ref_stop"] = ref_stop(dec, sX, sZ, p, iters, B, stream, world, fname, rank == 0 and not args.no_cpu)
+            out["ref_stop"] = ref_stop(dec, sX, sZ, p, iters, B, stream, world, fname, rank == 0 and cpu)
         out["sustained"] = sustained(step, stream, dev, world, ms_per_step, args.min_seconds,
                                      global_batch if scaling == "strong" else B * world)
 
-    if not args.no_extras and not args.graph:
+    if extras and not args.graph:
         out["graph"] = graph_retime(eager_step, S, dev, stream, B, outs, world, global_batch if scaling == "strong"
                                     else B * world, steps)
     if args.graph:
@@ -369,7 +388,7 @@ def main():
     if solo:  # an RCCL group of one, after every timed measurement above
         dist.init_process_group("nccl", init_method="tcp://127.0.0.1:%d" % free_port(), rank=0, world_size=1)
         backend = "nccl"
-    if (world > 1 or solo) and not args.no_gather and packed:
+    if ((world > 1 and args.full) or solo) and not args.no_gather and packed:
         try:
             out["gather"] = gather_measure(dec, step, rec, B, world, rank, dev, stream, steps, global_batch, backend,
                                            bound_into)
@@ -378,15 +397,37 @@ def main():
     if solo:
         dist.destroy_process_group()
 
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and cpu:
         out["cpu_baseline"] = cpu_baseline(code, fname, sX, sZ, p, iters, args, outs, packed)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras:
         out["published_blocks"] = published_blocks(local)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(out), flush=True)
+
+
+DUMP_BYTES = 48 << 20           # --dump-outputs: float32 bytes written at most (all arrays together)
+
+
+def dump_outputs(path, names, outs, rank, world):
+    """--dump-outputs: the step's output tensors (one row per syndrome) as DIR/<name>.npy in float32, each
+    element's value kept (bytes 0..255, iteration counts).  Where all rows would exceed DUMP_BYTES, the
+    same fixed sample of rows of every array (seeded, sorted; its indices in DIR/rows.npy as float64).  At
+    N > 1 every rank writes its shard's arrays as <name>_rank<r>.npy."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    B = outs[0].shape[0]
+    per_row = sum(t[0].numel() for t in outs) * 4
+    n = min(B, DUMP_BYTES // per_row)
+    rows = np.arange(B) if n == B else np.sort(np.random.default_rng(SEED).choice(B, n, replace=False))
+    sfx = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(path, "rows%s.npy" % sfx), rows.astype(np.float64))
+    idx = None if n == B else torch.as_tensor(rows, device=outs[0].device)
+    for name, t in zip(names, outs):
+        a = (t if idx is None else t.index_select(0, idx)).cpu().numpy()
+        np.save(os.path.join(path, name + sfx + ".npy"), a.astype(np.float32))
 
 
 def capture_graph(step, S, dev):

@@ -39,7 +39,7 @@ def launch(nproc, script, *args):
 
 
 def test_bench_two_ranks():
-    lines = run(launch(2, "bench.py", "--gpus", "2", "--global-batch", "16384", "--no-cpu", "--steps", "3",
+    lines = run(launch(2, "bench.py", "--gpus", "2", "--full", "--global-batch", "16384", "--no-cpu", "--steps", "3",
                        "--warmup", "1", "--min-seconds", "0.05"), {})
     assert len(lines) == 1, lines
     b = lines[0]
@@ -60,8 +60,8 @@ def test_bench_two_ranks():
 def test_bench_plain_python_two_gpus():
     """`python bench.py --gpus 2` with no launcher starts the two ranks itself (a child
     torch.distributed.run) and reports them: never a one-GPU line labelled --gpus 2."""
-    lines = run([sys.executable, "bench.py", "--gpus", "2", "--global-batch", "16384", "--no-cpu", "--no-extras",
-                 "--steps", "3", "--warmup", "1"], {})
+    lines = run([sys.executable, "bench.py", "--gpus", "2", "--full", "--global-batch", "16384", "--no-cpu",
+                 "--no-extras", "--steps", "3", "--warmup", "1"], {})
     assert len(lines) == 1, lines
     b = lines[0]
     assert b["n_gpus"] == 2 and b["config"]["parallelism"] == "dp2" and b["config"]["per_gpu_batch"] == 8192

@@ -9,7 +9,7 @@
 #   compare [ARGS]       tools/kbench/compare.py ARGS (A/B of build/variants libraries, one process)
 #   psweep [ARGS]        tools/psweep.py ARGS
 #   profile NAME [CODES] tools/gpu/run_profile.sh NAME CODES (PMC evidence; EXTRA="..." via env STEP_EXTRA)
-#   trace NAME [ARGS]    rocprofv3 --kernel-trace --stats of bench.py ARGS
+#   trace NAME [ARGS]    rocprofv3 --kernel-trace --stats of bench.py --full --no-cpu ARGS
 #   mctrace NAME [ARGS]  rocprofv3 --kernel-trace --stats of tools/psweep.py ARGS
 #   exec CMD             any other command (built beforehand on the CPU side)
 set -o pipefail
@@ -45,7 +45,7 @@ for spec in "$@"; do
       tail -3 "$O/profile_$i.log" | cut -c1-300;;
     trace|mctrace)
       read -r name rest <<< "$args"
-      prog="$R/bench.py --no-cpu"; [ "$step" = mctrace ] && prog="$R/tools/psweep.py"
+      prog="$R/bench.py --full --no-cpu"; [ "$step" = mctrace ] && prog="$R/tools/psweep.py"
       (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/$name" -o run -- \
           python3 $prog $rest > "$O/${name}.out" 2> "$O/${name}.err"); rc=$?
       [ $rc -eq 0 ] && cut -d, -f1-4 "$O/$name/run_kernel_stats.csv" | cut -c1-140 | head -12;;
