@@ -3,6 +3,7 @@
 // factory for Quantum_LDPC_Code.  The reference's version is commented out; its
 // formula regenerates both shipped code files bit-for-bit (tests/test_code_model.py).
 #pragma once
+#include <memory>
 #include <string>
 #include <vector>
 

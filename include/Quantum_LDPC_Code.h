@@ -66,6 +66,16 @@ public:
         return out != 0;
     }
 
+    // A new code with the same matrices whose logical check is derived from them
+    // (qec_code_with_logical; mode = QEC_LOGICAL_REFERENCE or QEC_LOGICAL_DEGENERATE).  No reference
+    // analogue: the reference only reads the I-P matrix from a code file.  Throws std::string.
+    Quantum_LDPC_Code withLogicalCheck(int mode) const
+    {
+        qec_code* h = qec_code_with_logical(handle_.get(), mode);
+        if (!h) throw std::string(qec_last_error());
+        return Quantum_LDPC_Code(h);
+    }
+
     const qec_code* handle() const { return handle_.get(); }
 
 private:

@@ -103,7 +103,8 @@ const char* qec_build_id(void);
  * 4-line text file "J K L P sigma tau" / HX / HZ / I-P.  NULL on error. */
 qec_code* qec_code_load(const char* path);
 /* Replaces the QC_LDPC_CSS(J,K,L,P,sigma,tau) generator (QEC_LDPC/QEC_LDPC_CSS.cu:5-131).
- * Generated codes carry no I-P matrix (the reference never generates one). */
+ * Generated codes carry no I-P matrix (the reference never generates one); qec_code_with_logical
+ * derives the check from the two matrices. */
 qec_code* qec_code_generate(int J, int K, int L, int P, int sigma, int tau);
 int qec_code_free(qec_code* code);
 /* J K L P sigma tau n numEqsX numEqsZ (Quantum_LDPC_Code.h:10-20) into out[9] */
@@ -121,6 +122,27 @@ int qec_code_syndrome(const qec_code* code, int sector, const uint8_t* e, size_t
 /* Quantum_LDPC_Code::CheckLogicalError (Quantum_LDPC_Code.h:126-142) on the
  * residual [ex | ez] of B samples; out[b] = 1 if logical error */
 int qec_code_check_logical(const qec_code* code, const uint8_t* ex, const uint8_t* ez, size_t B, uint8_t* out);
+/* The logical check derived from the two parity-check matrices (no reference analogue: the reference
+ * reads the I-P matrix from line 4 of a code file and never generates one).
+ *   QEC_LOGICAL_FILE: the matrix of the code file, if it had one.
+ *   QEC_LOGICAL_REFERENCE: logical iff rx is not in rowspace(pcmX) or rz is not in rowspace(pcmZ).
+ *     This is what the shipped I-P matrices compute: they are block-diagonal [A 0; 0 B] with
+ *     ker A = rowspace(pcmX), ker B = rowspace(pcmZ).  On the residuals
+ *     GetStatistics tests (rx in ker pcmX) nearly every non-zero residual is then a logical error,
+ *     degenerate corrections included; the published counters carry that meaning.
+ *   QEC_LOGICAL_DEGENERATE: logical iff rx is not in rowspace(pcmZ) or rz is not in rowspace(pcmX),
+ *     so a residual that is a product of stabilizers counts as corrected.  Needs pcmX pcmZ^T = 0
+ *     over GF(2) (otherwise NULL, QEC_ERR_UNSUPPORTED, "... do not commute").
+ * The derived matrix is block-diagonal, its rows bases of ker(H) for the two matrices (reduced
+ * row-echelon form, pivots left to right; one row per free column, ascending); every entry point
+ * that takes a code with an I-P matrix takes it.  2n <= 4096 (QEC_ERR_UNSUPPORTED above). */
+enum { QEC_LOGICAL_FILE = 0, QEC_LOGICAL_REFERENCE = 1, QEC_LOGICAL_DEGENERATE = 2 };
+/* A NEW code with the same matrices and the derived check; `code` is untouched (a qec_code stays
+ * immutable).  mode: QEC_LOGICAL_REFERENCE or QEC_LOGICAL_DEGENERATE.  NULL on error. */
+qec_code* qec_code_with_logical(const qec_code* code, int mode);
+int qec_code_logical_mode(const qec_code* code);            /* 0: the file's matrix, or none */
+int qec_code_logical_rows(const qec_code* code, int* rows); /* non-zero rows of the check; 0 if none */
+int qec_code_imp(const qec_code* code, uint8_t* out);       /* dense 2n x 2n; QEC_ERR_UNSUPPORTED if none */
 
 /* ---- decoder (DecoderGPU, QEC_LDPC/DecoderGPU.h:11-281) ------------------- */
 /* Replaces DecoderGPU(Quantum_LDPC_Code) (DecoderGPU.h:117-130) and, with device = -1,
@@ -318,6 +340,15 @@ int qec_statistics_dev(qec_decoder* dec, const uint8_t* x, const uint8_t* z, con
  * (B x 2, nullable) given, to counters[QEC_MC_NCOUNTERS_ALL] including the iteration sums. */
 int qec_statistics_packed_dev(qec_decoder* dec, const uint8_t* errp, const uint8_t* records, const int32_t* iters,
                               size_t B, uint64_t* counters, void* stream);
+/* Per-sample form of qec_statistics_packed_dev's logical / corrected split: errp B x 2 ceil(n/8),
+ * records B x QEC_RECORD_BYTES(n) (any base alignment), outcome B bytes: QEC_OUTCOME_SYNDROME_FAIL
+ * if the record's flags carry a syndrome failure, else QEC_OUTCOME_LOGICAL if the residual
+ * errp ^ record fails the code's logical check, else QEC_OUTCOME_CORRECTED (convergence bits do not
+ * matter).  Enqueued on `stream`; no synchronisation, no allocation, nothing written but outcome[0, B).
+ * GPU engines, single-device handle, code with a logical check, 2n <= 4096. */
+enum { QEC_OUTCOME_CORRECTED = 0, QEC_OUTCOME_LOGICAL = 1, QEC_OUTCOME_SYNDROME_FAIL = 2 };
+int qec_logical_packed_dev(qec_decoder* dec, const uint8_t* errp, const uint8_t* records, size_t B,
+                           uint8_t* outcome, void* stream);
 /* Decision records for gathering a sharded batch to one rank (the decoded
  * vectors travel bit-packed): out is B x (2 ceil(n/8) + 1) bytes, per syndrome eX packed
  * (bit j of byte k = qubit 8k + j), then eZ packed, then the ErrorCode flags byte.  Device

@@ -37,6 +37,7 @@ EXPORTS = (
     "qec_last_error", "qec_abi_version", "qec_build_id",
     "qec_code_load", "qec_code_generate", "qec_code_free", "qec_code_params", "qec_code_exponents",
     "qec_code_pcm", "qec_code_describe", "qec_code_syndrome", "qec_code_check_logical",
+    "qec_code_with_logical", "qec_code_logical_mode", "qec_code_logical_rows", "qec_code_imp",
     "qec_decoder_create", "qec_decoder_create_engine", "qec_decoder_create_multi", "qec_decoder_destroy",
     "qec_decoder_num_parts", "qec_decoder_part", "qec_decoder_device", "qec_decoder_describe",
     "qec_decoder_set_option", "qec_decoder_get_option",
@@ -44,9 +45,13 @@ EXPORTS = (
     "qec_decode_bits_packed_dev",
     "qec_sample_fixed_weight", "qec_get_statistics",
     "qec_sample_depolarizing_dev", "qec_sample_syndrome_dev", "qec_syndrome_dev", "qec_statistics_dev",
-    "qec_statistics_packed_dev", "qec_pack_decisions_dev",
+    "qec_statistics_packed_dev", "qec_logical_packed_dev", "qec_pack_decisions_dev",
     "qec_monte_carlo",
 )
+# QEC_LOGICAL_*: where a code's logical check comes from (include/qec_ldpc.h)
+LOGICAL = {"file": 0, "reference": 1, "degenerate": 2}
+# QEC_OUTCOME_*: logical_packed_dev's per-sample outcomes
+OUTCOME_CORRECTED, OUTCOME_LOGICAL, OUTCOME_SYNDROME_FAIL = 0, 1, 2
 MC_COUNTERS = ("withX", "withZ", "synX", "synZ", "logical", "corrected", "convX", "convZ")
 MC_COUNTERS_ALL = MC_COUNTERS + ("iterationsX", "iterationsZ")
 
@@ -115,6 +120,10 @@ def lib():
             "qec_code_describe": (i, [vp, ctypes.c_char_p, sz]),
             "qec_code_syndrome": (i, [vp, i, vp, sz, vp]),
             "qec_code_check_logical": (i, [vp, vp, vp, sz, vp]),
+            "qec_code_with_logical": (vp, [vp, i]),
+            "qec_code_logical_mode": (i, [vp]),
+            "qec_code_logical_rows": (i, [vp, vp]),
+            "qec_code_imp": (i, [vp, vp]),
             "qec_decoder_create": (vp, [vp, i, sz]),
             "qec_decoder_create_engine": (vp, [vp, i, sz, i]),
             "qec_decoder_create_multi": (vp, [vp, vp, i, sz]),
@@ -137,6 +146,7 @@ def lib():
             "qec_syndrome_dev": (i, [vp, vp, vp, sz, vp, vp, vp]),
             "qec_statistics_dev": (i, [vp, vp, vp, vp, vp, vp, sz, vp, vp]),
             "qec_statistics_packed_dev": (i, [vp, vp, vp, vp, sz, vp, vp]),
+            "qec_logical_packed_dev": (i, [vp, vp, vp, sz, vp, vp]),
             "qec_pack_decisions_dev": (i, [vp, vp, vp, vp, sz, vp, vp]),
             "qec_monte_carlo": (i, [vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, f, i, i, sz,
                                     ctypes.POINTER(MCResult)]),
@@ -268,9 +278,42 @@ class Quantum_LDPC_Code:
         errors = np.asarray(errors)
         return bool(self.check_logical(errors[: self.n], errors[self.n:])[0])
 
+    def with_logical(self, mode):
+        """A new code with the same matrices whose logical check is derived from them
+        (qec_code_with_logical): "reference" = rx not in rowspace(pcmX) or rz not in rowspace(pcmZ),
+        what the shipped I-P files compute; "degenerate" = rx not in rowspace(pcmZ) or rz not in
+        rowspace(pcmX), a residual that is a product of stabilizers counts as corrected (needs
+        pcmX pcmZ^T = 0).  This code is unchanged."""
+        if mode not in ("reference", "degenerate"):
+            raise QecError("with_logical: mode must be 'reference' or 'degenerate', not %r" % (mode,))
+        h = lib().qec_code_with_logical(self._h, LOGICAL[mode])
+        if not h:
+            raise QecError(last_error())
+        return Quantum_LDPC_Code(h)
+
+    @property
+    def logical_mode(self):
+        """"file" (the code file's I-P matrix, or no check at all), "reference" or "degenerate"."""
+        v = lib().qec_code_logical_mode(self._h)
+        return {b: a for a, b in LOGICAL.items()}[v]
+
+    @property
+    def logical_rows(self):
+        """Non-zero rows of the logical check's matrix (0: the code has none)."""
+        v = ctypes.c_int(0)
+        _check(lib().qec_code_logical_rows(self._h, ctypes.byref(v)), "qec_code_logical_rows")
+        return v.value
+
+    def imp(self):
+        """The dense 2n x 2n I-P matrix (the file's, or the derived one)."""
+        a = np.zeros((2 * self.n, 2 * self.n), dtype=np.uint8)
+        _check(lib().qec_code_imp(self._h, _ptr(a)), "qec_code_imp")
+        return a
+
 
 def QC_LDPC_CSS(J, K, L, P, sigma, tau):
-    """Generated code (QEC_LDPC/QEC_LDPC_CSS.cu:5-131); carries no I-P matrix."""
+    """Generated code (QEC_LDPC/QEC_LDPC_CSS.cu:5-131); carries no I-P matrix (with_logical derives
+    the check)."""
     h = lib().qec_code_generate(J, K, L, P, sigma, tau)
     if not h:
         raise QecError(last_error())
@@ -549,6 +592,19 @@ class DecoderGPU:
                                                self._t(iters, "iters", torch.int32, (B, 2), True), B,
                                                self._t(counters, "counters", torch.int64, (nc,)),
                                                ctypes.c_void_p(self._stream(stream))), "qec_statistics_packed_dev")
+
+    def logical_packed_dev(self, errp, records, outcome, stream=None):
+        """Per-sample outcome of packed errors + packed decision records into outcome [B] (uint8 device
+        tensor): OUTCOME_SYNDROME_FAIL if the record flags a syndrome failure, else OUTCOME_LOGICAL if
+        the residual fails the code's logical check, else OUTCOME_CORRECTED."""
+        import torch
+        self._single("logical_packed_dev")
+        c = self.code
+        B = errp.shape[0]
+        _check(lib().qec_logical_packed_dev(self._h, self._t(errp, "errp", torch.uint8, (B, 2 * ((c.n + 7) // 8))),
+                                            self._t(records, "records", torch.uint8, (B, self.record_bytes())),
+                                            B, self._t(outcome, "outcome", torch.uint8, (B,)),
+                                            ctypes.c_void_p(self._stream(stream))), "qec_logical_packed_dev")
 
     def pack_decisions_dev(self, eX, eZ, flags, out, stream=None):
         """Bit-packs a decoded device batch into out [B, record_bytes()] (uint8 device tensor)."""

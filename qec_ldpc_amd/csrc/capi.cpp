@@ -67,6 +67,8 @@ inline int mc_count_u64() { return (mc_fused_count_words() + 3) / 4 * 2; }  // w
 int launch_statistics_packed(const Code& c, const uint64_t* imp_cols, const uint8_t* errp, int estride, const uint8_t* rec,
                              const int32_t* iters, long long B, unsigned long long* counters, hipStream_t st,
                              int rec_stride = 0);
+int launch_logical_outcome(const Code& c, const uint64_t* imp_cols, const uint8_t* errp, const uint8_t* rec, long long B,
+                           uint8_t* outcome, hipStream_t st);
 void* sparse_plan_create(const Code& c, int device);
 void sparse_plan_free(void* plan);
 const char* sparse_plan_name(const void* plan);
@@ -330,6 +332,42 @@ int qec_code_check_logical(const qec_code* h, const uint8_t* ex, const uint8_t* 
     if (!h || (B && (!ex || !ez || !out))) return fail(QEC_ERR_ARG, "qec_code_check_logical: bad argument");
     if (h->c.imp.empty()) return fail(QEC_ERR_UNSUPPORTED, "code has no I-P matrix (generated codes carry none)");
     for (size_t b = 0; b < B; ++b) out[b] = host_check_logical(h->c, ex + b * h->c.n, ez + b * h->c.n) ? 1 : 0;
+    return QEC_OK;
+}
+
+qec_code* qec_code_with_logical(const qec_code* code, int mode)
+{
+    if (!code) { fail(QEC_ERR_ARG, "qec_code_with_logical: null code"); return nullptr; }
+    auto* h = new (std::nothrow) qec_code;
+    if (!h) { fail(QEC_ERR_NOMEM, "qec_code_with_logical: out of memory"); return nullptr; }
+    try {
+        if (derive_logical(code->c, mode, h->c) != QEC_OK) { delete h; return nullptr; }
+    } catch (const std::bad_alloc&) {
+        delete h;
+        fail(QEC_ERR_NOMEM, "qec_code_with_logical: out of memory");
+        return nullptr;
+    }
+    return h;
+}
+
+int qec_code_logical_mode(const qec_code* code)
+{
+    if (!code) return fail(QEC_ERR_ARG, "qec_code_logical_mode: null code");
+    return code->c.logical_mode;
+}
+
+int qec_code_logical_rows(const qec_code* code, int* rows)
+{
+    if (!code || !rows) return fail(QEC_ERR_ARG, "qec_code_logical_rows: null argument");
+    *rows = code->c.imp_words ? (int)(code->c.imp_rows.size() / code->c.imp_words) : 0;
+    return QEC_OK;
+}
+
+int qec_code_imp(const qec_code* code, uint8_t* out)
+{
+    if (!code || !out) return fail(QEC_ERR_ARG, "qec_code_imp: null argument");
+    if (code->c.imp.empty()) return fail(QEC_ERR_UNSUPPORTED, "code has no I-P matrix (qec_code_with_logical derives one)");
+    std::memcpy(out, code->c.imp.data(), code->c.imp.size());
     return QEC_OK;
 }
 
@@ -1321,6 +1359,19 @@ int qec_statistics_packed_dev(qec_decoder* d, const uint8_t* errp, const uint8_t
     QEC_DEVICE_SCOPE(d->device);
     return launch_statistics_packed(*d->code, d->imp_cols.data(), errp, 2 * ((d->code->n + 7) / 8), records, iters, (long long)B,
                                     reinterpret_cast<unsigned long long*>(counters), static_cast<hipStream_t>(stream));
+}
+
+int qec_logical_packed_dev(qec_decoder* d, const uint8_t* errp, const uint8_t* records, size_t B, uint8_t* outcome,
+                           void* stream)
+{
+    if (!d || (B && (!errp || !records || !outcome))) return fail(QEC_ERR_ARG, "qec_logical_packed_dev: bad argument");
+    if (B > (size_t)1 << 36) return fail(QEC_ERR_ARG, "qec_logical_packed_dev: batch too large");
+    int rc = single_device_only(d, "qec_logical_packed_dev");
+    if (rc) return rc;
+    if (d->code->imp.empty()) return fail(QEC_ERR_UNSUPPORTED, "qec_logical_packed_dev: code has no I-P matrix");
+    QEC_DEVICE_SCOPE(d->device);
+    return launch_logical_outcome(*d->code, d->imp_cols.data(), errp, records, (long long)B, outcome,
+                                  static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

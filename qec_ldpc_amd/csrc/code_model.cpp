@@ -192,6 +192,96 @@ int generate_code(int J, int K, int L, int P, int sigma, int tau, Code& c)
     return QEC_OK;
 }
 
+namespace {
+// m x n dense 0/1 matrix -> bit-packed rows of W = ceil(n / 64) words
+std::vector<uint64_t> pack_rows(const std::vector<uint8_t>& H, int m, int n)
+{
+    const int W = (n + 63) / 64;
+    std::vector<uint64_t> R((size_t)m * W, 0);
+    for (int i = 0; i < m; ++i)
+        for (int j = 0; j < n; ++j)
+            if (H[(size_t)i * n + j]) R[(size_t)i * W + (j >> 6)] |= 1ull << (j & 63);
+    return R;
+}
+
+// A basis of ker(H) over GF(2), one n-bit row per free column in ascending order: H is reduced to
+// reduced row-echelon form with pivots taken left to right; the row of free column f is e_f plus
+// e_pivot(r) for every pivot row r with R[r][f] = 1.  v is in rowspace(H) iff every basis row has
+// even overlap with v (rowspace(H) = ker(H)^perp).
+std::vector<std::vector<uint64_t>> kernel_basis(const std::vector<uint8_t>& H, int m, int n)
+{
+    const int W = (n + 63) / 64;
+    std::vector<uint64_t> R = pack_rows(H, m, n);
+    std::vector<int> pivot_col;  // of pivot row r
+    std::vector<uint8_t> is_pivot(n, 0);
+    int rank = 0;
+    for (int col = 0; col < n && rank < m; ++col) {
+        const int w = col >> 6;
+        const uint64_t bit = 1ull << (col & 63);
+        int sel = -1;
+        for (int i = rank; i < m; ++i)
+            if (R[(size_t)i * W + w] & bit) { sel = i; break; }
+        if (sel < 0) continue;
+        if (sel != rank) std::swap_ranges(&R[(size_t)sel * W], &R[(size_t)sel * W] + W, &R[(size_t)rank * W]);
+        const uint64_t* pr = &R[(size_t)rank * W];
+        for (int i = 0; i < m; ++i)
+            if (i != rank && (R[(size_t)i * W + w] & bit))
+                for (int k = 0; k < W; ++k) R[(size_t)i * W + k] ^= pr[k];
+        pivot_col.push_back(col);
+        is_pivot[col] = 1;
+        ++rank;
+    }
+    std::vector<std::vector<uint64_t>> basis;
+    for (int f = 0; f < n; ++f) {
+        if (is_pivot[f]) continue;
+        std::vector<uint64_t> row(W, 0);
+        row[f >> 6] |= 1ull << (f & 63);
+        for (int r = 0; r < rank; ++r)
+            if (R[(size_t)r * W + (f >> 6)] & (1ull << (f & 63))) row[pivot_col[r] >> 6] |= 1ull << (pivot_col[r] & 63);
+        basis.push_back(std::move(row));
+    }
+    return basis;
+}
+}  // namespace
+
+int derive_logical(const Code& src, int mode, Code& out)
+{
+    if (mode != QEC_LOGICAL_REFERENCE && mode != QEC_LOGICAL_DEGENERATE)
+        return fail(QEC_ERR_ARG, "qec_code_with_logical: mode must be QEC_LOGICAL_REFERENCE or QEC_LOGICAL_DEGENERATE");
+    const int n = src.n, N2 = 2 * n;
+    if (N2 > 4096)
+        return fail(QEC_ERR_UNSUPPORTED, "qec_code_with_logical: 2n > 4096 (the limit of the device statistics tables)");
+    if (mode == QEC_LOGICAL_DEGENERATE) {
+        // the rows of pcmZ (pcmX) are harmless x (z) residuals only if the two stabilizer sets commute
+        const int W = (n + 63) / 64;
+        const std::vector<uint64_t> X = pack_rows(src.pcmX, src.mX, n), Z = pack_rows(src.pcmZ, src.mZ, n);
+        for (int i = 0; i < src.mX; ++i)
+            for (int j = 0; j < src.mZ; ++j) {
+                uint64_t acc = 0;
+                for (int k = 0; k < W; ++k) acc ^= X[(size_t)i * W + k] & Z[(size_t)j * W + k];
+                if (__builtin_popcountll(acc) & 1)
+                    return fail(QEC_ERR_UNSUPPORTED, "qec_code_with_logical: the degenerate check needs pcmX pcmZ^T = 0, "
+                                                     "but the X and Z checks of this code do not commute");
+            }
+    }
+    out = src;
+    out.logical_mode = mode;
+    const bool ref = mode == QEC_LOGICAL_REFERENCE;
+    const auto bx = ref ? kernel_basis(src.pcmX, src.mX, n) : kernel_basis(src.pcmZ, src.mZ, n);
+    const auto bz = ref ? kernel_basis(src.pcmZ, src.mZ, n) : kernel_basis(src.pcmX, src.mX, n);
+    // block-diagonal [A 0; 0 B]: the x-half basis in rows [0, ..) of the upper-left n x n block, the
+    // z-half basis in rows [n, ..) of the lower-right one
+    out.imp.assign((size_t)N2 * N2, 0);
+    for (size_t r = 0; r < bx.size(); ++r)
+        for (int j = 0; j < n; ++j)
+            if (bx[r][j >> 6] >> (j & 63) & 1) out.imp[r * N2 + j] = 1;
+    for (size_t r = 0; r < bz.size(); ++r)
+        for (int j = 0; j < n; ++j)
+            if (bz[r][j >> 6] >> (j & 63) & 1) out.imp[(n + r) * N2 + n + j] = 1;
+    finalize_code(out);
+    return QEC_OK;
+}
+
 void host_syndrome(const Code& c, int sector, const uint8_t* e, uint8_t* s)
 {
     const int R = sector ? c.K : c.J, P = c.P, L = c.L, n = c.n;

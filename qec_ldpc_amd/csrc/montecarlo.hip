@@ -629,6 +629,56 @@ __global__ __launch_bounds__(64 * kLaneWaves) void statistics_lane_kernel(
     }
 }
 
+// Per-sample outcome of the logical / corrected split the statistics kernels count
+// (qec_logical_packed_dev): outcome[b] = QEC_OUTCOME_SYNDROME_FAIL if the record's flags carry a
+// syndrome failure (convergence bits do not matter), else QEC_OUTCOME_LOGICAL if the residual
+// errp[b] ^ rec[b] fails the I-P check, else QEC_OUTCOME_CORRECTED.  One wave per sample in a
+// grid-stride loop.  Record rows have the odd stride 2 nb + 1 and any base alignment, so the rows are
+// read byte by byte (lane t: bytes t, t + 64, ...; coalesced) and the residual is staged in the
+// wave's 64-word LDS slice in record layout for logical_from_columns; padding bits of the last x and
+// z byte are masked, so no column past 2n is ever read.  Lane 0 stores the byte; no atomics.
+constexpr int kOutcomeWaves = 4;  // 256 threads per workgroup
+constexpr int kOutcomeMaxBlocks = 2048;
+
+__global__ __launch_bounds__(64 * kOutcomeWaves) void logical_outcome_kernel(
+    const uint8_t* __restrict__ errp, const uint8_t* __restrict__ rec, long long B, int n, int nb,
+    const uint64_t* __restrict__ imp_cols, int imp_cw, uint8_t* __restrict__ outcome)
+{
+    __shared__ __attribute__((aligned(8))) uint8_t sres[kOutcomeWaves][8 * kMaxWords];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int eb = 2 * nb, recB = eb + 1;
+    const int nw = (eb + 7) / 8;  // <= kMaxWords (launcher)
+    const uint32_t tail = (n & 7) ? (1u << (n & 7)) - 1u : 0xFFu;  // valid bits of bytes nb - 1 and 2 nb - 1
+    const long long step = (long long)gridDim.x * kOutcomeWaves;
+    for (long long b = (long long)blockIdx.x * kOutcomeWaves + wv; b < B; b += step) {
+        const uint8_t* __restrict__ es = errp + b * eb;
+        const uint8_t* __restrict__ rs = rec + b * recB;
+        const uint32_t f = __builtin_amdgcn_readfirstlane((uint32_t)rs[eb]);
+        uint8_t out = QEC_OUTCOME_SYNDROME_FAIL;
+        if (!(f & (QEC_SYNDROME_FAIL_X | QEC_SYNDROME_FAIL_Z))) {  // wave-uniform
+            bool any = false;
+            for (int t = lane; t < 8 * nw; t += 64) {
+                uint32_t r = 0;
+                if (t < eb) {
+                    r = (uint32_t)(es[t] ^ rs[t]);
+                    if (t == nb - 1 || t == eb - 1) r &= tail;
+                }
+                any |= r != 0u;
+                sres[wv][t] = (uint8_t)r;
+            }
+            bool logical = false;
+            if (__any(any)) {  // a zero residual passes every check without reading a column
+                wave_sync();
+                logical = logical_from_columns<true>(reinterpret_cast<const unsigned long long*>(sres[wv]), nw, n, nb,
+                                                     imp_cols, imp_cw, lane);
+            }
+            wave_sync();  // sres is rewritten by the next sample
+            out = logical ? QEC_OUTCOME_LOGICAL : QEC_OUTCOME_CORRECTED;
+        }
+        if (lane == 0) outcome[b] = out;
+    }
+}
+
 // ---- launchers --------------------------------------------------------------
 static int launch_check(const char* what)
 {
@@ -791,6 +841,19 @@ int launch_statistics_packed(const Code& c, const uint64_t* imp_cols, const uint
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * kStatBlockWaves), 0, st, errp, estride, rec, iters, B,
                        c.n, nb, imp_cols, c.imp_col_words, counters);
     return launch_check("statistics_packed");
+}
+
+int launch_logical_outcome(const Code& c, const uint64_t* imp_cols, const uint8_t* errp, const uint8_t* rec, long long B,
+                           uint8_t* outcome, hipStream_t st)
+{
+    if (B <= 0) return QEC_OK;
+    if (2 * c.n > 64 * kMaxWords || c.imp_col_words > 64)
+        return fail(QEC_ERR_UNSUPPORTED, "logical outcome kernel: 2n > 4096");
+    const int nb = (c.n + 7) / 8;  // 2 nb <= 512 bytes = kMaxWords words
+    const long long blocks = std::min<long long>((B + kOutcomeWaves - 1) / kOutcomeWaves, kOutcomeMaxBlocks);
+    hipLaunchKernelGGL(logical_outcome_kernel, dim3((unsigned)blocks), dim3(64 * kOutcomeWaves), 0, st, errp, rec, B, c.n,
+                       nb, imp_cols, c.imp_col_words, outcome);
+    return launch_check("logical_outcome");
 }
 
 int launch_statistics(const Code& c, const uint64_t* imp_cols, const uint8_t* x, const uint8_t* z, const uint8_t* eX,

@@ -27,7 +27,8 @@ struct Code {
     int J = 0, K = 0, L = 0, P = 0, sigma = 0, tau = 0;
     int n = 0, mX = 0, mZ = 0;
     std::vector<uint8_t> pcmX, pcmZ;   // m x n dense, as read / generated
-    std::vector<uint8_t> imp;          // 2n x 2n dense I-P (empty for generated codes)
+    std::vector<uint8_t> imp;          // 2n x 2n dense I-P (empty for generated codes without a derived check)
+    int logical_mode = 0;              // QEC_LOGICAL_*: imp from the file (or none), or derived (derive_logical)
     bool is_qc = false;                // every block a circulant permutation matrix
     std::vector<int> EX, EZ;           // J x L / K x L shifts in [0, P): row i -> col (E + i) mod P
     // Bit-packed I-P rows that are not all-zero (for CheckLogicalError).
@@ -45,6 +46,11 @@ int generate_code(int J, int K, int L, int P, int sigma, int tau, Code& out);
 // Generator exponent tables (QEC_LDPC/QEC_LDPC_CSS.cu:37-90); returns false if sigma has no inverse.
 bool generator_exponents(int J, int K, int L, int P, int sigma, int tau, std::vector<int>& EX, std::vector<int>& EZ);
 void finalize_code(Code& c);  // derive circulant tables + packed I-P from the dense matrices
+// A copy of src whose logical check is derived from its parity-check matrices (QEC_LOGICAL_REFERENCE:
+// rx not in rowspace(pcmX) or rz not in rowspace(pcmZ), what the shipped I-P files compute;
+// QEC_LOGICAL_DEGENERATE: rx not in rowspace(pcmZ) or rz not in rowspace(pcmX), needs pcmX pcmZ^T = 0):
+// a block-diagonal imp whose rows are kernel bases of the two matrices.  2n <= 4096.
+int derive_logical(const Code& src, int mode, Code& out);
 
 // Host syndrome s = H e mod 2 via the circulant tables (or dense if not QC).
 void host_syndrome(const Code& c, int sector, const uint8_t* e, uint8_t* s);

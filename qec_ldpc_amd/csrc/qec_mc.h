@@ -142,7 +142,9 @@ __device__ __forceinline__ bool logical_from_columns(const unsigned long long* r
     const bool col_lane = lane < cw;
     uint64_t acc = 0;
     for (int w = 0; w < nw; ++w) {
-        uint64_t bits = ((uint64_t)__builtin_amdgcn_readlane(hi, w) << 32) | __builtin_amdgcn_readlane(lo, w);
+        // readlane returns int: without the cast a low word with bit 31 set sign-extends over the high one
+        uint64_t bits = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(hi, w) << 32) |
+                        (uint32_t)__builtin_amdgcn_readlane(lo, w);
         while (bits) {  // uniform
             int q[4];
 #pragma unroll

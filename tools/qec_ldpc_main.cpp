@@ -13,8 +13,14 @@
 //                      depolarising samples at p per run (qec_monte_carlo, GPU engine), w and W ignored
 //   --stop ref|fixed|syndrome   stop rule of --rng philox runs (default ref)
 //   --batch B          samples per device batch of --rng philox runs (default 2^20)
-//   --seed S           Philox stream of --rng philox runs (default 0x51EC0DE; GetStatistics draws its
-//                      own seed from std::random_device, as main.cu does)
+//   --seed S           Philox stream of --rng philox runs (default 0x51EC0DE).  --rng msvc: the mt19937
+//                      seed of every GetStatistics call, for a repeatable run (without it each call
+//                      draws its own from std::random_device, as main.cu does)
+//   --logical file|reference|degenerate   the logical-error check: the code file's I-P matrix (default;
+//                      main.cu's), or one derived from the two parity-check matrices after loading
+//                      (qec_code_with_logical), so a code file with only its first three lines works.
+//                      reference: what the shipped I-P matrices compute; degenerate: a residual that is
+//                      a product of stabilizers counts as corrected
 // Unknown or inconsistent flags exit with status 2.
 #include <algorithm>
 #include <chrono>
@@ -61,7 +67,7 @@ int usage(const std::string& why)
 {
     std::cerr << why << std::endl
               << "usage: qec_ldpc [--engine gpu|cpu] [--gpus N | --devices i,j,...] [--rng msvc|philox]"
-                 " [--stop ref|fixed|syndrome] [--batch B] [--seed S] initFile"
+                 " [--stop ref|fixed|syndrome] [--batch B] [--seed S] [--logical file|reference|degenerate] initFile"
               << std::endl;
     return 2;
 }
@@ -78,7 +84,7 @@ int main(int argc, char** argv)
     std::time_t ts = std::chrono::system_clock::to_time_t(std::chrono::system_clock::now());
     log << std::endl << std::ctime(&ts);
     std::vector<int> devices{0};
-    std::string engine = "gpu", rng = "msvc", stopName = "ref";
+    std::string engine = "gpu", rng = "msvc", stopName = "ref", logical = "file";
     bool deviceFlag = false, stopFlag = false, batchFlag = false, seedFlag = false;
     size_t batch = size_t(1) << 20;
     unsigned long long seed = 0x51EC0DE;
@@ -107,6 +113,10 @@ int main(int argc, char** argv)
                 stopFlag = true;
                 if (stopName != "ref" && stopName != "fixed" && stopName != "syndrome")
                     return usage("--stop: ref, fixed or syndrome");
+            } else if (flag == "--logical") {
+                logical = val;
+                if (logical != "file" && logical != "reference" && logical != "degenerate")
+                    return usage("--logical: file, reference or degenerate");
             } else if (flag == "--batch") {
                 const long long b = std::stoll(val);
                 if (b <= 0) return usage("--batch: a positive sample count");
@@ -124,8 +134,8 @@ int main(int argc, char** argv)
     }
     if (engine == "cpu" && deviceFlag) return usage("--gpus / --devices need --engine gpu");
     if (rng == "philox" && engine == "cpu") return usage("--rng philox runs on the GPU engine only");
-    if (rng == "msvc" && (stopFlag || batchFlag || seedFlag))
-        return usage("--stop / --batch / --seed apply to --rng philox (GetStatistics keeps the reference stop rule)");
+    if (rng == "msvc" && (stopFlag || batchFlag))
+        return usage("--stop / --batch apply to --rng philox (GetStatistics keeps the reference stop rule)");
     if (argc - a != 1 || devices.empty()) {
         log << "Must provide initialization file." << std::endl;
         return 0;
@@ -143,6 +153,8 @@ int main(int argc, char** argv)
     try {
         std::cout << "Creating code from file " << codeFile << std::endl;
         Quantum_LDPC_Code code = Quantum_LDPC_Code::createFromFile(codeFile);
+        if (logical != "file")
+            code = code.withLogicalCheck(logical == "reference" ? QEC_LOGICAL_REFERENCE : QEC_LOGICAL_DEGENERATE);
         int w, W, COUNT, MAX_ITERATIONS;
         float p;
         init >> w >> W >> COUNT >> MAX_ITERATIONS >> p;
@@ -189,7 +201,8 @@ int main(int argc, char** argv)
             str.erase(std::remove(str.begin(), str.end(), ' '), str.end());
             std::cout << str << std::endl;
             std::ofstream outFile(str, std::ios_base::app);
-            CodeStatistics stats = decoder->GetStatistics(w, COUNT, p, MAX_ITERATIONS);
+            CodeStatistics stats = seedFlag ? decoder->GetStatistics(w, COUNT, p, MAX_ITERATIONS, (unsigned int)seed)
+                                            : decoder->GetStatistics(w, COUNT, p, MAX_ITERATIONS);
             outFile << stats << std::endl << std::endl;
         }
     } catch (const std::string& s) {
