@@ -7,8 +7,8 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-f
 CSRC     := qec_ldpc_amd/csrc
 OBJ      := build/obj
 LIB      := qec_ldpc_amd/libqecldpc.so
-OBJS     := $(OBJ)/bp_decode.o $(OBJ)/bp_decode_p61.o $(OBJ)/bp_decode_phase.o $(OBJ)/bp_sparse.o $(OBJ)/schedule.o $(OBJ)/triage.o $(OBJ)/montecarlo.o $(OBJ)/code_model.o $(OBJ)/cpu_engine.o $(OBJ)/capi.o
-HDRS     := include/qec_ldpc.h include/HostDeviceArray.h $(CSRC)/qec_internal.h $(CSRC)/qec_device.h $(CSRC)/qec_mc.h $(CSRC)/qec_launch.h
+OBJS     := $(OBJ)/bp_decode.o $(OBJ)/bp_decode_p61.o $(OBJ)/bp_decode_phase.o $(OBJ)/bp_sparse.o $(OBJ)/schedule.o $(OBJ)/triage.o $(OBJ)/montecarlo.o $(OBJ)/code_model.o $(OBJ)/cpu_engine.o $(OBJ)/osd.o $(OBJ)/osd_host.o $(OBJ)/capi.o
+HDRS     := include/qec_ldpc.h include/HostDeviceArray.h $(CSRC)/qec_internal.h $(CSRC)/qec_device.h $(CSRC)/qec_mc.h $(CSRC)/qec_launch.h $(CSRC)/qec_osd.h
 # build id: hash of every library source and this Makefile (identical for every rebuild of one tree);
 # profiles/pmc_*.json carry it and bench.py uses a profile only with the library it was taken on
 SRCS     := $(sort $(wildcard $(CSRC)/*.hip $(CSRC)/*.cpp $(CSRC)/*.h)) include/qec_ldpc.h include/HostDeviceArray.h Makefile
@@ -46,6 +46,13 @@ $(OBJ)/code_model.o: $(CSRC)/code_model.cpp $(HDRS) | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -x c++ -c $< -o $@
 
 $(OBJ)/cpu_engine.o: $(CSRC)/cpu_engine.cpp $(HDRS) | $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -x c++ -c $< -o $@
+
+# OSD-0 post-processing: the kernels, and the host implementation (CPU engine, cross-check)
+$(OBJ)/osd.o: $(CSRC)/osd.hip $(HDRS) | $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(OBJ)/osd_host.o: $(CSRC)/osd_host.cpp $(HDRS) | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -x c++ -c $< -o $@
 
 $(OBJ)/capi.o: $(SRCS) | $(OBJ)

@@ -227,9 +227,38 @@ int qec_decoder_device(const qec_decoder* dec);         /* HIP device ordinal (o
  *   QEC_OPT_MC_DECODE_TIME (default 1): qec_monte_carlo times its decode kernels with an event pair
  *     per batch (qec_mc_result.decodeSeconds).  0: no events between its launches (each costs the
  *     GPU a few microseconds, ~5 % of a 2^20-sample batch at p = 0.001) and decodeSeconds = 0;
- *     counters unchanged. */
+ *     counters unchanged.
+ *   QEC_OPT_OSD (default 0): BP + OSD-0.  0 = off (nothing changes); 1 = ordered-statistics decoding of
+ *     order 0 as a post-processing stage of the SYNCHRONOUS calls (qec_decode_batch,
+ *     qec_decode_batch_packed, qec_get_statistics, qec_monte_carlo); other values QEC_ERR_ARG.  For every
+ *     sector whose SYNDROME_FAIL bit the main decode left set: the syndrome pair is decoded again with
+ *     QEC_STOP_FIXED, the same errorProbability and QEC_OPT_OSD_ITERATIONS iterations; the columns of
+ *     the sector's matrix are ordered by the final message r(v) at the lowest-index check that contains
+ *     v (key: the bit pattern of r(v) with the sign bit cleared, 0x3F000000 for a NaN, compared as
+ *     unsigned integers, descending, ties by v ascending); walking that order, a column becomes a pivot
+ *     if it is linearly independent (GF(2)) of the pivots so far, up to rank(H); if [H | s] is consistent
+ *     the estimate becomes the unique e supported on the pivots with H e = s and the sector's
+ *     SYNDROME_FAIL bit is cleared, otherwise estimate and flag stay as BP left them (a syndrome entry
+ *     other than 0 or 1 counts as inconsistent).  The other sector, the CONVERGENCE_FAIL bits and iters
+ *     are untouched.  The result depends only on (code, syndrome, p, QEC_OPT_OSD_ITERATIONS), not on the
+ *     engine, the batch or the main decode's path.  qec_monte_carlo then takes the unfused pipeline
+ *     (sample, packed decode, OSD stage, statistics) and reads the number of failed samples back once
+ *     per batch (one host synchronisation per batch); its counters describe the repaired estimates.
+ *     The asynchronous _dev decode entry points IGNORE this option (their no-synchronisation,
+ *     no-allocation contract stands): compose them with qec_osd_dev.  Limits of the kernel: n and the
+ *     checks per sector <= 2048 and the bit-packed [H | s] within one workgroup's 64 KiB of LDS
+ *     (QEC_ERR_UNSUPPORTED otherwise; the CPU engine has no limit).
+ *   QEC_OPT_OSD_ITERATIONS (default 3, >= 1): iterations of the soft decode that orders the columns
+ *     (a few: by the iteration cap a failing sector's fp32 posteriors are saturated and order nothing).
+ *   QEC_OPT_OSD_SECTORS (read only): sectors the OSD stage repaired in the handle's last synchronous
+ *     call (saturating; summed over the parts of a group).
+ *   QEC_OPT_OSD_SWEEP (default 0; measurement only, GPU engines): how the OSD kernel XORs a pivot row
+ *     into the rows that have the column's bit, per chunk of 64 rows.  1 = lanes across the row's words,
+ *     one row after the other; 2 = each lane walks its own row; 0 = whichever takes fewer steps for the
+ *     chunk (osd.hip).  Bit-identical in every state. */
 enum { QEC_OPT_HARD_PATHS = 1, QEC_OPT_CYCLE_JUMP = 2, QEC_OPT_SCHEDULE = 3, QEC_OPT_SECTOR_SPLIT = 4,
-       QEC_OPT_PHASE_STATS = 5, QEC_OPT_TRIAGE = 6, QEC_OPT_LAST_PATH = 7, QEC_OPT_MC_DECODE_TIME = 8 };
+       QEC_OPT_PHASE_STATS = 5, QEC_OPT_TRIAGE = 6, QEC_OPT_LAST_PATH = 7, QEC_OPT_MC_DECODE_TIME = 8,
+       QEC_OPT_OSD = 9, QEC_OPT_OSD_ITERATIONS = 10, QEC_OPT_OSD_SECTORS = 11, QEC_OPT_OSD_SWEEP = 12 };
 enum {
     QEC_PATH_ORDERED = 1,          /* dispatch order pass (schedule.hip) */
     QEC_PATH_SECTOR_ORDER = 2,     /* ... in the per-sector form (each sector's waves by its own weight) */
@@ -238,7 +267,8 @@ enum {
     QEC_PATH_TRIAGE = 16,          /* iteration-0 triage + list-mode decode */
     QEC_PATH_BIT_ROWS = 32,        /* bit-row syndromes in */
     QEC_PATH_SPARSE = 64,          /* sparse-graph engine */
-    QEC_PATH_RECORDS = 128         /* packed decision records out */
+    QEC_PATH_RECORDS = 128,        /* packed decision records out */
+    QEC_PATH_OSD = 256             /* the call ran the OSD stage (QEC_OPT_OSD) */
 };
 int qec_decoder_set_option(qec_decoder* dec, int option, int value);
 int qec_decoder_get_option(const qec_decoder* dec, int option, int* value);
@@ -349,6 +379,18 @@ int qec_statistics_packed_dev(qec_decoder* dec, const uint8_t* errp, const uint8
 enum { QEC_OUTCOME_CORRECTED = 0, QEC_OUTCOME_LOGICAL = 1, QEC_OUTCOME_SYNDROME_FAIL = 2 };
 int qec_logical_packed_dev(qec_decoder* dec, const uint8_t* errp, const uint8_t* records, size_t B,
                            uint8_t* outcome, void* stream);
+/* OSD-0 (QEC_OPT_OSD above, steps "order" to "flag") in place on a decoded DEVICE batch: sX, sZ, eX,
+ * eZ, flags in the layouts of qec_decode_batch_dev, q the soft input in the q_final layout (B x
+ * (numEqsX+numEqsZ) x L; any decode's q_final: the caller chooses the iterations).  Sectors without
+ * their SYNDROME_FAIL bit are skipped.  Enqueued on `stream`: no synchronisation, no allocation
+ * (graph-capturable); nothing is written but the repaired sectors' rows of eX / eZ and their bits of
+ * flags[0, B).  Single-device GPU handle.  Does not update QEC_OPT_OSD_SECTORS. */
+int qec_osd_dev(qec_decoder* dec, const uint8_t* sX, const uint8_t* sZ, size_t B, const float* q,
+                uint8_t* eX, uint8_t* eZ, uint8_t* flags, void* stream);
+/* The same on HOST buffers, synchronous, on any engine (the CPU engine runs the host implementation,
+ * osd_host.cpp; a GPU handle the kernel). */
+int qec_osd(qec_decoder* dec, const uint8_t* sX, const uint8_t* sZ, size_t B, const float* q,
+            uint8_t* eX, uint8_t* eZ, uint8_t* flags);
 /* Decision records for gathering a sharded batch to one rank (the decoded
  * vectors travel bit-packed): out is B x (2 ceil(n/8) + 1) bytes, per syndrome eX packed
  * (bit j of byte k = qubit 8k + j), then eZ packed, then the ErrorCode flags byte.  Device

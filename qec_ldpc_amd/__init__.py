@@ -27,10 +27,11 @@ CONVERGENCE_FAIL_Z = 8
 STOP = {"ref": 0, "fixed": 1, "syndrome": 2}
 ENGINE = {"auto": 0, "circulant": 1, "sparse": 2, "cpu": 3}
 OPTION = {"hard_paths": 1, "cycle_jump": 2, "schedule": 3, "sector_split": 4, "phase_stats": 5, "triage": 6,
-          "last_path": 7, "mc_decode_time": 8}
+          "last_path": 7, "mc_decode_time": 8, "osd": 9, "osd_iterations": 10, "osd_sectors": 11,
+          "osd_sweep": 12}
 # QEC_PATH_* bits of QEC_OPT_LAST_PATH (include/qec_ldpc.h): the launch sequence of the last decode call
 PATH = {"ordered": 1, "sector_order": 2, "split_waves": 4, "sector_launches": 8, "triage": 16, "bit_rows": 32,
-        "sparse": 64, "records": 128}
+        "sparse": 64, "records": 128, "osd": 256}
 
 # every symbol include/qec_ldpc.h declares
 EXPORTS = (
@@ -47,6 +48,7 @@ EXPORTS = (
     "qec_sample_depolarizing_dev", "qec_sample_syndrome_dev", "qec_syndrome_dev", "qec_statistics_dev",
     "qec_statistics_packed_dev", "qec_logical_packed_dev", "qec_pack_decisions_dev",
     "qec_monte_carlo",
+    "qec_osd", "qec_osd_dev",
 )
 # QEC_LOGICAL_*: where a code's logical check comes from (include/qec_ldpc.h)
 LOGICAL = {"file": 0, "reference": 1, "degenerate": 2}
@@ -148,6 +150,8 @@ def lib():
             "qec_statistics_packed_dev": (i, [vp, vp, vp, vp, sz, vp, vp]),
             "qec_logical_packed_dev": (i, [vp, vp, vp, sz, vp, vp]),
             "qec_pack_decisions_dev": (i, [vp, vp, vp, vp, sz, vp, vp]),
+            "qec_osd": (i, [vp, vp, vp, sz, vp, vp, vp, vp]),
+            "qec_osd_dev": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp]),
             "qec_monte_carlo": (i, [vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, f, i, i, sz,
                                     ctypes.POINTER(MCResult)]),
         }
@@ -430,6 +434,21 @@ class DecoderGPU:
                                              _ptr(rec), _ptr(iters)), "qec_decode_batch_packed")
         return rec, iters
 
+    def osd(self, sX, sZ, q, eX, eZ, flags):
+        """OSD-0 (qec_osd) on a decoded host batch: q is the soft input in decode_batch's q layout.
+        Returns repaired copies (eX, eZ, flags); sectors without their SYNDROME_FAIL bit are untouched."""
+        c = self.code
+        sX = np.atleast_2d(sX)
+        B = sX.shape[0]
+        sX = _u8(sX, (B, c.numEqsX))
+        sZ = _u8(sZ, (B, c.numEqsZ))
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(B, (c.numEqsX + c.numEqsZ) * c.L)
+        eX = _u8(eX, (B, c.n)).copy()
+        eZ = _u8(eZ, (B, c.n)).copy()
+        flags = _u8(flags, (B,)).copy()
+        _check(lib().qec_osd(self._h, _ptr(sX), _ptr(sZ), B, _ptr(q), _ptr(eX), _ptr(eZ), _ptr(flags)), "qec_osd")
+        return eX, eZ, flags
+
     # ---- device buffers (torch tensors on this decoder's GPU) ---------------------------
     _binding = False
 
@@ -529,6 +548,20 @@ class DecoderGPU:
                 self._t(iters, "iters", torch.int32, (B, 2), True),
                 self._t(q, "q", torch.float32, (B, (c.numEqsX + c.numEqsZ) * c.L), True))
         return self._issue("qec_decode_bits_packed_dev", (self._h, *args, ctypes.c_void_p(self._stream(stream))))
+
+    def osd_dev(self, sX, sZ, q, eX, eZ, flags, stream=None):
+        """OSD-0 (qec_osd_dev) in place on a decoded device batch: repairs the sectors of eX / eZ whose
+        SYNDROME_FAIL bit is set in flags from the soft input q (decode_batch_dev's q layout) and clears
+        the bit.  Async on `stream`; no allocation (graph-capturable)."""
+        import torch
+        self._single("osd_dev")
+        c = self.code
+        B = sX.shape[0]
+        u8 = torch.uint8
+        args = (self._t(sX, "sX", u8, (B, c.numEqsX)), self._t(sZ, "sZ", u8, (B, c.numEqsZ)), B,
+                self._t(q, "q", torch.float32, (B, (c.numEqsX + c.numEqsZ) * c.L)),
+                self._t(eX, "eX", u8, (B, c.n)), self._t(eZ, "eZ", u8, (B, c.n)), self._t(flags, "flags", u8, (B,)))
+        return self._issue("qec_osd_dev", (self._h, *args, ctypes.c_void_p(self._stream(stream))))
 
     def sample_depolarizing_dev(self, seed, start, p, x, z, stream=None):
         """Device depolarising errors (the gap walk over Philox4x32-10 words, include/qec_ldpc.h)

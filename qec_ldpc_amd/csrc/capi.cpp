@@ -11,6 +11,7 @@
 
 #include "../../include/HostDeviceArray.h"
 #include "qec_internal.h"
+#include "qec_osd.h"
 
 namespace {
 // The handle's own events order work on one device (the workspace's cross-stream event) or time it
@@ -86,6 +87,19 @@ int launch_pack_decisions(const uint8_t* eX, const uint8_t* eZ, const uint8_t* f
                           hipStream_t st);
 int launch_statistics(const Code& c, const uint64_t* imp_cols, const uint8_t* x, const uint8_t* z, const uint8_t* eX,
                       const uint8_t* eZ, const uint8_t* flags, long long B, unsigned long long* counters, hipStream_t st);
+struct OsdDevPlan;
+std::string osd_dev_unsupported(const OsdPlan& P);
+OsdDevPlan* osd_dev_create(const OsdPlan& P);
+void osd_dev_free(OsdDevPlan* D);
+int launch_osd(const OsdDevPlan* D, int sweep, const uint8_t* sX, const uint8_t* sZ, long long B, const float* q,
+               uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint32_t* repaired, hipStream_t st);
+int launch_osd_collect(const uint8_t* rec, int rstride, int n, long long B, int32_t* list, uint32_t* count,
+                       hipStream_t st);
+int launch_osd_gather(const int32_t* list, long long cnt, const uint8_t* sX, const uint8_t* sZ, bool bits, int mX,
+                      int mZ, const uint8_t* rec, int rstride, int n, uint8_t* oX, uint8_t* oZ, uint8_t* fl,
+                      uint8_t* fl0, hipStream_t st);
+int launch_osd_scatter(const int32_t* list, long long cnt, const uint8_t* eX, const uint8_t* eZ, const uint8_t* fl,
+                       const uint8_t* fl0, int n, uint8_t* rec, int rstride, hipStream_t st);
 }  // namespace qec
 
 using namespace qec;
@@ -129,6 +143,20 @@ struct qec_decoder {
     int triage = 1;                 // QEC_OPT_TRIAGE
     int last_path = 0;              // QEC_OPT_LAST_PATH: QEC_PATH_* bits of the last decode call
     int mc_time = 1;                // QEC_OPT_MC_DECODE_TIME
+    int osd = 0;                    // QEC_OPT_OSD (0 off, 1 = OSD-0)
+    int osd_iters = 3;              // QEC_OPT_OSD_ITERATIONS: iterations of the soft decode that feeds the order
+    int osd_sweep = 0;              // QEC_OPT_OSD_SWEEP (0 per-chunk choice, 1 lanes across words, 2 lanes over rows)
+    unsigned long long osd_sectors = 0;  // QEC_OPT_OSD_SECTORS: sectors repaired in the last call
+    // OSD stage: the elimination tables (host; device copy for the GPU engines), the compact
+    // batch of failed samples (syndromes, estimates, flags, soft output) and the failed-record list
+    std::shared_ptr<const OsdPlan> oplan;
+    OsdDevPlan* odev = nullptr;
+    std::string osd_why;            // why the kernel cannot take this code (empty: it can)
+    DeviceArray<uint8_t> osX, osZ, oeX, oeZ, ofl, ofl0, ofs;
+    DeviceArray<float> oq;
+    DeviceArray<int32_t> olist;
+    DeviceArray<uint32_t> ocnt;     // [0] list length, [1] sectors repaired
+    PinnedArray<uint32_t> ocnt_h;
     // workspace shared by every launch of this handle (dispatch order, split-flag merge words,
     // sparse byte staging for packed output); ws_ev marks the last launch that used it, so a call
     // on another stream waits for it (stream-ordered reuse)
@@ -166,6 +194,7 @@ struct qec_decoder {
             if (ws_ev) (void)hipEventDestroy(ws_ev);
             if (stream) (void)hipStreamDestroy(stream);
             if (sparse) sparse_plan_free(sparse);
+            if (odev) osd_dev_free(odev);
         }
     }
 };
@@ -396,6 +425,11 @@ qec_decoder* qec_decoder_create_engine(const qec_code* h, int device, size_t max
         d->engine = QEC_ENGINE_CPU;
         d->cpu = cpu_plan_create(*d->code);
         if (!d->cpu) return nullptr;
+        {
+            auto op = std::make_shared<OsdPlan>();
+            osd_plan_build(*d->code, *op);
+            d->oplan = op;
+        }
         d->variant_name = "cpu (" + std::to_string(cpu_threads()) + " threads) " + d->code->describe();
         return d.release();
     }
@@ -454,6 +488,17 @@ qec_decoder* qec_decoder_create_engine(const qec_code* h, int device, size_t max
         if (d->variant) {
             d->gbar.reserve(2);
             hip_throw(hipMemset(d->gbar.data(), 0, 2 * sizeof(uint32_t)), "grid-barrier words");
+        }
+        // the OSD stage's tables (a code the kernel cannot take keeps the reason for the OSD entry points)
+        auto op = std::make_shared<OsdPlan>();
+        osd_plan_build(*d->code, *op);
+        d->oplan = op;
+        d->osd_why = osd_dev_unsupported(*op);
+        if (d->osd_why.empty()) {
+            d->odev = osd_dev_create(*op);
+            if (!d->odev) return nullptr;
+            d->ocnt.reserve(2);
+            hip_throw(hipMemset(d->ocnt.data(), 0, 2 * sizeof(uint32_t)), "OSD counters");
         }
     } catch (const std::exception& ex) {
         fail(QEC_ERR_HIP, std::string("qec_decoder_create: ") + ex.what());
@@ -557,6 +602,20 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
         d->triage = value;
         return QEC_OK;
     case QEC_OPT_MC_DECODE_TIME: d->mc_time = value != 0; return QEC_OK;
+    case QEC_OPT_OSD:
+        if (value != 0 && value != 1) return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD is 0 (off) or 1 (OSD-0)");
+        if (value && d->parts.empty() && !d->cpu && !d->odev) return fail(QEC_ERR_UNSUPPORTED, d->osd_why);
+        d->osd = value;
+        return QEC_OK;
+    case QEC_OPT_OSD_ITERATIONS:
+        if (value < 1) return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD_ITERATIONS is >= 1");
+        d->osd_iters = value;
+        return QEC_OK;
+    case QEC_OPT_OSD_SECTORS: return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD_SECTORS is read only");
+    case QEC_OPT_OSD_SWEEP:
+        if (value < 0 || value > 2) return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD_SWEEP is 0 .. 2");
+        d->osd_sweep = value;
+        return QEC_OK;
     case QEC_OPT_LAST_PATH: return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_LAST_PATH is read only");
     default: return fail(QEC_ERR_ARG, "qec_decoder_set_option: unknown option");
     }
@@ -574,6 +633,15 @@ int qec_decoder_get_option(const qec_decoder* d, int option, int* value)
     case QEC_OPT_TRIAGE: *value = d->triage; return QEC_OK;
     case QEC_OPT_LAST_PATH: *value = d->parts.empty() ? d->last_path : d->parts[0]->last_path; return QEC_OK;
     case QEC_OPT_MC_DECODE_TIME: *value = d->mc_time; return QEC_OK;
+    case QEC_OPT_OSD: *value = d->osd; return QEC_OK;
+    case QEC_OPT_OSD_ITERATIONS: *value = d->osd_iters; return QEC_OK;
+    case QEC_OPT_OSD_SWEEP: *value = d->osd_sweep; return QEC_OK;
+    case QEC_OPT_OSD_SECTORS: {
+        unsigned long long t = d->osd_sectors;
+        for (const qec_decoder* p : d->parts) t += p->osd_sectors;
+        *value = (int)std::min<unsigned long long>(t, 0x7FFFFFFFull);
+        return QEC_OK;
+    }
     default: return fail(QEC_ERR_ARG, "qec_decoder_get_option: unknown option");
     }
 }
@@ -744,12 +812,185 @@ int single_device_only(const qec_decoder* d, const char* what)
     return QEC_OK;
 }
 
+// ---- OSD stage (QEC_OPT_OSD) ---------------------------------------------------------
+// Samples of the compact batch of failures decoded at once: the soft decode's q_final block is
+// (mX + mZ) L floats per sample (24 KB for P61), so the q buffer stays within 256 MiB.
+size_t osd_chunk(const Code& c)
+{
+    const size_t per = (size_t)(c.mX + c.mZ) * c.L * sizeof(float);
+    return std::max<size_t>(256, std::min<size_t>(65536, ((size_t)256 << 20) / std::max<size_t>(per, 1)));
+}
+
+int osd_reserve(qec_decoder* d, size_t cnt)
+{
+    const Code& c = *d->code;
+    try {
+        d->osX.reserve(cnt * c.mX); d->osZ.reserve(cnt * c.mZ);
+        d->oeX.reserve(cnt * c.n); d->oeZ.reserve(cnt * c.n);
+        d->ofl.reserve(cnt); d->ofl0.reserve(cnt); d->ofs.reserve(cnt);
+        d->oq.reserve(cnt * (size_t)(c.mX + c.mZ) * c.L);
+    } catch (const std::exception& ex) {
+        return fail(QEC_ERR_NOMEM, std::string("OSD workspace: ") + ex.what());
+    }
+    return QEC_OK;
+}
+
+// The compact device batch (osX, osZ: syndromes of samples with a failed sector; ofl: their flags):
+// soft decode with the existing decode path (fixed stop, osd_iters iterations, final messages), then
+// the elimination kernel repairs oeX / oeZ / ofl.  The soft decode's own flags go to a scratch array
+// and its launch sequence does not replace the main decode's in QEC_OPT_LAST_PATH.
+int osd_compact_dev(qec_decoder* d, long long cnt, float p, bool count, hipStream_t st)
+{
+    const int path = d->last_path;
+    int rc = dispatch_decode(d, d->osX.data(), d->osZ.data(), cnt, p, d->osd_iters, QEC_STOP_FIXED, d->oeX.data(),
+                             d->oeZ.data(), d->ofs.data(), nullptr, nullptr, d->oq.data(), st);
+    d->last_path = path;
+    if (rc) return rc;
+    return launch_osd(d->odev, d->osd_sweep, d->osX.data(), d->osZ.data(), cnt, d->oq.data(), d->oeX.data(), d->oeZ.data(),
+                      d->ofl.data(), count ? d->ocnt.data() + 1 : nullptr, st);
+}
+
+// The whole stage on a decoded host batch of one single-device handle (byte form, or records): find
+// the failures, soft decode + OSD of the compact batch in chunks, write the repaired sectors back.
+int osd_repair_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, float p, uint8_t* eX, uint8_t* eZ,
+                    uint8_t* flags, uint8_t* rec)
+{
+    const Code& c = *d->code;
+    const int n = c.n, nb = (n + 7) / 8;
+    const size_t recB = 2 * (size_t)nb + 1, qn = (size_t)(c.mX + c.mZ) * c.L;
+    if (!d->cpu && !d->odev) return fail(QEC_ERR_UNSUPPORTED, d->osd_why);
+    d->last_path |= QEC_PATH_OSD;
+    std::vector<size_t> failed;
+    for (size_t b = 0; b < B; ++b)
+        if ((rec ? rec[b * recB + 2 * nb] : flags[b]) & QEC_SYNDROME_FAIL_XZ) failed.push_back(b);
+    const size_t CH = osd_chunk(c);
+    std::vector<uint8_t> cX, cZ, cEX, cEZ, cF, cF0, cFs;
+    std::vector<float> cq;
+    for (size_t lo = 0; lo < failed.size(); lo += CH) {
+        const size_t cnt = std::min(CH, failed.size() - lo);
+        cX.resize(cnt * c.mX); cZ.resize(cnt * c.mZ); cEX.resize(cnt * n); cEZ.resize(cnt * n);
+        cF.resize(cnt); cF0.resize(cnt);
+        for (size_t i = 0; i < cnt; ++i) {
+            const size_t b = failed[lo + i];
+            std::memcpy(&cX[i * c.mX], sX + b * c.mX, c.mX);
+            std::memcpy(&cZ[i * c.mZ], sZ + b * c.mZ, c.mZ);
+            cF[i] = cF0[i] = rec ? rec[b * recB + 2 * nb] : flags[b];
+        }
+        if (d->cpu) {
+            cq.resize(cnt * qn);
+            cFs.resize(cnt);
+            const int rc = cpu_decode_batch(d->cpu, cX.data(), cZ.data(), (long long)cnt, p, d->osd_iters, QEC_STOP_FIXED,
+                                            cEX.data(), cEZ.data(), cFs.data(), nullptr, nullptr, cq.data(), 0);
+            if (rc) return rc;
+            osd_host_batch(*d->oplan, cX.data(), cZ.data(), (long long)cnt, cq.data(), cEX.data(), cEZ.data(), cF.data(), 0);
+        } else {
+            hipStream_t st = d->stream;
+            int rc = osd_reserve(d, cnt);
+            if (rc) return rc;
+            QEC_HIP_CHECK(hipMemcpyAsync(d->osX.data(), cX.data(), cnt * c.mX, hipMemcpyHostToDevice, st));
+            QEC_HIP_CHECK(hipMemcpyAsync(d->osZ.data(), cZ.data(), cnt * c.mZ, hipMemcpyHostToDevice, st));
+            QEC_HIP_CHECK(hipMemcpyAsync(d->ofl.data(), cF.data(), cnt, hipMemcpyHostToDevice, st));
+            if ((rc = osd_compact_dev(d, (long long)cnt, p, false, st))) return rc;
+            QEC_HIP_CHECK(hipMemcpyAsync(cEX.data(), d->oeX.data(), cnt * n, hipMemcpyDeviceToHost, st));
+            QEC_HIP_CHECK(hipMemcpyAsync(cEZ.data(), d->oeZ.data(), cnt * n, hipMemcpyDeviceToHost, st));
+            QEC_HIP_CHECK(hipMemcpyAsync(cF.data(), d->ofl.data(), cnt, hipMemcpyDeviceToHost, st));
+            QEC_HIP_CHECK(hipStreamSynchronize(st));
+        }
+        for (size_t i = 0; i < cnt; ++i) {
+            const size_t b = failed[lo + i];
+            const uint8_t fixed = cF0[i] & (uint8_t)~cF[i];  // fail bits the stage cleared
+            for (int sec = 0; sec < 2; ++sec) {
+                if (!(fixed & (sec ? QEC_SYNDROME_FAIL_Z : QEC_SYNDROME_FAIL_X))) continue;
+                ++d->osd_sectors;
+                const uint8_t* e = (sec ? cEZ.data() : cEX.data()) + i * n;
+                if (rec) {
+                    uint8_t* o = rec + b * recB + (size_t)sec * nb;
+                    std::memset(o, 0, nb);
+                    for (int v = 0; v < n; ++v) o[v >> 3] |= (uint8_t)((e[v] & 1) << (v & 7));
+                } else {
+                    std::memcpy((sec ? eZ : eX) + b * n, e, n);
+                }
+            }
+            if (rec) rec[b * recB + 2 * nb] = cF[i];
+            else flags[b] = cF[i];
+        }
+    }
+    return QEC_OK;
+}
+
+// The stage on the packed decision records of a device batch (the Monte-Carlo pipeline; syndromes as
+// bit rows or bytes, records at row stride rstride), on the handle's stream: the failed records'
+// indices, then per chunk of them gather, soft decode + OSD, write-back.  Reads the list length back
+// once (one synchronisation per batch).
+int osd_stage_records(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, bool bits, long long B, float p,
+                      uint8_t* rec, int rstride)
+{
+    const Code& c = *d->code;
+    hipStream_t st = d->stream;
+    if (!d->odev) return fail(QEC_ERR_UNSUPPORTED, d->osd_why);
+    if (B <= 0) return QEC_OK;
+    try {
+        d->olist.reserve((size_t)B);
+        d->ocnt_h.reserve(2);
+    } catch (const std::exception& ex) {
+        return fail(QEC_ERR_NOMEM, std::string("OSD workspace: ") + ex.what());
+    }
+    QEC_HIP_CHECK(hipMemsetAsync(d->ocnt.data(), 0, sizeof(uint32_t), st));
+    int rc = launch_osd_collect(rec, rstride, c.n, B, d->olist.data(), d->ocnt.data(), st);
+    if (rc) return rc;
+    QEC_HIP_CHECK(hipMemcpyAsync(d->ocnt_h.data(), d->ocnt.data(), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    QEC_HIP_CHECK(hipStreamSynchronize(st));
+    const size_t total = d->ocnt_h[0];
+    d->last_path |= QEC_PATH_OSD;
+    if (total == 0) return QEC_OK;
+    const size_t CH = osd_chunk(c);
+    if ((rc = osd_reserve(d, std::min(CH, total)))) return rc;
+    for (size_t lo = 0; lo < total; lo += CH) {
+        const long long cnt = (long long)std::min(CH, total - lo);
+        const int32_t* list = d->olist.data() + lo;
+        if ((rc = launch_osd_gather(list, cnt, sX, sZ, bits, c.mX, c.mZ, rec, rstride, c.n, d->osX.data(), d->osZ.data(),
+                                    d->ofl.data(), d->ofl0.data(), st)) ||
+            (rc = osd_compact_dev(d, cnt, p, true, st)) ||
+            (rc = launch_osd_scatter(list, cnt, d->oeX.data(), d->oeZ.data(), d->ofl.data(), d->ofl0.data(), c.n, rec,
+                                     rstride, st)))
+            return rc;
+    }
+    return QEC_OK;
+}
+
+// QEC_OPT_OSD_SECTORS of a device pipeline call: the kernel's counter, zeroed before the call's
+// first batch and read after its last (the stream is synchronised then).
+int osd_count_begin(qec_decoder* d)
+{
+    d->osd_sectors = 0;
+    if (d->osd && d->odev) QEC_HIP_CHECK(hipMemsetAsync(d->ocnt.data() + 1, 0, sizeof(uint32_t), d->stream));
+    return QEC_OK;
+}
+int osd_count_end(qec_decoder* d)
+{
+    if (!d->osd || !d->odev) return QEC_OK;
+    try {
+        d->ocnt_h.reserve(2);
+    } catch (const std::exception& ex) {
+        return fail(QEC_ERR_NOMEM, std::string("OSD workspace: ") + ex.what());
+    }
+    QEC_HIP_CHECK(hipMemcpyAsync(d->ocnt_h.data() + 1, d->ocnt.data() + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    QEC_HIP_CHECK(hipStreamSynchronize(d->stream));
+    d->osd_sectors = d->ocnt_h[1];
+    return QEC_OK;
+}
+
 // Host-buffer decode of one single-device handle (synchronous): stage, decode, copy back.
 int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, float p, int maxIter, int stop,
                 uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* q)
 {
+    d->osd_sectors = 0;
     if (B == 0) return QEC_OK;
-    if (d->cpu) return cpu_decode_batch(d->cpu, sX, sZ, (long long)B, p, maxIter, stop, eX, eZ, flags, rec, iters, q, 0);
+    if (d->cpu) {
+        const int rc = cpu_decode_batch(d->cpu, sX, sZ, (long long)B, p, maxIter, stop, eX, eZ, flags, rec, iters, q, 0);
+        d->last_path = 0;
+        return rc || !d->osd ? rc : osd_repair_host(d, sX, sZ, B, p, eX, eZ, flags, rec);
+    }
     QEC_DEVICE_SCOPE(d->device);
     const Code& c = *d->code;
     const size_t qn = (size_t)(c.mX + c.mZ) * c.L;
@@ -781,7 +1022,7 @@ int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
     if (iters) QEC_HIP_CHECK(hipMemcpyAsync(iters, d->iters.data(), 2 * B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (q) QEC_HIP_CHECK(hipMemcpyAsync(q, d->q.data(), B * qn * sizeof(float), hipMemcpyDeviceToHost, st));
     QEC_HIP_CHECK(hipStreamSynchronize(st));
-    return QEC_OK;
+    return d->osd ? osd_repair_host(d, sX, sZ, B, p, eX, eZ, flags, rec) : QEC_OK;
 }
 
 // Host-buffer decode on every part of a handle: contiguous shards, one host thread per part
@@ -932,7 +1173,7 @@ int mc_batch(qec_decoder* d, McArgsHost h, int src, float p, int maxIter, int st
     // the fused low-p pipeline (triage.hip: sampler, syndromes, iteration-0 triage and the finished
     // samples' statistics in one kernel; the list-mode decode and the survivors' statistics after it)
     uint32_t pats[4];
-    if (bits && stop == QEC_STOP_SYNDROME && want_iters && d->triage != 3 && triage_on(d, p) && maxIter >= 2 &&
+    if (!d->osd && bits && stop == QEC_STOP_SYNDROME && want_iters && d->triage != 3 && triage_on(d, p) && maxIter >= 2 &&
         h.B < (1LL << 31) && decode_has_list(d->variant) && mc_fused_supported(c, rstride) &&
         decode_pattern_masks(d->variant, p, pats)) {
         const long long B = h.B;
@@ -989,6 +1230,9 @@ int mc_batch(qec_decoder* d, McArgsHost h, int src, float p, int maxIter, int st
                          d->mrec.data(), want_iters ? d->mit.data() : nullptr, nullptr, st, bits, rstride);
     if (rc) return rc;
     if (ev1) QEC_HIP_CHECK(hipEventRecord(ev1, st));
+    // QEC_OPT_OSD: repair the records of the samples BP left unsatisfied before they are counted
+    if (d->osd && (rc = osd_stage_records(d, d->msX.data(), d->msZ.data(), bits, h.B, p, d->mrec.data(), rstride)))
+        return rc;
     return launch_statistics_packed(c, d->imp_cols.data(), d->merrp.data(), estride, d->mrec.data(),
                                     want_iters ? d->mit.data() : nullptr, h.B, d->mcount.data(), st, rstride);
 }
@@ -1024,7 +1268,7 @@ int monte_carlo_part(qec_decoder* d, uint64_t seed, uint64_t start, uint64_t cou
     QEC_DEVICE_SCOPE(d->device);
     hipStream_t st = d->stream;
     int rc = mc_reserve(d, (size_t)std::min<uint64_t>(batch, std::max<uint64_t>(count, 1)), 0);
-    if (rc) return rc;
+    if (rc || (rc = osd_count_begin(d))) return rc;
     // decode-kernel time from a ring of event pairs: the host waits only on a pair it reuses,
     // kRing batches behind the launches (no per-batch synchronisation)
     constexpr size_t kRing = 32;
@@ -1058,7 +1302,7 @@ int monte_carlo_part(qec_decoder* d, uint64_t seed, uint64_t start, uint64_t cou
     for (uint64_t j = k > kRing ? k - kRing : 0; d->mc_time && j < k; ++j)
         if ((rc = harvest(j % kRing))) return rc;
     *decode_s = dec;
-    return QEC_OK;
+    return osd_count_end(d);
 }
 
 // GetStatistics on the CPU engine: the same draws, host syndromes, CPU decode (reference stop
@@ -1070,6 +1314,7 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
     const long CH = 1 << 14;
     std::vector<uint8_t> x, z, sx, sz, ex, ez, fl, rx(n), rz(n);
     unsigned long long cn[QEC_MC_NCOUNTERS] = {};
+    unsigned long long repaired = 0;
     Mt19937 g(seed);
     for (long base = 0; base < tested; base += CH) {
         const long cnt = std::min(CH, tested - base);
@@ -1093,6 +1338,12 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
         const int rc = cpu_decode_batch(d->cpu, sx.data(), sz.data(), cnt, p, maxIter, QEC_STOP_REF, ex.data(), ez.data(),
                                         fl.data(), nullptr, nullptr, nullptr, 0);
         if (rc) return rc;
+        if (d->osd) {  // the counters describe the repaired estimates
+            d->osd_sectors = 0;
+            const int rc2 = osd_repair_host(d, sx.data(), sz.data(), (size_t)cnt, p, ex.data(), ez.data(), fl.data(), nullptr);
+            if (rc2) return rc2;
+            repaired += d->osd_sectors;
+        }
         for (long s = 0; s < cnt; ++s) {
             bool ax = false, az = false;
             for (int v = 0; v < n; ++v) {
@@ -1115,6 +1366,8 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
             cn[QEC_MC_CONVZ] += (fl[s] & QEC_CONVERGENCE_FAIL_Z) != 0;
         }
     }
+    d->osd_sectors = repaired;
+    d->last_path = d->osd ? QEC_PATH_OSD : 0;
     std::memset(out, 0, sizeof *out);
     out->randSeed = seed;
     out->numErrorsTested = (uint32_t)tested;
@@ -1165,7 +1418,7 @@ int qec_get_statistics(qec_decoder* d, int W, int numErrors, float p, int maxIte
     for (int j = 0; j < np; ++j) {
         QEC_DEVICE_SCOPE(parts[j]->device);
         int rc = mc_reserve(parts[j], (size_t)cap, W);
-        if (rc) return rc;
+        if (rc || (rc = osd_count_begin(parts[j]))) return rc;
         QEC_HIP_CHECK(hipMemsetAsync(parts[j]->mcount.data(), 0, QEC_MC_NCOUNTERS_ALL * sizeof(unsigned long long),
                                      parts[j]->stream));
         for (int k = 0; k < 2; ++k)
@@ -1215,8 +1468,8 @@ int qec_get_statistics(qec_decoder* d, int W, int numErrors, float p, int maxIte
     for (qec_decoder* pd : parts) {
         QEC_DEVICE_SCOPE(pd->device);
         unsigned long long part[QEC_MC_NCOUNTERS_ALL];
-        const int rc = mc_fetch_counters(pd, part);
-        if (rc) return rc;
+        int rc = mc_fetch_counters(pd, part);
+        if (rc || (rc = osd_count_end(pd))) return rc;
         for (int k = 0; k < QEC_MC_NCOUNTERS_ALL; ++k) cn[k] += part[k];
     }
     const auto t1 = std::chrono::high_resolution_clock::now();
@@ -1372,6 +1625,59 @@ int qec_logical_packed_dev(qec_decoder* d, const uint8_t* errp, const uint8_t* r
     QEC_DEVICE_SCOPE(d->device);
     return launch_logical_outcome(*d->code, d->imp_cols.data(), errp, records, (long long)B, outcome,
                                   static_cast<hipStream_t>(stream));
+}
+
+int qec_osd_dev(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, const float* q, uint8_t* eX, uint8_t* eZ,
+                uint8_t* flags, void* stream)
+{
+    if (!d || (B && (!sX || !sZ || !q || !eX || !eZ || !flags))) return fail(QEC_ERR_ARG, "qec_osd_dev: bad argument");
+    int rc = single_device_only(d, "qec_osd_dev");
+    if (rc) return rc;
+    if (!d->odev) return fail(QEC_ERR_UNSUPPORTED, d->osd_why);
+    QEC_DEVICE_SCOPE(d->device);
+    // the kernel reads only the handle's tables: no workspace, no allocation, nothing to order
+    return launch_osd(d->odev, d->osd_sweep, sX, sZ, (long long)B, q, eX, eZ, flags, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int qec_osd(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, const float* q, uint8_t* eX, uint8_t* eZ,
+            uint8_t* flags)
+{
+    if (!d || (B && (!sX || !sZ || !q || !eX || !eZ || !flags))) return fail(QEC_ERR_ARG, "qec_osd: bad argument");
+    d->osd_sectors = 0;
+    for (qec_decoder* p : d->parts) p->osd_sectors = 0;
+    if (B == 0) return QEC_OK;
+    if (d->cpu) {
+        d->osd_sectors = (unsigned long long)osd_host_batch(*d->oplan, sX, sZ, (long long)B, q, eX, eZ, flags, 0);
+        return QEC_OK;
+    }
+    qec_decoder* w = d->parts.empty() ? d : d->parts[0];  // a group's first part does the work
+    if (!w->odev) return fail(QEC_ERR_UNSUPPORTED, w->osd_why);
+    QEC_DEVICE_SCOPE(w->device);
+    const Code& c = *w->code;
+    const size_t qn = (size_t)(c.mX + c.mZ) * c.L;
+    hipStream_t st = w->stream;
+    std::vector<uint8_t> f0(flags, flags + B);
+    try {
+        DeviceArray<uint8_t> dsX(B * c.mX), dsZ(B * c.mZ), deX(B * c.n), deZ(B * c.n), dfl(B);
+        DeviceArray<float> dq(B * qn);
+        QEC_HIP_CHECK(hipMemcpyAsync(dsX.data(), sX, B * c.mX, hipMemcpyHostToDevice, st));
+        QEC_HIP_CHECK(hipMemcpyAsync(dsZ.data(), sZ, B * c.mZ, hipMemcpyHostToDevice, st));
+        QEC_HIP_CHECK(hipMemcpyAsync(deX.data(), eX, B * c.n, hipMemcpyHostToDevice, st));
+        QEC_HIP_CHECK(hipMemcpyAsync(deZ.data(), eZ, B * c.n, hipMemcpyHostToDevice, st));
+        QEC_HIP_CHECK(hipMemcpyAsync(dfl.data(), flags, B, hipMemcpyHostToDevice, st));
+        QEC_HIP_CHECK(hipMemcpyAsync(dq.data(), q, B * qn * sizeof(float), hipMemcpyHostToDevice, st));
+        const int rc = launch_osd(w->odev, w->osd_sweep, dsX.data(), dsZ.data(), (long long)B, dq.data(), deX.data(), deZ.data(),
+                                  dfl.data(), nullptr, st);
+        if (rc) return rc;
+        QEC_HIP_CHECK(hipMemcpyAsync(eX, deX.data(), B * c.n, hipMemcpyDeviceToHost, st));
+        QEC_HIP_CHECK(hipMemcpyAsync(eZ, deZ.data(), B * c.n, hipMemcpyDeviceToHost, st));
+        QEC_HIP_CHECK(hipMemcpyAsync(flags, dfl.data(), B, hipMemcpyDeviceToHost, st));
+        QEC_HIP_CHECK(hipStreamSynchronize(st));
+    } catch (const std::exception& ex) {
+        return fail(QEC_ERR_NOMEM, std::string("qec_osd: ") + ex.what());
+    }
+    for (size_t b = 0; b < B; ++b) w->osd_sectors += __builtin_popcount((unsigned)(f0[b] & (uint8_t)~flags[b] & QEC_SYNDROME_FAIL_XZ));
+    return QEC_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,50 @@
+// OSD-0 post-processing: the per-sector tables both implementations read,
+// the host implementation (osd_host.cpp) and the kernel launchers (osd.hip).
+#pragma once
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "qec_internal.h"
+
+namespace qec {
+
+// One sector's parity-check matrix for the elimination.
+struct OsdSector {
+    int m = 0, n = 0;
+    int W = 0;                   // 32-bit words per row of the augmented matrix [H | s]: ceil((n + 1) / 32)
+    int rank = 0;                // rank(H) over GF(2): the column walk stops there
+    std::vector<uint32_t> H;     // m x W, bit v of row c = H[c][v] (bit v % 32 of word v / 32); column n clear
+    std::vector<int32_t> qpos;   // n: offset, in one sample's q_final block, of the slot of v at the lowest-index
+                                 // check that contains v; -1 if no check does (key 0.5 then)
+};
+
+struct OsdPlan {
+    OsdSector sec[2];
+    size_t qn = 0;  // floats of one sample's q_final block: (mX + mZ) L
+};
+
+// Sort key of a soft value: NaN -> the pattern of 0.5f, else the sign bit cleared;
+// keys compare as unsigned integers.
+constexpr uint32_t kOsdHalf = 0x3F000000u;
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint32_t osd_key(uint32_t bits)
+{
+    const uint32_t a = bits & 0x7FFFFFFFu;
+    return a > 0x7F800000u ? kOsdHalf : a;
+}
+
+void osd_plan_build(const Code& c, OsdPlan& out);
+
+// Steps 2-6 for one sector of one sample: q = the sample's q_final block, s = the sector's syndrome
+// bytes, e = the sector's estimate (n bytes), rewritten only if [H | s] is consistent.  Returns
+// whether it was.
+bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8_t* e);
+
+// Steps 2-7 on a decoded host batch, in place; returns the number of sectors repaired.
+long long osd_host_batch(const OsdPlan& P, const uint8_t* sX, const uint8_t* sZ, long long B, const float* q,
+                         uint8_t* eX, uint8_t* eZ, uint8_t* flags, int threads);
+
+}  // namespace qec

@@ -21,6 +21,9 @@
 //                      (qec_code_with_logical), so a code file with only its first three lines works.
 //                      reference: what the shipped I-P matrices compute; degenerate: a residual that is
 //                      a product of stabilizers counts as corrected
+//   --osd 0            BP + OSD-0: samples whose syndrome BP leaves unsatisfied are repaired by ordered-statistics
+//                      decoding of order 0 (the only order; QEC_OPT_OSD) before they are counted
+//   --osd-iterations K iterations of the soft decode that orders OSD's columns (default 3; needs --osd)
 // Unknown or inconsistent flags exit with status 2.
 #include <algorithm>
 #include <chrono>
@@ -67,7 +70,8 @@ int usage(const std::string& why)
 {
     std::cerr << why << std::endl
               << "usage: qec_ldpc [--engine gpu|cpu] [--gpus N | --devices i,j,...] [--rng msvc|philox]"
-                 " [--stop ref|fixed|syndrome] [--batch B] [--seed S] [--logical file|reference|degenerate] initFile"
+                 " [--stop ref|fixed|syndrome] [--batch B] [--seed S] [--logical file|reference|degenerate]"
+                 " [--osd 0 [--osd-iterations K]] initFile"
               << std::endl;
     return 2;
 }
@@ -85,7 +89,8 @@ int main(int argc, char** argv)
     log << std::endl << std::ctime(&ts);
     std::vector<int> devices{0};
     std::string engine = "gpu", rng = "msvc", stopName = "ref", logical = "file";
-    bool deviceFlag = false, stopFlag = false, batchFlag = false, seedFlag = false;
+    bool deviceFlag = false, stopFlag = false, batchFlag = false, seedFlag = false, osd = false, osdIterFlag = false;
+    int osdIterations = 3;
     size_t batch = size_t(1) << 20;
     unsigned long long seed = 0x51EC0DE;
     int a = 1;
@@ -122,6 +127,13 @@ int main(int argc, char** argv)
                 if (b <= 0) return usage("--batch: a positive sample count");
                 batch = (size_t)b;
                 batchFlag = true;
+            } else if (flag == "--osd") {
+                if (val != "0") return usage("--osd: the OSD order; only 0 exists");
+                osd = true;
+            } else if (flag == "--osd-iterations") {
+                osdIterations = std::stoi(val);
+                osdIterFlag = true;
+                if (osdIterations < 1) return usage("--osd-iterations: at least 1");
             } else if (flag == "--seed") {
                 seed = std::stoull(val, nullptr, 0);
                 seedFlag = true;
@@ -136,6 +148,7 @@ int main(int argc, char** argv)
     if (rng == "philox" && engine == "cpu") return usage("--rng philox runs on the GPU engine only");
     if (rng == "msvc" && (stopFlag || batchFlag))
         return usage("--stop / --batch apply to --rng philox (GetStatistics keeps the reference stop rule)");
+    if (osdIterFlag && !osd) return usage("--osd-iterations needs --osd 0");
     if (argc - a != 1 || devices.empty()) {
         log << "Must provide initialization file." << std::endl;
         return 0;
@@ -168,6 +181,7 @@ int main(int argc, char** argv)
         }
         if (rng == "philox") {
             DecoderGPU decoder(code, devices);
+            if (osd) decoder.SetOsd(0, osdIterations);
             std::cout << "Engine: " << decoder.Describe() << std::endl;
             const int stop = stopName == "ref" ? QEC_STOP_REF : stopName == "fixed" ? QEC_STOP_FIXED : QEC_STOP_SYNDROME;
             std::stringstream fileName;
@@ -187,11 +201,14 @@ int main(int argc, char** argv)
         }
         std::unique_ptr<Decoder> decoder;
         if (engine == "cpu") {
-            decoder.reset(new DecoderCPU(code));
+            DecoderCPU* c = new DecoderCPU(code);
+            decoder.reset(c);
+            if (osd) c->SetOsd(0, osdIterations);
             std::cout << "Engine: CPU (" << std::thread::hardware_concurrency() << " threads)" << std::endl;
         } else {
             DecoderGPU* g = new DecoderGPU(code, devices);
             decoder.reset(g);
+            if (osd) g->SetOsd(0, osdIterations);
             std::cout << "Engine: " << g->Describe() << std::endl;
         }
         for (; w <= W; ++w) {
