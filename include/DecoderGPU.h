@@ -131,13 +131,14 @@ public:
         qec_decoder_describe(dec_, buf, sizeof buf);
         return buf;
     }
-    // BP + OSD-0 post-processing (QEC_OPT_OSD): order 0 is the only one; a negative order turns it off.
+    // BP + OSD post-processing (QEC_OPT_OSD): order 0 is OSD-0, 1 .. 64 the combination sweep over that
+    // many of the most suspicious non-pivot columns (QEC_OPT_OSD_ORDER); a negative order turns it off.
     // iterations: the soft decode that orders the columns (QEC_OPT_OSD_ITERATIONS, >= 1).
     void SetOsd(int order, int iterations = 3)
     {
-        if (order > 0) throw std::string("SetOsd: only OSD order 0 exists");
+        check(qec_decoder_set_option(dec_, QEC_OPT_OSD_ORDER, order > 0 ? order : 0));
         check(qec_decoder_set_option(dec_, QEC_OPT_OSD_ITERATIONS, iterations));
-        check(qec_decoder_set_option(dec_, QEC_OPT_OSD, order == 0 ? 1 : 0));
+        check(qec_decoder_set_option(dec_, QEC_OPT_OSD, order >= 0 ? 1 : 0));
     }
     qec_decoder* handle() { return dec_; }
 

@@ -255,10 +255,24 @@ int qec_decoder_device(const qec_decoder* dec);         /* HIP device ordinal (o
  *   QEC_OPT_OSD_SWEEP (default 0; measurement only, GPU engines): how the OSD kernel XORs a pivot row
  *     into the rows that have the column's bit, per chunk of 64 rows.  1 = lanes across the row's words,
  *     one row after the other; 2 = each lane walks its own row; 0 = whichever takes fewer steps for the
- *     chunk (osd.hip).  Bit-identical in every state. */
+ *     chunk (osd.hip).  Bit-identical in every state.
+ *   QEC_OPT_OSD_ORDER (default 0, range 0 .. 64; other values QEC_ERR_ARG): lambda of the combination
+ *     sweep (OSD-CS), with effect wherever the OSD stage runs (the synchronous calls under
+ *     QEC_OPT_OSD = 1, qec_osd, qec_osd_dev).  With T = the non-pivot columns in the order of the walk
+ *     (f = n - rank(H) of them), the candidates are, in this index order, the OSD-0 estimate, the f
+ *     estimates with one column of T flipped, and those with two of the first min(lambda, f) columns of T
+ *     flipped ({t_i, t_j}, i < j, by i then j); each is completed on the pivots so that H e = s.  The
+ *     candidate of least Hamming weight becomes the estimate, among equals the lowest index.  0 = OSD-0
+ *     exactly.  The result depends only on (code, syndrome, p, QEC_OPT_OSD_ITERATIONS, lambda).  A group
+ *     applies the value to every part.  On a GPU handle lambda > 0 needs up to 65 more bit vectors over
+ *     the checks in LDS: QEC_ERR_UNSUPPORTED if the sum passes one workgroup's 64 KiB.
+ *   QEC_OPT_OSD_CS_SECTORS (read only): of the sectors counted by QEC_OPT_OSD_SECTORS, those whose
+ *     lightest candidate was not the OSD-0 estimate (index > 0), in the handle's last synchronous call
+ *     (saturating; summed over the parts of a group; zeroed and collected where QEC_OPT_OSD_SECTORS is). */
 enum { QEC_OPT_HARD_PATHS = 1, QEC_OPT_CYCLE_JUMP = 2, QEC_OPT_SCHEDULE = 3, QEC_OPT_SECTOR_SPLIT = 4,
        QEC_OPT_PHASE_STATS = 5, QEC_OPT_TRIAGE = 6, QEC_OPT_LAST_PATH = 7, QEC_OPT_MC_DECODE_TIME = 8,
-       QEC_OPT_OSD = 9, QEC_OPT_OSD_ITERATIONS = 10, QEC_OPT_OSD_SECTORS = 11, QEC_OPT_OSD_SWEEP = 12 };
+       QEC_OPT_OSD = 9, QEC_OPT_OSD_ITERATIONS = 10, QEC_OPT_OSD_SECTORS = 11, QEC_OPT_OSD_SWEEP = 12,
+       QEC_OPT_OSD_ORDER = 13, QEC_OPT_OSD_CS_SECTORS = 14 };
 enum {
     QEC_PATH_ORDERED = 1,          /* dispatch order pass (schedule.hip) */
     QEC_PATH_SECTOR_ORDER = 2,     /* ... in the per-sector form (each sector's waves by its own weight) */
@@ -379,12 +393,14 @@ int qec_statistics_packed_dev(qec_decoder* dec, const uint8_t* errp, const uint8
 enum { QEC_OUTCOME_CORRECTED = 0, QEC_OUTCOME_LOGICAL = 1, QEC_OUTCOME_SYNDROME_FAIL = 2 };
 int qec_logical_packed_dev(qec_decoder* dec, const uint8_t* errp, const uint8_t* records, size_t B,
                            uint8_t* outcome, void* stream);
-/* OSD-0 (QEC_OPT_OSD above, steps "order" to "flag") in place on a decoded DEVICE batch: sX, sZ, eX,
+/* OSD (QEC_OPT_OSD above, steps "order" to "flag"; the handle's QEC_OPT_OSD_ORDER chooses OSD-0 or the
+ * combination sweep, read at the call as QEC_OPT_OSD_SWEEP is) in place on a decoded DEVICE batch: sX, sZ, eX,
  * eZ, flags in the layouts of qec_decode_batch_dev, q the soft input in the q_final layout (B x
  * (numEqsX+numEqsZ) x L; any decode's q_final: the caller chooses the iterations).  Sectors without
  * their SYNDROME_FAIL bit are skipped.  Enqueued on `stream`: no synchronisation, no allocation
  * (graph-capturable); nothing is written but the repaired sectors' rows of eX / eZ and their bits of
- * flags[0, B).  Single-device GPU handle.  Does not update QEC_OPT_OSD_SECTORS. */
+ * flags[0, B).  Single-device GPU handle.  Updates neither QEC_OPT_OSD_SECTORS nor
+ * QEC_OPT_OSD_CS_SECTORS. */
 int qec_osd_dev(qec_decoder* dec, const uint8_t* sX, const uint8_t* sZ, size_t B, const float* q,
                 uint8_t* eX, uint8_t* eZ, uint8_t* flags, void* stream);
 /* The same on HOST buffers, synchronous, on any engine (the CPU engine runs the host implementation,

@@ -28,7 +28,8 @@ STOP = {"ref": 0, "fixed": 1, "syndrome": 2}
 ENGINE = {"auto": 0, "circulant": 1, "sparse": 2, "cpu": 3}
 OPTION = {"hard_paths": 1, "cycle_jump": 2, "schedule": 3, "sector_split": 4, "phase_stats": 5, "triage": 6,
           "last_path": 7, "mc_decode_time": 8, "osd": 9, "osd_iterations": 10, "osd_sectors": 11,
-          "osd_sweep": 12}
+          "osd_sweep": 12, "osd_order": 13, "osd_cs_sectors": 14}
+OPTIONS = OPTION
 # QEC_PATH_* bits of QEC_OPT_LAST_PATH (include/qec_ldpc.h): the launch sequence of the last decode call
 PATH = {"ordered": 1, "sector_order": 2, "split_waves": 4, "sector_launches": 8, "triage": 16, "bit_rows": 32,
         "sparse": 64, "records": 128, "osd": 256}
@@ -435,8 +436,11 @@ class DecoderGPU:
         return rec, iters
 
     def osd(self, sX, sZ, q, eX, eZ, flags):
-        """OSD-0 (qec_osd) on a decoded host batch: q is the soft input in decode_batch's q layout.
-        Returns repaired copies (eX, eZ, flags); sectors without their SYNDROME_FAIL bit are untouched."""
+        """OSD (qec_osd) on a decoded host batch: q is the soft input in decode_batch's q layout.
+        Returns repaired copies (eX, eZ, flags); sectors without their SYNDROME_FAIL bit are untouched.
+        set_option("osd_order", lam) chooses OSD-0 (0, the default) or the combination sweep OSD-CS over
+        the lam <= 64 most suspicious non-pivot columns; get_option("osd_sectors") / ("osd_cs_sectors")
+        then give the sectors repaired and those whose lightest candidate was not the OSD-0 estimate."""
         c = self.code
         sX = np.atleast_2d(sX)
         B = sX.shape[0]
@@ -550,9 +554,11 @@ class DecoderGPU:
         return self._issue("qec_decode_bits_packed_dev", (self._h, *args, ctypes.c_void_p(self._stream(stream))))
 
     def osd_dev(self, sX, sZ, q, eX, eZ, flags, stream=None):
-        """OSD-0 (qec_osd_dev) in place on a decoded device batch: repairs the sectors of eX / eZ whose
+        """OSD (qec_osd_dev) in place on a decoded device batch: repairs the sectors of eX / eZ whose
         SYNDROME_FAIL bit is set in flags from the soft input q (decode_batch_dev's q layout) and clears
-        the bit.  Async on `stream`; no allocation (graph-capturable)."""
+        the bit.  The handle's "osd_order" option (read at the call) chooses OSD-0 or the combination
+        sweep.  Async on `stream`; no allocation (graph-capturable); updates neither "osd_sectors" nor
+        "osd_cs_sectors"."""
         import torch
         self._single("osd_dev")
         c = self.code

@@ -88,11 +88,11 @@ int launch_pack_decisions(const uint8_t* eX, const uint8_t* eZ, const uint8_t* f
 int launch_statistics(const Code& c, const uint64_t* imp_cols, const uint8_t* x, const uint8_t* z, const uint8_t* eX,
                       const uint8_t* eZ, const uint8_t* flags, long long B, unsigned long long* counters, hipStream_t st);
 struct OsdDevPlan;
-std::string osd_dev_unsupported(const OsdPlan& P);
+std::string osd_dev_unsupported(const OsdPlan& P, int order);
 OsdDevPlan* osd_dev_create(const OsdPlan& P);
 void osd_dev_free(OsdDevPlan* D);
-int launch_osd(const OsdDevPlan* D, int sweep, const uint8_t* sX, const uint8_t* sZ, long long B, const float* q,
-               uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint32_t* repaired, hipStream_t st);
+int launch_osd(const OsdDevPlan* D, int sweep, int order, const uint8_t* sX, const uint8_t* sZ, long long B, const float* q,
+               uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint32_t* repaired, uint32_t* swept, hipStream_t st);
 int launch_osd_collect(const uint8_t* rec, int rstride, int n, long long B, int32_t* list, uint32_t* count,
                        hipStream_t st);
 int launch_osd_gather(const int32_t* list, long long cnt, const uint8_t* sX, const uint8_t* sZ, bool bits, int mX,
@@ -147,6 +147,8 @@ struct qec_decoder {
     int osd_iters = 3;              // QEC_OPT_OSD_ITERATIONS: iterations of the soft decode that feeds the order
     int osd_sweep = 0;              // QEC_OPT_OSD_SWEEP (0 per-chunk choice, 1 lanes across words, 2 lanes over rows)
     unsigned long long osd_sectors = 0;  // QEC_OPT_OSD_SECTORS: sectors repaired in the last call
+    int osd_order = 0;              // QEC_OPT_OSD_ORDER: lambda of the combination sweep, 0 = OSD-0
+    unsigned long long osd_cs_sectors = 0;  // QEC_OPT_OSD_CS_SECTORS: of those, the winner was not the OSD-0 estimate
     // OSD stage: the elimination tables (host; device copy for the GPU engines), the compact
     // batch of failed samples (syndromes, estimates, flags, soft output) and the failed-record list
     std::shared_ptr<const OsdPlan> oplan;
@@ -155,7 +157,7 @@ struct qec_decoder {
     DeviceArray<uint8_t> osX, osZ, oeX, oeZ, ofl, ofl0, ofs;
     DeviceArray<float> oq;
     DeviceArray<int32_t> olist;
-    DeviceArray<uint32_t> ocnt;     // [0] list length, [1] sectors repaired
+    DeviceArray<uint32_t> ocnt;     // [0] list length, [1] sectors repaired, [2] of those swept (index > 0)
     PinnedArray<uint32_t> ocnt_h;
     // workspace shared by every launch of this handle (dispatch order, split-flag merge words,
     // sparse byte staging for packed output); ws_ev marks the last launch that used it, so a call
@@ -493,12 +495,12 @@ qec_decoder* qec_decoder_create_engine(const qec_code* h, int device, size_t max
         auto op = std::make_shared<OsdPlan>();
         osd_plan_build(*d->code, *op);
         d->oplan = op;
-        d->osd_why = osd_dev_unsupported(*op);
+        d->osd_why = osd_dev_unsupported(*op, 0);
         if (d->osd_why.empty()) {
             d->odev = osd_dev_create(*op);
             if (!d->odev) return nullptr;
-            d->ocnt.reserve(2);
-            hip_throw(hipMemset(d->ocnt.data(), 0, 2 * sizeof(uint32_t)), "OSD counters");
+            d->ocnt.reserve(3);
+            hip_throw(hipMemset(d->ocnt.data(), 0, 3 * sizeof(uint32_t)), "OSD counters");
         }
     } catch (const std::exception& ex) {
         fail(QEC_ERR_HIP, std::string("qec_decoder_create: ") + ex.what());
@@ -616,6 +618,16 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
         if (value < 0 || value > 2) return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD_SWEEP is 0 .. 2");
         d->osd_sweep = value;
         return QEC_OK;
+    case QEC_OPT_OSD_ORDER:
+        if (value < 0 || value > kOsdMaxOrder) return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD_ORDER is 0 .. 64");
+        if (value && d->odev) {  // the sweep's column vectors share the workgroup's LDS with [H | s]
+            const std::string why = osd_dev_unsupported(*d->oplan, value);
+            if (!why.empty()) return fail(QEC_ERR_UNSUPPORTED, why);
+        }
+        d->osd_order = value;
+        return QEC_OK;
+    case QEC_OPT_OSD_CS_SECTORS:
+        return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD_CS_SECTORS is read only");
     case QEC_OPT_LAST_PATH: return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_LAST_PATH is read only");
     default: return fail(QEC_ERR_ARG, "qec_decoder_set_option: unknown option");
     }
@@ -639,6 +651,13 @@ int qec_decoder_get_option(const qec_decoder* d, int option, int* value)
     case QEC_OPT_OSD_SECTORS: {
         unsigned long long t = d->osd_sectors;
         for (const qec_decoder* p : d->parts) t += p->osd_sectors;
+        *value = (int)std::min<unsigned long long>(t, 0x7FFFFFFFull);
+        return QEC_OK;
+    }
+    case QEC_OPT_OSD_ORDER: *value = d->osd_order; return QEC_OK;
+    case QEC_OPT_OSD_CS_SECTORS: {
+        unsigned long long t = d->osd_cs_sectors;
+        for (const qec_decoder* p : d->parts) t += p->osd_cs_sectors;
         *value = (int)std::min<unsigned long long>(t, 0x7FFFFFFFull);
         return QEC_OK;
     }
@@ -837,7 +856,8 @@ int osd_reserve(qec_decoder* d, size_t cnt)
 
 // The compact device batch (osX, osZ: syndromes of samples with a failed sector; ofl: their flags):
 // soft decode with the existing decode path (fixed stop, osd_iters iterations, final messages), then
-// the elimination kernel repairs oeX / oeZ / ofl.  The soft decode's own flags go to a scratch array
+// the elimination kernel repairs oeX / oeZ / ofl (and adds the swept sectors to ocnt[2]; `count`: the
+// repaired ones to ocnt[1]).  The soft decode's own flags go to a scratch array
 // and its launch sequence does not replace the main decode's in QEC_OPT_LAST_PATH.
 int osd_compact_dev(qec_decoder* d, long long cnt, float p, bool count, hipStream_t st)
 {
@@ -846,8 +866,8 @@ int osd_compact_dev(qec_decoder* d, long long cnt, float p, bool count, hipStrea
                              d->oeZ.data(), d->ofs.data(), nullptr, nullptr, d->oq.data(), st);
     d->last_path = path;
     if (rc) return rc;
-    return launch_osd(d->odev, d->osd_sweep, d->osX.data(), d->osZ.data(), cnt, d->oq.data(), d->oeX.data(), d->oeZ.data(),
-                      d->ofl.data(), count ? d->ocnt.data() + 1 : nullptr, st);
+    return launch_osd(d->odev, d->osd_sweep, d->osd_order, d->osX.data(), d->osZ.data(), cnt, d->oq.data(), d->oeX.data(),
+                      d->oeZ.data(), d->ofl.data(), count ? d->ocnt.data() + 1 : nullptr, d->ocnt.data() + 2, st);
 }
 
 // The whole stage on a decoded host batch of one single-device handle (byte form, or records): find
@@ -882,7 +902,10 @@ int osd_repair_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t
             const int rc = cpu_decode_batch(d->cpu, cX.data(), cZ.data(), (long long)cnt, p, d->osd_iters, QEC_STOP_FIXED,
                                             cEX.data(), cEZ.data(), cFs.data(), nullptr, nullptr, cq.data(), 0);
             if (rc) return rc;
-            osd_host_batch(*d->oplan, cX.data(), cZ.data(), (long long)cnt, cq.data(), cEX.data(), cEZ.data(), cF.data(), 0);
+            long long swept = 0;
+            osd_host_batch(*d->oplan, cX.data(), cZ.data(), (long long)cnt, cq.data(), cEX.data(), cEZ.data(), cF.data(), 0,
+                           d->osd_order, &swept);
+            d->osd_cs_sectors += (unsigned long long)swept;
         } else {
             hipStream_t st = d->stream;
             int rc = osd_reserve(d, cnt);
@@ -890,11 +913,15 @@ int osd_repair_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t
             QEC_HIP_CHECK(hipMemcpyAsync(d->osX.data(), cX.data(), cnt * c.mX, hipMemcpyHostToDevice, st));
             QEC_HIP_CHECK(hipMemcpyAsync(d->osZ.data(), cZ.data(), cnt * c.mZ, hipMemcpyHostToDevice, st));
             QEC_HIP_CHECK(hipMemcpyAsync(d->ofl.data(), cF.data(), cnt, hipMemcpyHostToDevice, st));
+            QEC_HIP_CHECK(hipMemsetAsync(d->ocnt.data() + 2, 0, sizeof(uint32_t), st));
             if ((rc = osd_compact_dev(d, (long long)cnt, p, false, st))) return rc;
+            uint32_t swept = 0;
+            QEC_HIP_CHECK(hipMemcpyAsync(&swept, d->ocnt.data() + 2, sizeof swept, hipMemcpyDeviceToHost, st));
             QEC_HIP_CHECK(hipMemcpyAsync(cEX.data(), d->oeX.data(), cnt * n, hipMemcpyDeviceToHost, st));
             QEC_HIP_CHECK(hipMemcpyAsync(cEZ.data(), d->oeZ.data(), cnt * n, hipMemcpyDeviceToHost, st));
             QEC_HIP_CHECK(hipMemcpyAsync(cF.data(), d->ofl.data(), cnt, hipMemcpyDeviceToHost, st));
             QEC_HIP_CHECK(hipStreamSynchronize(st));
+            d->osd_cs_sectors += swept;
         }
         for (size_t i = 0; i < cnt; ++i) {
             const size_t b = failed[lo + i];
@@ -931,7 +958,7 @@ int osd_stage_records(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, bool
     if (B <= 0) return QEC_OK;
     try {
         d->olist.reserve((size_t)B);
-        d->ocnt_h.reserve(2);
+        d->ocnt_h.reserve(3);
     } catch (const std::exception& ex) {
         return fail(QEC_ERR_NOMEM, std::string("OSD workspace: ") + ex.what());
     }
@@ -958,25 +985,27 @@ int osd_stage_records(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, bool
     return QEC_OK;
 }
 
-// QEC_OPT_OSD_SECTORS of a device pipeline call: the kernel's counter, zeroed before the call's
-// first batch and read after its last (the stream is synchronised then).
+// QEC_OPT_OSD_SECTORS and QEC_OPT_OSD_CS_SECTORS of a device pipeline call: the kernel's counters,
+// zeroed before the call's first batch and read after its last (the stream is synchronised then).
 int osd_count_begin(qec_decoder* d)
 {
     d->osd_sectors = 0;
-    if (d->osd && d->odev) QEC_HIP_CHECK(hipMemsetAsync(d->ocnt.data() + 1, 0, sizeof(uint32_t), d->stream));
+    d->osd_cs_sectors = 0;
+    if (d->osd && d->odev) QEC_HIP_CHECK(hipMemsetAsync(d->ocnt.data() + 1, 0, 2 * sizeof(uint32_t), d->stream));
     return QEC_OK;
 }
 int osd_count_end(qec_decoder* d)
 {
     if (!d->osd || !d->odev) return QEC_OK;
     try {
-        d->ocnt_h.reserve(2);
+        d->ocnt_h.reserve(3);
     } catch (const std::exception& ex) {
         return fail(QEC_ERR_NOMEM, std::string("OSD workspace: ") + ex.what());
     }
-    QEC_HIP_CHECK(hipMemcpyAsync(d->ocnt_h.data() + 1, d->ocnt.data() + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    QEC_HIP_CHECK(hipMemcpyAsync(d->ocnt_h.data() + 1, d->ocnt.data() + 1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
     QEC_HIP_CHECK(hipStreamSynchronize(d->stream));
     d->osd_sectors = d->ocnt_h[1];
+    d->osd_cs_sectors = d->ocnt_h[2];
     return QEC_OK;
 }
 
@@ -985,6 +1014,7 @@ int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
                 uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* q)
 {
     d->osd_sectors = 0;
+    d->osd_cs_sectors = 0;
     if (B == 0) return QEC_OK;
     if (d->cpu) {
         const int rc = cpu_decode_batch(d->cpu, sX, sZ, (long long)B, p, maxIter, stop, eX, eZ, flags, rec, iters, q, 0);
@@ -1314,7 +1344,7 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
     const long CH = 1 << 14;
     std::vector<uint8_t> x, z, sx, sz, ex, ez, fl, rx(n), rz(n);
     unsigned long long cn[QEC_MC_NCOUNTERS] = {};
-    unsigned long long repaired = 0;
+    unsigned long long repaired = 0, swept = 0;
     Mt19937 g(seed);
     for (long base = 0; base < tested; base += CH) {
         const long cnt = std::min(CH, tested - base);
@@ -1340,9 +1370,11 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
         if (rc) return rc;
         if (d->osd) {  // the counters describe the repaired estimates
             d->osd_sectors = 0;
+            d->osd_cs_sectors = 0;
             const int rc2 = osd_repair_host(d, sx.data(), sz.data(), (size_t)cnt, p, ex.data(), ez.data(), fl.data(), nullptr);
             if (rc2) return rc2;
             repaired += d->osd_sectors;
+            swept += d->osd_cs_sectors;
         }
         for (long s = 0; s < cnt; ++s) {
             bool ax = false, az = false;
@@ -1367,6 +1399,7 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
         }
     }
     d->osd_sectors = repaired;
+    d->osd_cs_sectors = swept;
     d->last_path = d->osd ? QEC_PATH_OSD : 0;
     std::memset(out, 0, sizeof *out);
     out->randSeed = seed;
@@ -1636,18 +1669,22 @@ int qec_osd_dev(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
     if (!d->odev) return fail(QEC_ERR_UNSUPPORTED, d->osd_why);
     QEC_DEVICE_SCOPE(d->device);
     // the kernel reads only the handle's tables: no workspace, no allocation, nothing to order
-    return launch_osd(d->odev, d->osd_sweep, sX, sZ, (long long)B, q, eX, eZ, flags, nullptr, static_cast<hipStream_t>(stream));
+    return launch_osd(d->odev, d->osd_sweep, d->osd_order, sX, sZ, (long long)B, q, eX, eZ, flags, nullptr, nullptr,
+                      static_cast<hipStream_t>(stream));
 }
 
 int qec_osd(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, const float* q, uint8_t* eX, uint8_t* eZ,
             uint8_t* flags)
 {
     if (!d || (B && (!sX || !sZ || !q || !eX || !eZ || !flags))) return fail(QEC_ERR_ARG, "qec_osd: bad argument");
-    d->osd_sectors = 0;
-    for (qec_decoder* p : d->parts) p->osd_sectors = 0;
+    d->osd_sectors = d->osd_cs_sectors = 0;
+    for (qec_decoder* p : d->parts) p->osd_sectors = p->osd_cs_sectors = 0;
     if (B == 0) return QEC_OK;
     if (d->cpu) {
-        d->osd_sectors = (unsigned long long)osd_host_batch(*d->oplan, sX, sZ, (long long)B, q, eX, eZ, flags, 0);
+        long long swept = 0;
+        d->osd_sectors = (unsigned long long)osd_host_batch(*d->oplan, sX, sZ, (long long)B, q, eX, eZ, flags, 0,
+                                                            d->osd_order, &swept);
+        d->osd_cs_sectors = (unsigned long long)swept;
         return QEC_OK;
     }
     qec_decoder* w = d->parts.empty() ? d : d->parts[0];  // a group's first part does the work
@@ -1657,6 +1694,7 @@ int qec_osd(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, cons
     const size_t qn = (size_t)(c.mX + c.mZ) * c.L;
     hipStream_t st = w->stream;
     std::vector<uint8_t> f0(flags, flags + B);
+    uint32_t swept = 0;
     try {
         DeviceArray<uint8_t> dsX(B * c.mX), dsZ(B * c.mZ), deX(B * c.n), deZ(B * c.n), dfl(B);
         DeviceArray<float> dq(B * qn);
@@ -1666,9 +1704,11 @@ int qec_osd(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, cons
         QEC_HIP_CHECK(hipMemcpyAsync(deZ.data(), eZ, B * c.n, hipMemcpyHostToDevice, st));
         QEC_HIP_CHECK(hipMemcpyAsync(dfl.data(), flags, B, hipMemcpyHostToDevice, st));
         QEC_HIP_CHECK(hipMemcpyAsync(dq.data(), q, B * qn * sizeof(float), hipMemcpyHostToDevice, st));
-        const int rc = launch_osd(w->odev, w->osd_sweep, dsX.data(), dsZ.data(), (long long)B, dq.data(), deX.data(), deZ.data(),
-                                  dfl.data(), nullptr, st);
+        QEC_HIP_CHECK(hipMemsetAsync(w->ocnt.data() + 2, 0, sizeof(uint32_t), st));
+        const int rc = launch_osd(w->odev, w->osd_sweep, w->osd_order, dsX.data(), dsZ.data(), (long long)B, dq.data(),
+                                  deX.data(), deZ.data(), dfl.data(), nullptr, w->ocnt.data() + 2, st);
         if (rc) return rc;
+        QEC_HIP_CHECK(hipMemcpyAsync(&swept, w->ocnt.data() + 2, sizeof swept, hipMemcpyDeviceToHost, st));
         QEC_HIP_CHECK(hipMemcpyAsync(eX, deX.data(), B * c.n, hipMemcpyDeviceToHost, st));
         QEC_HIP_CHECK(hipMemcpyAsync(eZ, deZ.data(), B * c.n, hipMemcpyDeviceToHost, st));
         QEC_HIP_CHECK(hipMemcpyAsync(flags, dfl.data(), B, hipMemcpyDeviceToHost, st));
@@ -1677,6 +1717,7 @@ int qec_osd(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, cons
         return fail(QEC_ERR_NOMEM, std::string("qec_osd: ") + ex.what());
     }
     for (size_t b = 0; b < B; ++b) w->osd_sectors += __builtin_popcount((unsigned)(f0[b] & (uint8_t)~flags[b] & QEC_SYNDROME_FAIL_XZ));
+    w->osd_cs_sectors = swept;
     return QEC_OK;
 }
 

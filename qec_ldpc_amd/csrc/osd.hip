@@ -1,6 +1,7 @@
-// OSD-0 post-processing on the device: one wave64 per failed sector
-// eliminates the bit-packed augmented matrix [H | s] in LDS, walking the columns in the order of the
-// soft input.  Beside it the three small kernels of the Monte-Carlo path (failed-record list, syndrome
+// OSD post-processing on the device (DESIGN.md sections 1.2, 1.3, section 6): one wave64 per failed
+// sector eliminates the bit-packed augmented matrix [H | s] in LDS, walking the columns in the order of
+// the soft input; with QEC_OPT_OSD_ORDER > 0 the same wave then scores the combination sweep on the
+// reduced matrix.  Beside it the three small kernels of the Monte-Carlo path (failed-record list, syndrome
 // gather, write-back into the packed decision records).  gfx950 only.
 #include <hip/hip_runtime.h>
 
@@ -26,6 +27,12 @@ struct OsdDev {
     int sweep;                // QEC_OPT_OSD_SWEEP: how a pivot row is XORed into the rows with the bit
 };
 
+// What the sweep takes beside it (behind the arguments the order-0 kernel always had).
+struct OsdCs {
+    int order;                // QEC_OPT_OSD_ORDER: lambda of the combination sweep
+    int RWs;                  // LDS stride in words of a column's bit vector over the rows (odd, see osd_rws)
+};
+
 struct OsdDevPlan {
     OsdDev d{};
     void* mem = nullptr;      // one allocation behind the four tables
@@ -45,20 +52,34 @@ int launch_check(const char* what)
     return QEC_OK;
 }
 
-// LDS image of one wave (32-bit words): rows [mmax][Ws] | keys [n] (later the estimate's bytes) |
-// order [n] u16 | pivcol [mmax] u16
-__host__ __device__ inline uint32_t osd_lds_words(int mmax, int n, int Ws)
+// Words of a bit vector over the rows, one 64-bit ballot per chunk of 64 rows, padded to an odd count
+// so that lanes reading a vector each (the pairs) spread over the banks.
+__host__ __device__ inline int osd_rws(int mmax) { return (2 * ((mmax + 63) >> 6)) | 1; }
+
+// LDS image of one wave (32-bit words): rows [mmax][Ws] | keys [n] (later the estimate's bytes [n]
+// and, for the sweep, T [n] u16 behind them: ceil(n / 4) + ceil(n / 2) <= n words for n >= 2) |
+// order [n] u16 | pivcol [mmax] u16 | for lambda > 0 the bit vectors of the first lambda columns of T
+// and of s': [lambda + 1][RWs]
+__host__ __device__ inline uint32_t osd_lds_words(int mmax, int n, int Ws, int order)
 {
-    return (uint32_t)mmax * Ws + n + (n + 1) / 2 + (mmax + 1) / 2;
+    return (uint32_t)mmax * Ws + n + (n + 1) / 2 + (mmax + 1) / 2 +
+           (order > 0 ? (uint32_t)(order + 1) * osd_rws(mmax) : 0u);
 }
 
 // Block t: sample t / 2, sector t % 2.  A sector without its SYNDROME_FAIL bit exits at once, so the
 // launch needs no list of failures.  Writes: e[b][0, n) and the sector's bit of flags[b], both only
-// when [H | s] is consistent; *repaired (nullable) counts those sectors.
-__global__ __launch_bounds__(64) void osd0_kernel(OsdDev P, const uint8_t* __restrict__ sX,
-                                                  const uint8_t* __restrict__ sZ, long long B,
-                                                  const float* __restrict__ q, uint8_t* __restrict__ eX,
-                                                  uint8_t* __restrict__ eZ, uint8_t* flags, uint32_t* repaired)
+// when [H | s] is consistent; *repaired (nullable) counts those sectors.  CS: the combination sweep
+// of section 1.3 between the consistency test and the write-out; *swept (nullable) counts the sectors
+// whose lightest candidate is not the OSD-0 estimate.
+// The kernel itself is the template (osd_kernel<false> is the order-0 kernel, instruction for
+// instruction what it was before the sweep existed: a shared body inlined into two kernels compiled
+// to a slower elimination loop).
+template <bool CS>
+__global__ __launch_bounds__(64) void osd_kernel(OsdDev P, const uint8_t* __restrict__ sX,
+                                                 const uint8_t* __restrict__ sZ, long long B,
+                                                 const float* __restrict__ q, uint8_t* __restrict__ eX,
+                                                 uint8_t* __restrict__ eZ, uint8_t* flags, uint32_t* repaired,
+                                                 OsdCs C, uint32_t* swept)
 {
     extern __shared__ uint32_t lds[];
     const long long b = (long long)(blockIdx.x >> 1);
@@ -167,15 +188,129 @@ __global__ __launch_bounds__(64) void osd0_kernel(OsdDev P, const uint8_t* __res
         incons |= r < m && !((used >> k) & 1u) && (rows[r * Ws + sw] & sbit);
     }
     if (__ballot(incons)) return;
-    // the estimate in LDS (over the keys), then out
     uint8_t* eb = reinterpret_cast<uint8_t*>(keys);
+    int fa = -1, fb = -1;  // CS: the columns the lightest candidate flips (wave-uniform)
+    if constexpr (CS) {
+        // T = the non-pivot columns in the walk's order, behind the estimate's bytes: mark the pivot
+        // columns in those bytes, then compact `order` a ballot of 64 entries at a time
+        uint16_t* T = reinterpret_cast<uint16_t*>(keys + (n + 3) / 4);
+        for (int v = lane; v < n; v += 64) eb[v] = 0;
+        wave_sync();
+        for (int k = 0; k < nchunk; ++k) {
+            const int r = (k << 6) + lane;
+            if (r < m && ((used >> k) & 1u)) eb[pivcol[r]] = 1;
+        }
+        wave_sync();
+        int f = 0;
+        for (int t0 = 0; t0 < n; t0 += 64) {
+            const int t = t0 + lane;
+            const int v = t < n ? order[t] : 0;
+            const bool free = t < n && !eb[v];
+            const unsigned long long bal = __ballot(free);
+            if (free) T[f + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)v;
+            f += __popcll(bal);
+        }
+        wave_sync();
+        // bit vectors over the rows (bit r of word pair k = row 64 k + r; rows without a pivot are zero):
+        // s' and the first lam columns of T; |s'| is the OSD-0 estimate's weight
+        const int lam = C.order < f ? C.order : f;
+        const int RWs = C.RWs, RW = 2 * nchunk;
+        uint32_t* cv = reinterpret_cast<uint32_t*>(pivcol + 2 * ((mmax + 1) / 2));
+        uint32_t* sv = cv + lam * RWs;
+        int w0 = 0;
+        for (int k = 0; k < nchunk; ++k) {
+            const int r = (k << 6) + lane;
+            const unsigned long long bal = __ballot(r < m && (rows[r * Ws + sw] & sbit));
+            w0 += __popcll(bal);
+            if (lane < 2) sv[2 * k + lane] = (uint32_t)(bal >> (32 * lane));
+        }
+        for (int j = 0; j < lam; ++j) {
+            const int v = T[j];  // one address per wave: a broadcast
+            const int w = v >> 5;
+            const uint32_t bit = 1u << (v & 31);
+            for (int k = 0; k < nchunk; ++k) {
+                const int r = (k << 6) + lane;
+                const unsigned long long bal = __ballot(r < m && (rows[r * Ws + w] & bit));
+                if (lane < 2) cv[j * RWs + 2 * k + lane] = (uint32_t)(bal >> (32 * lane));
+            }
+        }
+        wave_sync();
+        // packed (weight, index): weights <= rank + 2 <= 2050, indices < 1 + 2048 + 2016 < 2^12
+        uint32_t best = (uint32_t)w0 << 12;
+        // singles, lanes across the columns of T: flipping t changes the weight by one for t itself, by
+        // +1 for each row with R[r][t] = 1 and s'[r] = 0, by -1 for each with s'[r] = 1
+        for (int j0 = 0; j0 < f; j0 += 64) {
+            const int j = j0 + lane;
+            const int v = j < f ? T[j] : 0;
+            const int w = v >> 5, sh = v & 31;
+            int d = 0;
+            for (int x = 0; x < RW; ++x) {
+                const uint32_t sword = sv[x];  // a broadcast
+                const int r0 = x << 5;
+                const int r1 = r0 + 32 < m ? r0 + 32 : m;
+                for (int r = r0; r < r1; ++r) {
+                    const int cb = (int)((rows[r * Ws + w] >> sh) & 1u);
+                    d += cb - 2 * (cb & (int)((sword >> (r - r0)) & 1u));
+                }
+            }
+            if (j < f) {
+                const uint32_t c = ((uint32_t)(w0 + 1 + d) << 12) | (uint32_t)(1 + j);
+                best = c < best ? c : best;
+            }
+        }
+        // pairs {t_i, t_j}, i < j < lam <= 64: a wave-uniform loop over i, lanes across j
+        int pidx = 1 + f;  // index of the pair (i, i + 1)
+        for (int i = 0; i + 1 < lam; ++i) {
+            const int j = i + 1 + lane;
+            if (j < lam) {
+                int wt = 2;
+                for (int x = 0; x < RW; ++x) wt += __popc(cv[i * RWs + x] ^ sv[x] ^ cv[j * RWs + x]);
+                const uint32_t c = ((uint32_t)wt << 12) | (uint32_t)(pidx + lane);
+                best = c < best ? c : best;
+            }
+            pidx += lam - 1 - i;
+        }
+        for (int o = 32; o; o >>= 1) {
+            const uint32_t other = (uint32_t)__shfl_xor((int)best, o);
+            best = other < best ? other : best;
+        }
+        const int idx = (int)(best & 0xFFFu);
+        if (idx > 0 && idx <= f) {
+            fa = T[idx - 1];
+        } else if (idx > f) {
+            int rem = idx - 1 - f, i = 0;
+            while (rem >= lam - 1 - i) {
+                rem -= lam - 1 - i;
+                ++i;
+            }
+            fa = T[i];
+            fb = T[i + 1 + rem];
+        }
+        if (lane == 0 && idx > 0 && swept) atomicAdd(swept, 1u);
+        wave_sync();
+    }
+    // the estimate in LDS (over the keys), then out
     for (int v = lane; v < n; v += 64) eb[v] = 0;
     wave_sync();
     for (int k = 0; k < nchunk; ++k) {
         const int r = (k << 6) + lane;
-        if (r < m && ((used >> k) & 1u)) eb[pivcol[r]] = (rows[r * Ws + sw] & sbit) ? 1 : 0;
+        if constexpr (CS) {
+            if (r < m && ((used >> k) & 1u)) {
+                uint32_t bit = (rows[r * Ws + sw] & sbit) ? 1u : 0u;
+                if (fa >= 0) bit ^= (rows[r * Ws + (fa >> 5)] >> (fa & 31)) & 1u;
+                if (fb >= 0) bit ^= (rows[r * Ws + (fb >> 5)] >> (fb & 31)) & 1u;
+                eb[pivcol[r]] = (uint8_t)bit;
+            }
+        } else {
+            if (r < m && ((used >> k) & 1u)) eb[pivcol[r]] = (rows[r * Ws + sw] & sbit) ? 1 : 0;
+        }
     }
     wave_sync();
+    if constexpr (CS) {
+        if (lane == 0 && fa >= 0) eb[fa] = 1;
+        if (lane == 0 && fb >= 0) eb[fb] = 1;
+        wave_sync();
+    }
     for (int v = lane; v < n; v += 64) e[v] = eb[v];
     if (lane == 0) {
         // the other sector's wave may clear its own bit of the same byte: an atomic AND on the aligned
@@ -249,18 +384,19 @@ __global__ void osd_scatter_kernel(const int32_t* __restrict__ list, long long c
 }  // namespace
 
 // ---- host side ----------------------------------------------------------------------------------
-// Why this code cannot take the kernel (empty: it can).
-std::string osd_dev_unsupported(const OsdPlan& P)
+// Why this code cannot take the kernel at QEC_OPT_OSD_ORDER = order (empty: it can).
+std::string osd_dev_unsupported(const OsdPlan& P, int order)
 {
     const int n = P.sec[0].n, mmax = std::max(P.sec[0].m, P.sec[1].m);
     if (n > kOsdMaxN || mmax > kOsdMaxN)
         return "OSD: n = " + std::to_string(n) + ", " + std::to_string(mmax) + " checks; the kernel takes up to " +
                std::to_string(kOsdMaxN) + " of each";
+    if (order > 0 && n < 2) return "OSD: the combination sweep takes codes of n >= 2";
     const int W = P.sec[0].W;
-    const size_t bytes = 4 * (size_t)osd_lds_words(mmax, n, W | 1);
+    const size_t bytes = 4 * (size_t)osd_lds_words(mmax, n, W | 1, order);
     if (bytes > kOsdMaxLds)
-        return "OSD: the augmented matrix needs " + std::to_string(bytes) + " B of LDS, one workgroup has " +
-               std::to_string(kOsdMaxLds);
+        return "OSD: the augmented matrix" + std::string(order > 0 ? " and the sweep's column vectors need " : " needs ") +
+               std::to_string(bytes) + " B of LDS, one workgroup has " + std::to_string(kOsdMaxLds);
     return std::string();
 }
 
@@ -299,7 +435,7 @@ OsdDevPlan* osd_dev_create(const OsdPlan& P)
     D->d.Ws = W | 1;
     D->d.qn = (long long)P.qn;
     D->mmax = std::max(P.sec[0].m, P.sec[1].m);
-    D->lds_bytes = 4 * osd_lds_words(D->mmax, n, D->d.Ws);
+    D->lds_bytes = 4 * osd_lds_words(D->mmax, n, D->d.Ws, 0);
     return D;
 }
 
@@ -310,16 +446,27 @@ void osd_dev_free(OsdDevPlan* D)
     delete D;
 }
 
-int launch_osd(const OsdDevPlan* D, int sweep, const uint8_t* sX, const uint8_t* sZ, long long B, const float* q,
-               uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint32_t* repaired, hipStream_t st)
+int launch_osd(const OsdDevPlan* D, int sweep, int order, const uint8_t* sX, const uint8_t* sZ, long long B,
+               const float* q, uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint32_t* repaired, uint32_t* swept,
+               hipStream_t st)
 {
     if (B <= 0) return QEC_OK;
     if (B >= (1LL << 30)) return fail(QEC_ERR_ARG, "OSD: batch too large");
     OsdDev P = D->d;
     P.sweep = sweep;
-    hipLaunchKernelGGL(osd0_kernel, dim3((unsigned)(2 * B)), dim3(64), D->lds_bytes, st, P, sX, sZ, B, q, eX, eZ,
-                       flags, repaired);
-    return launch_check("osd0");
+    if (order <= 0) {
+        hipLaunchKernelGGL(osd_kernel<false>, dim3((unsigned)(2 * B)), dim3(64), D->lds_bytes, st, P, sX, sZ, B, q, eX,
+                           eZ, flags, repaired, OsdCs{}, nullptr);
+        return launch_check("osd0");
+    }
+    // the sweep's column vectors behind the elimination's image (QEC_OPT_OSD_ORDER is refused where
+    // the sum does not fit: osd_dev_unsupported)
+    const uint32_t lds = 4 * osd_lds_words(D->mmax, P.n, P.Ws, order);
+    if (order > kOsdMaxOrder || lds > kOsdMaxLds) return fail(QEC_ERR_UNSUPPORTED, "OSD: the sweep does not fit in LDS");
+    const OsdCs C{order, osd_rws(D->mmax)};
+    hipLaunchKernelGGL(osd_kernel<true>, dim3((unsigned)(2 * B)), dim3(64), lds, st, P, sX, sZ, B, q, eX, eZ, flags,
+                       repaired, C, swept);
+    return launch_check("osd_cs");
 }
 
 int launch_osd_collect(const uint8_t* rec, int rstride, int n, long long B, int32_t* list, uint32_t* count,

@@ -1,5 +1,6 @@
-// OSD-0 on the host: the CPU engine's post-processing stage and the
-// in-library cross-check of the kernel (osd.hip).  Plain C++ on bit-packed rows; no GPU.
+// OSD-0 and the combination sweep on the host (DESIGN.md sections 1.2, 1.3): the CPU engine's
+// post-processing stage and the in-library cross-check of the kernel (osd.hip).  Plain C++ on
+// bit-packed rows; no GPU.
 #include <algorithm>
 #include <thread>
 
@@ -54,8 +55,9 @@ void osd_plan_build(const Code& c, OsdPlan& out)
     build_sector(c.pcmZ, c.mZ, c.n, c.L, (size_t)c.mX * c.L, out.sec[1]);
 }
 
-bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8_t* e)
+bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8_t* e, int order_cs, bool* swept)
 {
+    if (swept) *swept = false;
     const int m = S.m, n = S.n, W = S.W;
     // a syndrome entry other than 0 or 1 can never be reproduced (the reference compares exact values)
     for (int c = 0; c < m; ++c)
@@ -95,32 +97,77 @@ bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8
     // the rows without a pivot are zero in H now: s is in the column space iff they are zero in s too
     for (int c = 0; c < m; ++c)
         if (pivcol[c] < 0 && (A[(size_t)c * W + sw] & sbit)) return false;
+    // section 1.3: T = the non-pivot columns in the walk's order; a candidate flips a set F of them, and
+    // its weight is |F| plus the pivot rows whose s' bit, XOR their bits in the columns of F, is set
+    int F[2] = {-1, -1};
+    if (order_cs > 0) {
+        std::vector<uint8_t> is_piv(n, 0);
+        for (int c = 0; c < m; ++c)
+            if (pivcol[c] >= 0) is_piv[pivcol[c]] = 1;
+        std::vector<int> T;
+        for (int t = 0; t < n; ++t)
+            if (!is_piv[order[t]]) T.push_back(order[t]);
+        const int f = (int)T.size(), lam = std::min(order_cs, f);
+        auto bit_at = [&](int c, int v) { return (A[(size_t)c * W + (v >> 5)] >> (v & 31)) & 1u; };
+        auto weight = [&](int a, int b) {
+            int wt = (a >= 0) + (b >= 0);
+            for (int c = 0; c < m; ++c) {
+                if (pivcol[c] < 0) continue;
+                uint32_t x = bit_at(c, n);
+                if (a >= 0) x ^= bit_at(c, a);
+                if (b >= 0) x ^= bit_at(c, b);
+                wt += (int)x;
+            }
+            return wt;
+        };
+        // candidates in index order, a strictly lighter one replaces the best: the first minimum wins
+        int best = weight(-1, -1);
+        for (int j = 0; j < f; ++j) {
+            const int wt = weight(T[j], -1);
+            if (wt < best) { best = wt; F[0] = T[j]; F[1] = -1; if (swept) *swept = true; }
+        }
+        for (int i = 0; i < lam; ++i)
+            for (int j = i + 1; j < lam; ++j) {
+                const int wt = weight(T[i], T[j]);
+                if (wt < best) { best = wt; F[0] = T[i]; F[1] = T[j]; if (swept) *swept = true; }
+            }
+    }
     std::memset(e, 0, n);
-    for (int c = 0; c < m; ++c)
-        if (pivcol[c] >= 0) e[pivcol[c]] = (A[(size_t)c * W + sw] & sbit) ? 1 : 0;
+    for (int c = 0; c < m; ++c) {
+        if (pivcol[c] < 0) continue;
+        uint32_t x = A[(size_t)c * W + sw] & sbit ? 1u : 0u;
+        for (int k = 0; k < 2; ++k)
+            if (F[k] >= 0) x ^= (A[(size_t)c * W + (F[k] >> 5)] >> (F[k] & 31)) & 1u;
+        e[pivcol[c]] = (uint8_t)x;
+    }
+    for (int k = 0; k < 2; ++k)
+        if (F[k] >= 0) e[F[k]] = 1;
     return true;
 }
 
 long long osd_host_batch(const OsdPlan& P, const uint8_t* sX, const uint8_t* sZ, long long B, const float* q,
-                         uint8_t* eX, uint8_t* eZ, uint8_t* flags, int threads)
+                         uint8_t* eX, uint8_t* eZ, uint8_t* flags, int threads, int order, long long* swept)
 {
+    if (swept) *swept = 0;
     if (B <= 0) return 0;
     if (threads <= 0) {
         const unsigned h = std::thread::hardware_concurrency();
         threads = h ? (int)h : 1;
     }
     threads = (int)std::max<long long>(1, std::min<long long>(threads, B));
-    std::vector<long long> fixed(threads, 0);
+    std::vector<long long> fixed(threads, 0), cs(threads, 0);
     auto run = [&](int t, long long lo, long long hi) {
         for (long long b = lo; b < hi; ++b)
             for (int sec = 0; sec < 2; ++sec) {
                 const uint8_t fbit = sec ? QEC_SYNDROME_FAIL_Z : QEC_SYNDROME_FAIL_X;
                 if (!(flags[b] & fbit)) continue;
                 const OsdSector& S = P.sec[sec];
+                bool sw = false;
                 if (osd_host_sector(S, q + (size_t)b * P.qn, (sec ? sZ : sX) + (size_t)b * S.m,
-                                    (sec ? eZ : eX) + (size_t)b * S.n)) {
+                                    (sec ? eZ : eX) + (size_t)b * S.n, order, &sw)) {
                     flags[b] &= (uint8_t)~fbit;
                     ++fixed[t];
+                    cs[t] += sw;
                 }
             }
     };
@@ -133,6 +180,8 @@ long long osd_host_batch(const OsdPlan& P, const uint8_t* sX, const uint8_t* sZ,
     }
     long long total = 0;
     for (long long f : fixed) total += f;
+    if (swept)
+        for (long long x : cs) *swept += x;
     return total;
 }
 

@@ -1,5 +1,6 @@
-// OSD-0 post-processing: the per-sector tables both implementations read,
-// the host implementation (osd_host.cpp) and the kernel launchers (osd.hip).
+// OSD post-processing (DESIGN.md sections 1.2 and 1.3: OSD-0 and the combination sweep OSD-CS): the
+// per-sector tables both implementations read, the host implementation (osd_host.cpp) and the kernel
+// launchers (osd.hip).
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -38,13 +39,19 @@ inline uint32_t osd_key(uint32_t bits)
 
 void osd_plan_build(const Code& c, OsdPlan& out);
 
+constexpr int kOsdMaxOrder = 64;  // QEC_OPT_OSD_ORDER: lambda of the combination sweep, 0 .. 64
+
 // Steps 2-6 for one sector of one sample: q = the sample's q_final block, s = the sector's syndrome
 // bytes, e = the sector's estimate (n bytes), rewritten only if [H | s] is consistent.  Returns
-// whether it was.
-bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8_t* e);
+// whether it was.  order = lambda of section 1.3 (0: the OSD-0 estimate); *swept (nullable) tells
+// whether the lightest candidate was another than the OSD-0 estimate (index > 0).
+bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8_t* e, int order = 0,
+                     bool* swept = nullptr);
 
-// Steps 2-7 on a decoded host batch, in place; returns the number of sectors repaired.
+// Steps 2-7 on a decoded host batch, in place; returns the number of sectors repaired, and in
+// *swept (nullable) how many of them took a candidate of index > 0.
 long long osd_host_batch(const OsdPlan& P, const uint8_t* sX, const uint8_t* sZ, long long B, const float* q,
-                         uint8_t* eX, uint8_t* eZ, uint8_t* flags, int threads);
+                         uint8_t* eX, uint8_t* eZ, uint8_t* flags, int threads, int order = 0,
+                         long long* swept = nullptr);
 
 }  // namespace qec

@@ -1,0 +1,334 @@
+"""The combination sweep behind OSD-0 (OSD-CS; QEC_OPT_OSD_ORDER) without a GPU:
+the host implementation (osd_host.cpp) through qec_osd and the CPU engine's synchronous calls, the
+options, the CLI and the C++ wrapper, against a dense numpy restatement of the definition that extends
+the yardstick of tests/test_osd_host.py: enumerate the candidates, count, take the first minimum.
+tests/test_gpu_osd_cs.py reuses it for the kernel."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import qec_ldpc_amd as q
+from conftest import ROOT
+from qec_ldpc_amd.gather import pack_records
+from test_osd_host import (FAIL, KEYS, MAIN, Yardstick, _cli, _fields, env, forced_batch,  # noqa: F401 (env: fixture)
+                           inconsistent_syndrome, main_case, osd_keys)
+
+ORDERS = (0, 1, 2, 10, 64)
+FORCED_B = {"P7": 32, "G13": 32, "P61": 8}
+
+
+# ---- the yardstick: section 1.3 in numpy ---------------------------------------------------------
+class YardstickCS(Yardstick):
+    """The yardstick of section 1.2 with the sweep of section 1.3 behind it."""
+
+    def __init__(self, ys):
+        self.__dict__.update(ys.__dict__)  # the matrices, ranks and q_final offsets, computed once
+
+    def reduce(self, sec, s, qrow):
+        """Section 1.2 steps 1-5: (R with s' as column n, pivots [(row, column)], the column order), or
+        None if [H | s] is inconsistent."""
+        H, n = self.H[sec], self.n
+        key = osd_keys(qrow[self.pos[sec]]).astype(np.int64)
+        order = np.lexsort((np.arange(n), -key))  # key descending, ties by v ascending
+        A = np.concatenate([H, np.asarray(s, dtype=np.uint8)[:, None] & 1], axis=1).astype(np.uint8)
+        used = np.zeros(H.shape[0], dtype=bool)
+        piv = []
+        for v in order:
+            if len(piv) == self.rank[sec]:
+                break
+            rows = np.nonzero(A[:, v].astype(bool) & ~used)[0]
+            if not len(rows):
+                continue
+            p = rows[0]
+            others = A[:, v].astype(bool)
+            others[p] = False
+            A[others] ^= A[p]
+            used[p] = True
+            piv.append((p, v))
+        if A[~used, n].any():
+            return None
+        return A, piv, order
+
+    def sweep(self, red, lam):
+        """Section 1.3 on a reduced sector -> (estimate, winner's index, f, candidates at the minimum)."""
+        A, piv, order = red
+        n = self.n
+        prow = np.array([p for p, _ in piv], dtype=np.int64)
+        pcol = np.array([v for _, v in piv], dtype=np.int64)
+        pivots = set(pcol.tolist())
+        T = [int(v) for v in order if int(v) not in pivots]
+        f = len(T)
+        top = min(lam, f)
+        flips = [()]
+        if lam > 0:
+            flips += [(t,) for t in T]
+            flips += [(T[i], T[j]) for i in range(top) for j in range(i + 1, top)]
+
+        def estimate(F):
+            e = np.zeros(n, dtype=np.uint8)
+            x = A[prow, n].copy()
+            for t in F:
+                x ^= A[prow, t]
+            e[pcol] = x
+            e[list(F)] = 1
+            return e
+
+        weights = [int(estimate(F).sum()) for F in flips]
+        index = int(np.argmin(weights))  # the first minimum
+        return estimate(flips[index]), index, f, weights.count(min(weights))
+
+    def repair_cs(self, sX, sZ, qf, eX, eZ, flags, lams):
+        """Steps 2-7 with the sweep, for each lambda of `lams` (the elimination is shared) ->
+        {lambda: (eX, eZ, flags, sectors repaired, sectors with index > 0, winner kinds, tied sectors)}."""
+        out = {lam: [eX.copy(), eZ.copy(), flags.copy(), 0, 0, {"osd0": 0, "single": 0, "pair": 0}, 0] for lam in lams}
+        for b in range(len(flags)):
+            for sec, s in enumerate((sX, sZ)):
+                if not flags[b] & FAIL[sec]:
+                    continue
+                red = self.reduce(sec, s[b], qf[b])
+                if red is None:
+                    continue
+                for lam, o in out.items():
+                    e, index, f, at_min = self.sweep(red, lam)
+                    o[sec][b] = e
+                    o[2][b] &= ~FAIL[sec] & 0xFF
+                    o[3] += 1
+                    o[4] += index > 0
+                    o[5]["osd0" if index == 0 else "single" if index <= f else "pair"] += 1
+                    o[6] += at_min > 1
+        return {lam: tuple(o) for lam, o in out.items()}
+
+    def bp_osd_cs(self, orc, sX, sZ, p, N, stop, lam, n_osd=3):
+        """bp_osd of the base class with the sweep -> (eX, eZ, flags, repaired, swept)."""
+        eX, eZ, flags, _ = orc.decode_batch(sX, sZ, p, N, stop)[:4]
+        bad = np.nonzero(flags & 3)[0]
+        if not len(bad):
+            return eX, eZ, flags, 0, 0
+        qf = orc.decode_batch(sX[bad], sZ[bad], p, n_osd, "fixed", want_q=True)[4].reshape(len(bad), self.qn)
+        r = self.repair_cs(sX[bad], sZ[bad], qf, eX[bad], eZ[bad], flags[bad], (lam,))[lam]
+        oX, oZ, of = eX.copy(), eZ.copy(), flags.copy()
+        oX[bad], oZ[bad], of[bad] = r[0], r[1], r[2]
+        return oX, oZ, of, r[3], r[4]
+
+
+_forced = {}
+
+
+def forced_cs(env, key):
+    """forced_batch(code, default_rng(2024), B) and the yardstick's repair of it for every lambda."""
+    if key not in _forced:
+        code, _, _, ys = env[key]
+        batch = forced_batch(code, np.random.default_rng(2024), FORCED_B[key])
+        _forced[key] = (batch, YardstickCS(ys).repair_cs(*batch, ORDERS))
+    return _forced[key]
+
+
+_main = {}
+
+
+def main_cs(env, key, lam=10):
+    """The yardstick's BP + OSD-CS result for the sampled batch of MAIN[key]."""
+    if (key, lam) not in _main:
+        _, _, orc, ys = env[key]
+        p, N, _, _ = MAIN[key]
+        sX, sZ = main_case(env, key)[:2]
+        _main[key, lam] = YardstickCS(ys).bp_osd_cs(orc, sX, sZ, p, N, "syndrome", lam)
+    return _main[key, lam]
+
+
+class osd_order:
+    """`with osd_order(dec, lam, osd=1)`: the options for the block, reset behind it."""
+
+    def __init__(self, dec, lam, osd=None):
+        self.dec, self.lam, self.osd = dec, lam, osd
+
+    def __enter__(self):
+        self.dec.set_option("osd_order", self.lam)
+        if self.osd is not None:
+            self.dec.set_option("osd", self.osd)
+        return self.dec
+
+    def __exit__(self, *exc):
+        self.dec.set_option("osd_order", 0)
+        if self.osd is not None:
+            self.dec.set_option("osd", 0)
+
+
+# ---- tests ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("key", KEYS)
+def test_qec_osd_matches_numpy_for_every_order(env, key):
+    code, dec, _, ys = env[key]
+    (sX, sZ, qf, eX, eZ, flags), want = forced_cs(env, key)
+    check_forced_conditions(env, key)
+    B = len(flags)
+    for lam in ORDERS:
+        wX, wZ, wf, cnt, swept = want[lam][:5]
+        assert cnt == 2 * B
+        with osd_order(dec, lam):
+            gX, gZ, gf = dec.osd(sX, sZ, qf, eX, eZ, flags)
+            assert np.array_equal(gX, wX) and np.array_equal(gZ, wZ) and np.array_equal(gf, wf), lam
+            assert dec.get_option("osd_sectors") == cnt and dec.get_option("osd_cs_sectors") == swept, lam
+    # lambda = 0 is OSD-0: the existing yardstick
+    zX, zZ, zf, zc = ys.repair(sX, sZ, qf, eX, eZ, flags)
+    assert np.array_equal(want[0][0], zX) and np.array_equal(want[0][1], zZ) and np.array_equal(want[0][2], zf)
+    assert want[0][3] == zc and want[0][4] == 0
+
+
+def check_forced_conditions(env, key):
+    """Conditions on the inputs, not measurements of the code under test: every winner kind, ties,
+    the clamp."""
+    want = forced_cs(env, key)[1]
+    if key == "P61":
+        assert want[64][5]["pair"] >= 1
+    else:
+        assert min(want[10][5].values()) >= 1, want[10][5]
+    assert want[10][6] >= 1  # two candidates tie for the minimum somewhere
+    if key == "P7":
+        ys = env[key][3]
+        assert max(ys.n - r for r in ys.rank) < 64  # f < lambda = 64: the clamp
+
+
+@pytest.mark.parametrize("key", KEYS)
+def test_sweep_properties(env, key):
+    code, dec, _, ys = env[key]
+    (sX, sZ, qf, eX, eZ, flags), _ = forced_cs(env, key)
+    got = {}
+    for lam in ORDERS:
+        with osd_order(dec, lam):
+            got[lam] = dec.osd(sX, sZ, qf, eX, eZ, flags)
+        assert not (got[lam][2] & 3).any()
+        assert np.array_equal(code.syndrome(0, got[lam][0]), sX) and np.array_equal(code.syndrome(1, got[lam][1]), sZ)
+    wt = {lam: np.concatenate([got[lam][0].sum(1, dtype=np.int64), got[lam][1].sum(1, dtype=np.int64)]) for lam in ORDERS}
+    for lam in ORDERS:
+        assert (wt[lam] <= wt[0]).all(), lam
+    assert (wt[64] <= wt[10]).all() and (wt[10] <= wt[1]).all()
+
+
+@pytest.mark.parametrize("key", KEYS)
+def test_inconsistent_syndrome_is_left_alone_by_the_sweep(env, key):
+    code, dec, _, ys = env[key]
+    rng = np.random.default_rng(5)
+    sX, sZ, qf, eX, eZ, flags = forced_batch(code, rng, 4)
+    deficient = [sec for sec in (0, 1) if ys.rank[sec] < ys.H[sec].shape[0]]
+    assert deficient
+    for sec in deficient:
+        s = (sX, sZ)[sec]
+        s[1] = inconsistent_syndrome(ys, sec, s[1], rng)
+    wX, wZ, wf, cnt, swept = YardstickCS(ys).repair_cs(sX, sZ, qf, eX, eZ, flags, (10,))[10][:5]
+    assert cnt == 8 - len(deficient)
+    with osd_order(dec, 10):
+        gX, gZ, gf = dec.osd(sX, sZ, qf, eX, eZ, flags)
+        assert dec.get_option("osd_sectors") == cnt and dec.get_option("osd_cs_sectors") == swept
+    assert np.array_equal(gX, wX) and np.array_equal(gZ, wZ) and np.array_equal(gf, wf)
+    for sec in deficient:
+        assert gf[1] & FAIL[sec]
+        assert np.array_equal((gX, gZ)[sec][1], (eX, eZ)[sec][1])
+
+
+@pytest.mark.parametrize("key", KEYS)
+def test_decoder_cpu_with_osd_cs(env, key):
+    code, dec, _, _ = env[key]
+    p, N, B, _ = MAIN[key]
+    sX, sZ, _, _, zero = main_case(env, key)
+    eX, eZ, flags, cnt, swept = main_cs(env, key)
+    assert swept >= 1 and cnt == zero[3] and not (flags & 3).any()  # the winner differs from OSD-0 somewhere
+    assert not (np.array_equal(eX, zero[0]) and np.array_equal(eZ, zero[1]))
+    assert np.array_equal(code.syndrome(0, eX), sX) and np.array_equal(code.syndrome(1, eZ), sZ)
+    with osd_order(dec, 10, osd=1):
+        assert dec.get_option("osd_order") == 10
+        g = dec.decode_batch(sX, sZ, p, N, "syndrome", want_iters=True)
+        assert np.array_equal(g[0], eX) and np.array_equal(g[1], eZ) and np.array_equal(g[2], flags)
+        assert np.array_equal(g[3], zero[4])  # still the main decode's iterations
+        assert dec.get_option("osd_sectors") == cnt and dec.get_option("osd_cs_sectors") == swept
+        assert dec.last_path() == {"osd"}
+        rec, its = dec.decode_batch_packed(sX, sZ, p, N, "syndrome", want_iters=True)
+        assert np.array_equal(rec, pack_records(eX, eZ, flags)) and np.array_equal(its, zero[4])
+        assert dec.get_option("osd_sectors") == cnt and dec.get_option("osd_cs_sectors") == swept
+    # the order back at 0: today's BP + OSD-0 outputs
+    dec.set_option("osd", 1)
+    try:
+        g = dec.decode_batch(sX, sZ, p, N, "syndrome")
+        assert np.array_equal(g[0], zero[0]) and np.array_equal(g[1], zero[1]) and np.array_equal(g[2], zero[2])
+        assert dec.get_option("osd_sectors") == cnt and dec.get_option("osd_cs_sectors") == 0
+    finally:
+        dec.set_option("osd", 0)
+    dec.decode_batch(sX, sZ, p, N, "syndrome")
+    assert dec.get_option("osd_sectors") == 0 and dec.get_option("osd_cs_sectors") == 0
+
+
+def test_get_statistics_with_osd_cs(env):
+    """GetStatistics on the CPU engine with the sweep on: host counting over the numpy-repaired estimates."""
+    code, dec, orc, ys = env["P7"]
+    W, count, p, N, seed = 6, 1500, 0.05, 20, 20240607
+    x, z = q.sample_fixed_weight(seed, W, count, code.n)
+    sX, sZ = code.syndrome(0, x), code.syndrome(1, z)
+    eX, eZ, flags, cnt, swept = YardstickCS(ys).bp_osd_cs(orc, sX, sZ, p, N, "ref", 10)
+    assert cnt >= 50 and swept >= 1 and not (flags & 3).any()
+    logical = code.check_logical(x ^ eX, z ^ eZ)
+    want = {"numErrorsTested": count, "corrected": int((~logical).sum()), "logicalErrors": int(logical.sum()),
+            "syndromeErrorsX": 0, "syndromeErrorsZ": 0, "convergenceFailX": int(((flags & 4) != 0).sum()),
+            "convergenceFailZ": int(((flags & 8) != 0).sum())}
+    with osd_order(dec, 10, osd=1):
+        st = dec.GetStatistics(W, count, p, N, seed)
+        assert dec.get_option("osd_sectors") == cnt and dec.get_option("osd_cs_sectors") == swept
+    assert {k: st[k] for k in want} == want
+    dec.GetStatistics(W, count, p, N, seed)
+    assert dec.get_option("osd_cs_sectors") == 0
+
+
+def test_option_checks(env):
+    code, dec, _, _ = env["P7"]
+    assert dec.get_option("osd_order") == 0 and dec.get_option("osd_cs_sectors") == 0
+    assert q.OPTIONS["osd_order"] == 13 and q.OPTIONS["osd_cs_sectors"] == 14
+    dec.set_option("osd_order", 7)
+    for name, value in (("osd_order", -1), ("osd_order", 65), ("osd_cs_sectors", 0), ("osd_cs_sectors", 3)):
+        with pytest.raises(q.QecError):
+            dec.set_option(name, value)
+    assert dec.get_option("osd_order") == 7
+    for lam in (64, 0):
+        dec.set_option("osd_order", lam)
+        assert dec.get_option("osd_order") == lam
+    assert dec.get_option("osd") == 0  # the order alone turns nothing on
+
+
+def test_cli_osd_order(tmp_path, code_paths):
+    line = "6 6 2000 20 0.05"
+    a = tmp_path / "on"
+    a.mkdir()
+    r = _cli(a, ["--engine", "cpu", "--seed", "7", "--osd", "0", "--osd-order", "10"], code_paths["P7"], line)
+    assert r.returncode == 0, r.stderr
+    on = _fields(a)
+    assert int(on["Syndrome Errors X"]) == 0 and int(on["Syndrome Errors Z"]) == 0
+    assert int(on["Corrected"]) + int(on["Logical Errors"]) == int(on["Errors Tested"]) > 0
+    for flags in (["--osd-order", "10"], ["--osd", "0", "--osd-order", "65"], ["--osd", "0", "--osd-order", "-1"]):
+        c = tmp_path / ("bad" + "_".join(flags).replace("-", ""))
+        c.mkdir()
+        r = _cli(c, ["--engine", "cpu"] + flags, code_paths["P7"], line)
+        assert r.returncode == 2 and "usage: qec_ldpc" in r.stderr, flags
+
+
+def test_set_osd_from_cpp(tmp_path, code_paths):
+    """include/DecoderCPU.h: SetOsd(10, 3) sets the order (option 13), the iterations and the stage."""
+    src = tmp_path / "m.cpp"
+    src.write_text('#include <iostream>\n#include "DecoderCPU.h"\n#include "Quantum_LDPC_Code.h"\n'
+                   'int main(int, char** argv){ Quantum_LDPC_Code code = Quantum_LDPC_Code::createFromFile(argv[1]);\n'
+                   ' DecoderCPU decoder(code); int v[6] = {-1, -1, -1, -1, -1, -1};\n'
+                   ' decoder.SetOsd(10, 3);\n'
+                   ' qec_decoder_get_option(decoder.handle(), 13, &v[0]); qec_decoder_get_option(decoder.handle(), QEC_OPT_OSD, &v[1]);\n'
+                   ' qec_decoder_get_option(decoder.handle(), QEC_OPT_OSD_ITERATIONS, &v[2]);\n'
+                   ' decoder.SetOsd(0);\n'
+                   ' qec_decoder_get_option(decoder.handle(), QEC_OPT_OSD_ORDER, &v[3]); qec_decoder_get_option(decoder.handle(), QEC_OPT_OSD, &v[4]);\n'
+                   ' decoder.SetOsd(-1);\n'
+                   ' qec_decoder_get_option(decoder.handle(), QEC_OPT_OSD, &v[5]);\n'
+                   ' bool refused = false; try { decoder.SetOsd(65); } catch (const std::string&) { refused = true; }\n'
+                   ' for (int x : v) std::cout << x << " "; std::cout << refused << std::endl; return 0; }\n')
+    exe = tmp_path / "m"
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
+                        "-L", os.path.join(ROOT, "qec_ldpc_amd"), "-lqecldpc",
+                        "-Wl,-rpath," + os.path.join(ROOT, "qec_ldpc_amd")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe), code_paths["P7"]], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout.split() == ["10", "1", "3", "0", "1", "0", "1"]

@@ -22,7 +22,10 @@
 //                      reference: what the shipped I-P matrices compute; degenerate: a residual that is
 //                      a product of stabilizers counts as corrected
 //   --osd 0            BP + OSD-0: samples whose syndrome BP leaves unsatisfied are repaired by ordered-statistics
-//                      decoding of order 0 (the only order; QEC_OPT_OSD) before they are counted
+//                      decoding (QEC_OPT_OSD) before they are counted; the value stays 0, the sweep's
+//                      order is --osd-order
+//   --osd-order L      with --osd 0: the combination sweep OSD-CS over the L most suspicious non-pivot
+//                      columns (QEC_OPT_OSD_ORDER, 0 .. 64; default 0 = OSD-0)
 //   --osd-iterations K iterations of the soft decode that orders OSD's columns (default 3; needs --osd)
 // Unknown or inconsistent flags exit with status 2.
 #include <algorithm>
@@ -71,7 +74,7 @@ int usage(const std::string& why)
     std::cerr << why << std::endl
               << "usage: qec_ldpc [--engine gpu|cpu] [--gpus N | --devices i,j,...] [--rng msvc|philox]"
                  " [--stop ref|fixed|syndrome] [--batch B] [--seed S] [--logical file|reference|degenerate]"
-                 " [--osd 0 [--osd-iterations K]] initFile"
+                 " [--osd 0 [--osd-order L] [--osd-iterations K]] initFile"
               << std::endl;
     return 2;
 }
@@ -90,7 +93,8 @@ int main(int argc, char** argv)
     std::vector<int> devices{0};
     std::string engine = "gpu", rng = "msvc", stopName = "ref", logical = "file";
     bool deviceFlag = false, stopFlag = false, batchFlag = false, seedFlag = false, osd = false, osdIterFlag = false;
-    int osdIterations = 3;
+    bool osdOrderFlag = false;
+    int osdIterations = 3, osdOrder = 0;
     size_t batch = size_t(1) << 20;
     unsigned long long seed = 0x51EC0DE;
     int a = 1;
@@ -128,8 +132,13 @@ int main(int argc, char** argv)
                 batch = (size_t)b;
                 batchFlag = true;
             } else if (flag == "--osd") {
-                if (val != "0") return usage("--osd: the OSD order; only 0 exists");
+                if (val != "0") return usage("--osd: 0 turns the OSD stage on (its order is --osd-order)");
                 osd = true;
+            } else if (flag == "--osd-order") {
+                size_t used = 0;
+                osdOrder = std::stoi(val, &used);
+                osdOrderFlag = true;
+                if (used != val.size() || osdOrder < 0 || osdOrder > 64) return usage("--osd-order: 0 .. 64");
             } else if (flag == "--osd-iterations") {
                 osdIterations = std::stoi(val);
                 osdIterFlag = true;
@@ -149,6 +158,7 @@ int main(int argc, char** argv)
     if (rng == "msvc" && (stopFlag || batchFlag))
         return usage("--stop / --batch apply to --rng philox (GetStatistics keeps the reference stop rule)");
     if (osdIterFlag && !osd) return usage("--osd-iterations needs --osd 0");
+    if (osdOrderFlag && !osd) return usage("--osd-order needs --osd 0");
     if (argc - a != 1 || devices.empty()) {
         log << "Must provide initialization file." << std::endl;
         return 0;
@@ -181,7 +191,7 @@ int main(int argc, char** argv)
         }
         if (rng == "philox") {
             DecoderGPU decoder(code, devices);
-            if (osd) decoder.SetOsd(0, osdIterations);
+            if (osd) decoder.SetOsd(osdOrder, osdIterations);
             std::cout << "Engine: " << decoder.Describe() << std::endl;
             const int stop = stopName == "ref" ? QEC_STOP_REF : stopName == "fixed" ? QEC_STOP_FIXED : QEC_STOP_SYNDROME;
             std::stringstream fileName;
@@ -203,12 +213,12 @@ int main(int argc, char** argv)
         if (engine == "cpu") {
             DecoderCPU* c = new DecoderCPU(code);
             decoder.reset(c);
-            if (osd) c->SetOsd(0, osdIterations);
+            if (osd) c->SetOsd(osdOrder, osdIterations);
             std::cout << "Engine: CPU (" << std::thread::hardware_concurrency() << " threads)" << std::endl;
         } else {
             DecoderGPU* g = new DecoderGPU(code, devices);
             decoder.reset(g);
-            if (osd) g->SetOsd(0, osdIterations);
+            if (osd) g->SetOsd(osdOrder, osdIterations);
             std::cout << "Engine: " << g->Describe() << std::endl;
         }
         for (; w <= W; ++w) {
