@@ -184,6 +184,13 @@ int qec_decoder_device(const qec_decoder* dec);         /* HIP device ordinal (o
  *     (bp_decode.hip, cycle_end), so the kernel jumps to the sector's last iteration.
  *     Bit-identical either way; 0 runs the remaining hard iterations one by one (for
  *     measurement).
+ *   QEC_OPT_NEAR_HARD_JUMP (default 1; needs QEC_OPT_HARD_PATHS; fixed and reference stop, no q_final
+ *     requested; wave-circulant kernels and the CPU engine): once a sector's messages are all within
+ *     eps0 of 0 or 1, each variable's on one side, and those sides satisfy the syndrome, every later
+ *     state provably stays so (eps0 per launch and sector from
+ *     qec_near_hard_threshold), so the decisions, both flags and the iteration count are known and the
+ *     sector jumps to its end.  Every output bit identical either way; 0 runs those iterations (for
+ *     measurement).  A call that requests q_final, and the soft decode of the OSD stage, never jump.
  *   QEC_OPT_SCHEDULE (default 1): dispatch order of the wave-circulant launch.  Two small
  *     kernels (a counting sort) order the batch by syndrome weight and the decode waves take syndromes heaviest
  *     first, so the rare syndromes that run every iteration in full arithmetic start early
@@ -272,7 +279,7 @@ int qec_decoder_device(const qec_decoder* dec);         /* HIP device ordinal (o
 enum { QEC_OPT_HARD_PATHS = 1, QEC_OPT_CYCLE_JUMP = 2, QEC_OPT_SCHEDULE = 3, QEC_OPT_SECTOR_SPLIT = 4,
        QEC_OPT_PHASE_STATS = 5, QEC_OPT_TRIAGE = 6, QEC_OPT_LAST_PATH = 7, QEC_OPT_MC_DECODE_TIME = 8,
        QEC_OPT_OSD = 9, QEC_OPT_OSD_ITERATIONS = 10, QEC_OPT_OSD_SECTORS = 11, QEC_OPT_OSD_SWEEP = 12,
-       QEC_OPT_OSD_ORDER = 13, QEC_OPT_OSD_CS_SECTORS = 14 };
+       QEC_OPT_OSD_ORDER = 13, QEC_OPT_OSD_CS_SECTORS = 14, QEC_OPT_NEAR_HARD_JUMP = 15 };
 enum {
     QEC_PATH_ORDERED = 1,          /* dispatch order pass (schedule.hip) */
     QEC_PATH_SECTOR_ORDER = 2,     /* ... in the per-sector form (each sector's waves by its own weight) */
@@ -284,6 +291,12 @@ enum {
     QEC_PATH_RECORDS = 128,        /* packed decision records out */
     QEC_PATH_OSD = 256             /* the call ran the OSD stage (QEC_OPT_OSD) */
 };
+/* The near-hard jump's threshold for p' = pPrime (the float (2/3) errorProbability the decoder forms), R
+ * checks per variable and L variables per check: *eps0 = the largest power of two in [2^-20, 2^-8] with
+ * 2 ((1 - p') / p') (delta / (1 - delta))^(R - 1) <= eps0, delta = (L - 1) eps0 + 2^-20 (evaluated in double),
+ * or 0 if there is none or p' is outside (0, 1/2] (the jump then never fires); *T = the bit pattern one below
+ * the float eps0 (1 - eps0): bits(fma(-q, q, q)) <= T as unsigned integers implies q <= eps0 or q >= 1 - eps0. */
+int qec_near_hard_threshold(float pPrime, int R, int L, float* eps0, uint32_t* T);
 int qec_decoder_set_option(qec_decoder* dec, int option, int value);
 int qec_decoder_get_option(const qec_decoder* dec, int option, int* value);
 /* which kernel variant serves this code: writes a short name (e.g. "wave-circulant P=61 G=1") */

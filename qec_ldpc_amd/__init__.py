@@ -28,7 +28,7 @@ STOP = {"ref": 0, "fixed": 1, "syndrome": 2}
 ENGINE = {"auto": 0, "circulant": 1, "sparse": 2, "cpu": 3}
 OPTION = {"hard_paths": 1, "cycle_jump": 2, "schedule": 3, "sector_split": 4, "phase_stats": 5, "triage": 6,
           "last_path": 7, "mc_decode_time": 8, "osd": 9, "osd_iterations": 10, "osd_sectors": 11,
-          "osd_sweep": 12, "osd_order": 13, "osd_cs_sectors": 14}
+          "osd_sweep": 12, "osd_order": 13, "osd_cs_sectors": 14, "near_hard": 15}
 OPTIONS = OPTION
 # QEC_PATH_* bits of QEC_OPT_LAST_PATH (include/qec_ldpc.h): the launch sequence of the last decode call
 PATH = {"ordered": 1, "sector_order": 2, "split_waves": 4, "sector_launches": 8, "triage": 16, "bit_rows": 32,
@@ -42,7 +42,7 @@ EXPORTS = (
     "qec_code_with_logical", "qec_code_logical_mode", "qec_code_logical_rows", "qec_code_imp",
     "qec_decoder_create", "qec_decoder_create_engine", "qec_decoder_create_multi", "qec_decoder_destroy",
     "qec_decoder_num_parts", "qec_decoder_part", "qec_decoder_device", "qec_decoder_describe",
-    "qec_decoder_set_option", "qec_decoder_get_option",
+    "qec_decoder_set_option", "qec_decoder_get_option", "qec_near_hard_threshold",
     "qec_decode_batch", "qec_decode_batch_dev", "qec_decode_batch_packed", "qec_decode_batch_packed_dev",
     "qec_decode_bits_packed_dev",
     "qec_sample_fixed_weight", "qec_get_statistics",
@@ -137,6 +137,7 @@ def lib():
             "qec_decoder_describe": (i, [vp, ctypes.c_char_p, sz]),
             "qec_decoder_set_option": (i, [vp, i, i]),
             "qec_decoder_get_option": (i, [vp, i, vp]),
+            "qec_near_hard_threshold": (i, [f, i, i, vp, vp]),
             "qec_decode_batch": (i, [vp, vp, vp, sz, f, i, i, vp, vp, vp, vp, vp]),
             "qec_decode_batch_dev": (i, [vp, vp, vp, sz, f, i, i, vp, vp, vp, vp, vp, vp]),
             "qec_decode_batch_packed": (i, [vp, vp, vp, sz, f, i, i, vp, vp]),
@@ -171,6 +172,15 @@ def last_error():
 def build_id():
     """Hash of the sources and flags the loaded library was built from (Makefile BUILD_ID)."""
     return lib().qec_build_id().decode()
+
+
+def near_hard_threshold(p_prime, R, L):
+    """qec_near_hard_threshold: (eps0, T) of the near-hard jump for p' (a float32), R checks per variable
+    and L variables per check; eps0 = 0.0 means the jump never fires."""
+    eps0, T = ctypes.c_float(0.0), ctypes.c_uint32(0)
+    _check(lib().qec_near_hard_threshold(float(np.float32(p_prime)), int(R), int(L), ctypes.byref(eps0), ctypes.byref(T)),
+           "qec_near_hard_threshold")
+    return float(eps0.value), int(T.value)
 
 
 def _check(rc, what):

@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -40,6 +41,7 @@
 #include "qec_device.h"
 #include "qec_internal.h"
 #include "qec_launch.h"
+#include "qec_near.h"
 
 #pragma clang fp contract(off)
 
@@ -57,7 +59,8 @@ namespace qec {
 #define QEC_PHASE_STATS 0
 #endif
 // First iteration whose var pass tests whether the sector became hard (iterations 0 and 1 essentially
-// never end hard; skipping the test there only delays the exact hard forms, never changes a bit).
+// never end hard; skipping the test there only delays the exact hard forms, never changes a bit).  A
+// launch with the near-hard jump tests from iteration 1 on: its criterion usually holds there.
 constexpr int kTrackFrom = 2;
 
 // Per-variant tuning: minimum waves per SIMD for the register allocator, and the options above.
@@ -163,8 +166,10 @@ __device__ __forceinline__ bool all_live_sh(bool pred, bool live)
 }
 
 // The hard-message paths need 0 < p' < 1: then every message lies in [0, 1], zeros are +0,
-// and q - q*q == 0 exactly iff q is +0 or 1 (NaN fails the test).
-__device__ __forceinline__ bool hard_ok(float pp) { return pp > 0.0f && pp < 1.0f; }
+// and q - q*q == 0 exactly iff q is +0 or 1 (NaN fails the test).  Evaluated once per launch on the host,
+// which clears BpArgs::hardPaths for any other p' (as a lane mask kept across the iteration loop the
+// device-side compare cost the fixed-stop kernels a scalar register pair they do not have).
+inline bool hard_ok(float pp) { return pp > 0.0f && pp < 1.0f; }
 
 constexpr int kMaxRL = 128;  // largest R*L a kernel argument block carries
 constexpr int kMaxTab0 = 448;  // iteration-0 table entries, (2^RX RX + 2^RZ RZ), of every instantiated variant
@@ -202,6 +207,9 @@ struct BpArgs {
     int maxIter, stop;
     int hardPaths;  // QEC_HP_* bits: hard-message paths / cycle jump (QEC_OPT_HARD_PATHS, QEC_OPT_CYCLE_JUMP)
     int scaled;     // p' in [2^-20, 1/2] (scaled_ok): var passes with at most 4 factors per fold divide guard-free
+    // near-hard jump (qec_near.h), per sector: the compare value T of this launch's
+    // eps0; 0 = off (option off, final messages requested, syndrome stop, or no eps0 for this p')
+    uint32_t nearT[2];
     // lane-relabelled circulant tables (see relabel() below)
     // iteration-0 tables of both sectors computed on the host (launch_decode: the same operations,
     // so the same bits, as table0_entry on the device; each workgroup copies them to LDS)
@@ -588,6 +596,21 @@ __device__ __forceinline__ void return_pass(const BpArgs& a, float (&msg)[R][L],
         }
 }
 
+// The near-hard compare value of this launch and sector (BpArgs::nearT; 0 = off), read from the kernel
+// arguments at each use: the kernel-argument pointer is laundered so that the value is not hoisted into a
+// scalar register live across the whole sector (the fixed- and reference-stop kernels have none to spare:
+// it spilled them).  BpArgs is the kernels' only argument, at offset 0 of the segment.  (Taking the address
+// of a.nearT instead moves the whole argument block to scratch.)
+template <int SEC>
+__device__ __forceinline__ uint32_t near_T(const BpArgs&)
+{
+    static_assert(std::is_standard_layout<BpArgs>::value, "offsetof(BpArgs, nearT)");
+    const __attribute__((address_space(4))) uint32_t* k =
+        (const __attribute__((address_space(4))) uint32_t*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return k[offsetof(BpArgs, nearT) / sizeof(uint32_t) + SEC];
+}
+
 // VarNodeUpdate (DecoderCPU.h:188-229) for variables (l, i): gather the R incoming
 // check messages by forward rotation, update, scatter back by the inverse rotation.
 // LAST: the final iteration includes the self message (DecoderCPU.h:216).
@@ -604,14 +627,23 @@ __device__ __forceinline__ void return_pass(const BpArgs& a, float (&msg)[R][L],
 // SOFT_IN: the caller knows the inputs are soft, so no column takes the agreeing-inputs branch (soft
 // passes are straight-line code per column group: P61 headline +3.6 %, P7 +1 %;
 // profiles/r03/cmp_soft_straight_*.txt).
-template <int R, int L, int SEC, bool LAST, bool HD, class SH, class TU, int CG = 1, bool SOFT_IN = false>
+// near (out; NEAR passes only): every outgoing message is within eps0 of 0 or 1 (near_T, 0 = off) and each
+// variable's R messages lie on one side of 0.5, on every live lane -- the var-view half of the near-hard
+// criterion (iteration tests the checks).
+// NEAR: compiled with the near-hard test (else near comes out false).
+template <int R, int L, int SEC, bool LAST, bool HD, class SH, class TU, int CG = 1, bool SOFT_IN = false,
+          bool NEAR = false>
 __device__ __forceinline__ uint32_t var_pass(const BpArgs& a, float (&msg)[R][L], const Lane& ln, float pp,
-                                             float one_minus_pp, bool& hard, bool& vagree, bool track = true)
+                                             float one_minus_pp, bool& hard, bool& vagree, bool track, bool& near)
 {
     static_assert(L % CG == 0, "column groups must tile the L columns");
     const bool hard_in = !SOFT_IN && CG == 1 && hard;
-    bool vsame = true;  // this lane's variables: all R outputs equal (float compare: NaN is unequal)
-    uint32_t soft_bits = 0;  // OR of bits(q - q*q) over the outputs: 0 iff all are 0 or 1
+    // this lane's variables: all R outputs equal (float compare: NaN is unequal); NEAR: all R on one side
+    // of 0.5, which for hard outputs (+0 or 1.0) is the same
+    bool vsame = true;
+    // unsigned maximum of bits(q - q*q) over the outputs: 0 iff all are +0 or 1.0, <= nearT iff all are
+    // within eps0 of 0 or 1 (a NaN or a negative value is above every nearT)
+    uint32_t soft_bits = 0;
     constexpr int F = LAST ? R : R - 1;  // factors per fold
     constexpr bool kScalable = TU::kFastDiv && F <= 4;
     const bool scaled = kScalable && a.scaled;  // wave-uniform (see scaled_ok)
@@ -748,9 +780,10 @@ __device__ __forceinline__ uint32_t var_pass(const BpArgs& a, float (&msg)[R][L]
                     for (int c = 0; c < CG; ++c) {
 #pragma unroll
                         for (int j = 0; j < ND; ++j)
-                            soft_bits |= __float_as_uint(__builtin_fmaf(-qd[c][j], qd[c][j], qd[c][j]));
+                            soft_bits = max(soft_bits, __float_as_uint(__builtin_fmaf(-qd[c][j], qd[c][j], qd[c][j])));
 #pragma unroll
-                        for (int j = 1; j < ND; ++j) vsame &= qd[c][j] == qd[c][0];
+                        for (int j = 1; j < ND; ++j)
+                            vsame &= NEAR ? (qd[c][j] >= 0.5f) == (qd[c][0] >= 0.5f) : qd[c][j] == qd[c][0];
                     }
                 }
             }
@@ -770,20 +803,26 @@ __device__ __forceinline__ uint32_t var_pass(const BpArgs& a, float (&msg)[R][L]
             }
         }
         if constexpr (TU::kSaturate) {
-            // a soft output in the first column group already decides that the sector does not turn hard in
-            // this pass: the remaining columns skip the hard-state test (its fma and OR per message, compare
-            // per variable), which otherwise costs ~9 % of a soft pass (headline +1.1 %, 50 fixed iterations
-            // at p = 0.1 +7.7 %, P7 +2.6 %; profiles/r06/ab/cmp_track_early.txt)
-            if (l0 == 0 && track && !all_live_sh<SH>(soft_bits == 0u, ln.live)) track = false;
+            // a soft output in the first column group already decides that the sector does not turn hard (or,
+            // with nearT, near-hard) in this pass: the remaining columns skip the hard-state test (its fma and
+            // maximum per message, compare per variable), which otherwise costs ~9 % of a soft pass (headline
+            // +1.1 %, 50 fixed iterations at p = 0.1 +7.7 %, P7 +2.6 %; profiles/r06/ab/cmp_track_early.txt)
+            if (l0 == 0 && track && !all_live_sh<SH>(soft_bits <= (NEAR ? near_T<SEC>(a) : 0u), ln.live)) track = false;
         }
         // a scheduling barrier after each column group: the machine scheduler otherwise hoists work
         // across columns into more live registers (P61 headline +2.8 %, profiles/r03/cmp_col_barrier_*.txt)
         __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (TU::kSaturate) {
-        const bool forms = track && (a.hardPaths & QEC_HP_FORMS) && hard_ok(pp);
+        const bool forms = track && (a.hardPaths & QEC_HP_FORMS);  // (the host cleared it unless hard_ok(p'))
         hard = forms && all_live_sh<SH>(soft_bits == 0u, ln.live);
         vagree = hard && all_live_sh<SH>(vsame, ln.live);
+        // (one ballot of its own, taken only behind forms: a ballot of vsame shared with vagree runs in every
+        // tracked pass and cost the fixed-stop kernels their last registers)
+        if constexpr (NEAR) {
+            const uint32_t nearT = near_T<SEC>(a);
+            near = nearT != 0u && forms && all_live_sh<SH>(soft_bits <= nearT && vsame, ln.live);
+        }
     }
     return hdmask;
 }
@@ -857,6 +896,30 @@ __device__ __forceinline__ bool group_syndrome_ok(const BpArgs& a, uint32_t hdma
     return group_all_sh<SH>(lane_syndrome_ok<R, L, SEC, SH>(a, hdmask, sbits, ln), ln, SH::P(a));
 }
 
+// The check half of the near-hard criterion, lane-local in the check view: with
+// each variable's messages on one side of 0.5 (var_pass's near), h_v = that side, and check (r, i) holds
+// H h = s iff the XOR of (msg[r][l] >= 0.5f) over its L edges is its syndrome bit.  An entry other than
+// 0 / 1 fails, as it fails every syndrome test (load_sbits).
+template <int R, int L>
+__device__ __forceinline__ bool lane_parity_ok(const float (&msg)[R][L], uint32_t sbits)
+{
+    // On sign bits (vector XORs; R L compares into lane masks at once spilled the scalar registers): q - 0.5f
+    // is negative iff q < 0.5f (0.5f - 0.5f = +0; no NaN here, var_pass's near excludes them), so a row's XOR
+    // of the differences carries parity(edges below 0.5) = parity(L) ^ parity(edges at or above it).
+    // (sbits laundered, as in check_pass_hard: the R row seeds are formed here, not hoisted out of the
+    // iteration loop into R live registers)
+    asm volatile("" : "+v"(sbits));
+    uint32_t bad = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        uint32_t x = (((sbits >> r) ^ (uint32_t)L) & 1u) << 31;
+#pragma unroll
+        for (int l = 0; l < L; ++l) x ^= __float_as_uint(msg[r][l] - 0.5f);
+        bad |= x;
+    }
+    return (int32_t)bad >= 0 && !(sbits & kNonBinary);
+}
+
 // Whether a hard sector first tries the whole-sector agreement test (var_pass_agree, the entry to
 // the cycle jump).  Not for the syndrome stop rule: there it costs more than it saves -- with it the
 // P61 kernel spills at 128 VGPRs, without it P61 decodes 4-15 % faster at p = 0.1 .. 0.002 and P7
@@ -896,10 +959,13 @@ constexpr bool kSkipSeen() { return L < 32; }
 // equal), i.e. it mapped msg to check_pass_hard(msg) (wave-uniform).
 // vagree: the new state is hard and each variable's R messages are equal (set on the agreement
 // path, where the new state passed that test; tracked by var_pass otherwise).
+// near: the new state of every live lane's sector meets the near-hard criterion C(eps0) of this launch
+// (qec_near.h; fixed / reference stop, a soft pass that is not the last): every later state does too, so the
+// caller jumps to the sector's end (wave-uniform).
 template <int R, int L, int SEC, int STOP, bool LAST, class SH, class TU>
 __device__ __forceinline__ bool iteration(const BpArgs& a, float (&msg)[R][L], uint32_t sbits, int n, Lane& ln,
                                           float pp, float one_minus_pp, bool& hard, bool& agreed, bool& vagree,
-                                          uint32_t& hd_out, uint32_t (&seen)[2])
+                                          uint32_t& hd_out, uint32_t (&seen)[2], bool& near)
 {
     const int P = SH::P(a);
     // launder the permute bases so their per-rotation selects are recomputed inside the
@@ -909,6 +975,8 @@ __device__ __forceinline__ bool iteration(const BpArgs& a, float (&msg)[R][L], u
     uint32_t hdmask = 0;
     agreed = false;
     vagree = false;
+    near = false;
+    bool unused = false;
     bool var_layout = defer_return<HD, SH>();  // the messages are left in the variable view (defer_return)
     if (TU::kSaturate && hard) {
         check_pass_hard<R, L>(msg, sbits);  // outputs are hard too: hard stays set for the var pass
@@ -919,7 +987,7 @@ __device__ __forceinline__ bool iteration(const BpArgs& a, float (&msg)[R][L], u
         } else {
             // (without the agreement test, a pass whose every column took the agreeing-inputs shortcut could
             // count as the agreement path: 0-6 % slower, profiles/r05/README.md)
-            hdmask = var_pass<R, L, SEC, LAST, HD, SH, TU>(a, msg, ln, pp, one_minus_pp, hard, vagree, true);
+            hdmask = var_pass<R, L, SEC, LAST, HD, SH, TU>(a, msg, ln, pp, one_minus_pp, hard, vagree, true, unused);
         }
     } else {
         check_pass<R, L, TU::kRowBarrier>(msg, sbits);
@@ -930,8 +998,15 @@ __device__ __forceinline__ bool iteration(const BpArgs& a, float (&msg)[R][L], u
         // straight-line pass (var_pass's CG, SOFT_IN).  (One division branch per pass instead of per column
         // group: P61 2x slower, profiles/r03/cmp_soft_straight_*.txt.)
         constexpr int CG = col_group<TU, L>();
-        const bool track = (LAST || n >= kTrackFrom) && (a.hardPaths & QEC_HP_FORMS);
-        hdmask = var_pass<R, L, SEC, LAST, HD, SH, TU, CG, true>(a, msg, ln, pp, one_minus_pp, hard, vagree, track);
+        constexpr bool kNear = TU::kSaturate && !LAST && STOP != QEC_STOP_SYNDROME;
+        const bool from1 = kNear && near_T<SEC>(a) != 0u;
+        const bool track = (LAST || n >= (from1 ? 1 : kTrackFrom)) && (a.hardPaths & QEC_HP_FORMS);
+        hdmask = var_pass<R, L, SEC, LAST, HD, SH, TU, CG, true, kNear>(a, msg, ln, pp, one_minus_pp, hard, vagree, track,
+                                                                        near);
+        // the messages are back in the check view (no deferred return under these stops)
+        if constexpr (kNear) {
+            if (near) near = all_live_sh<SH>(lane_parity_ok<R, L>(msg, sbits), ln.live);
+        }
     }
     if constexpr (STOP == QEC_STOP_REF) {
         if (n % 10 == 0) return group_all_sh<SH>(lane_converged<R, L>(msg), ln, P);  // DecoderCPU.h:287-290
@@ -1315,6 +1390,8 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
     // can read it lane-locally
     bool in_agree = false, st_agreed = false;
     bool agreed = false, vagree = false;
+    // near-hard jump: this iteration's new state meets C(eps0) (iteration)
+    bool near = false;
     int ph_soft = 0, ph_hard = 0, ph_agree = 0, ph_jump = 0;  // QEC_PHASE_STATS
     // syndrome stop rule: the hard decision of the last executed iteration and its syndrome test
     // (hd_valid: the current state is that iteration's output, i.e. not reached by a cycle jump).
@@ -1344,7 +1421,7 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
             ++it;
             const bool was_hard = hard;
             syn_last = iteration<R, L, SEC, STOP, false, SH, TU>(a, msg, sbits, n, ln, pp, one_minus_pp, hard, agreed,
-                                                                 vagree, hd_last, seen);
+                                                                 vagree, hd_last, seen, near);
             hd_valid = true;
             if (syn_last) active = false;
             if constexpr (QEC_PHASE_STATS) { ph_soft += !was_hard; ph_hard += was_hard && !agreed; ph_agree += agreed; }
@@ -1362,6 +1439,26 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
                     n = N;  // skips the peeled last iteration too
                 }
                 in_agree = vagree;
+                // near-hard jump: C(eps0) holds from here on with this state's h, so
+                // the final decisions are h, both flags are clear and the sector ends where cycle_end puts it
+                // (under the reference stop a state tested at this n has already stopped: active is clear).
+                // The registers take h itself (+0 / 1.0 by each message's side of 0.5): a hard state whose
+                // variables agree and whose checks hold, which the agreeing-state post-processing below reads
+                // to exactly those outputs (the messages are not an output of such a launch).
+                if constexpr (STOP != QEC_STOP_SYNDROME) {
+                    if (near && active) {
+#pragma unroll
+                        for (int r = 0; r < R; ++r)
+#pragma unroll
+                            for (int l = 0; l < L; ++l) msg[r][l] = msg[r][l] >= 0.5f ? 1.0f : 0.0f;
+                        st_agreed = true;
+                        const int last = cycle_end<STOP>(n, N);
+                        it += last - n;
+                        if constexpr (QEC_PHASE_STATS) ph_jump = last - n;
+                        active = false;
+                        n = N;  // skips the peeled last iteration too
+                    }
+                }
             }
         }
     }
@@ -1369,7 +1466,7 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
         ++it;
         const bool was_hard = hard;
         syn_last = iteration<R, L, SEC, STOP, true, SH, TU>(a, msg, sbits, n, ln, pp, one_minus_pp, hard, agreed, vagree,
-                                                            hd_last, seen);
+                                                            hd_last, seen, near);
         hd_valid = true;
         if constexpr (QEC_PHASE_STATS) { ph_soft += !was_hard; ph_hard += was_hard && !agreed; ph_agree += agreed; }
         st_agreed = vagree;
@@ -1965,8 +2062,14 @@ int launch_decode(const void* variant, const Code& c, const uint8_t* sX, const u
     a.errorProbability = errorProbability;
     a.maxIter = maxIter < 0 ? 0 : maxIter;
     a.stop = stop;
-    a.hardPaths = hardPaths & (QEC_HP_FORMS | QEC_HP_CYCLE);
+    a.hardPaths = hard_ok(2.0f / 3.0f * errorProbability) ? hardPaths & (QEC_HP_FORMS | QEC_HP_CYCLE | QEC_HP_NEAR) : 0;
     a.scaled = scaled_ok(2.0f / 3.0f * errorProbability) ? 1 : 0;
+    // near-hard jump: the outputs are decisions, flags and count only, under the fixed / reference stop
+    // (no threshold for a p' outside (0, 1/2], where hard_ok or the lemma fails: T = 0)
+    if ((hardPaths & QEC_HP_FORMS) && (hardPaths & QEC_HP_NEAR) && q == nullptr && stop != QEC_STOP_SYNDROME) {
+        a.nearT[0] = near_hard_threshold(2.0f / 3.0f * errorProbability, c.J, c.L).T;
+        a.nearT[1] = near_hard_threshold(2.0f / 3.0f * errorProbability, c.K, c.L).T;
+    }
     v->fill_tab0(2.0f / 3.0f * errorProbability, a.tab0);  // p' as the kernel forms it
     if (!phase)
         for (int sec = 0; sec < 2; ++sec) a.zs[sec] = v->zero_out[sec](2.0f / 3.0f * errorProbability, a.maxIter, stop);
@@ -2066,7 +2169,8 @@ int launch_decode_list(const void* variant, const Code& c, const uint8_t* sX, co
     a.errorProbability = errorProbability;
     a.maxIter = maxIter < 0 ? 0 : maxIter;
     a.stop = QEC_STOP_SYNDROME;
-    a.hardPaths = hardPaths & (QEC_HP_FORMS | QEC_HP_CYCLE);
+    // (syndrome stop: nearT stays 0)
+    a.hardPaths = hard_ok(2.0f / 3.0f * errorProbability) ? hardPaths & (QEC_HP_FORMS | QEC_HP_CYCLE | QEC_HP_NEAR) : 0;
     a.scaled = scaled_ok(2.0f / 3.0f * errorProbability) ? 1 : 0;
     v->fill_tab0(2.0f / 3.0f * errorProbability, a.tab0);
     relabel(c.EX.data(), c.J, c.L, c.P, v->relabel, a.SX, a.DX, a.CX);

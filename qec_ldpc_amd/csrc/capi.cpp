@@ -11,6 +11,7 @@
 
 #include "../../include/HostDeviceArray.h"
 #include "qec_internal.h"
+#include "qec_near.h"
 #include "qec_osd.h"
 
 namespace {
@@ -82,7 +83,8 @@ void* cpu_plan_create(const Code& c);
 void cpu_plan_free(void* plan);
 int cpu_threads();
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
-                     uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads);
+                     uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
+                     bool near_hard);
 int launch_pack_decisions(const uint8_t* eX, const uint8_t* eZ, const uint8_t* flags, long long B, int n, uint8_t* out,
                           hipStream_t st);
 int launch_statistics(const Code& c, const uint64_t* imp_cols, const uint8_t* x, const uint8_t* z, const uint8_t* eX,
@@ -137,6 +139,7 @@ struct qec_decoder {
     std::string variant_name;
     int hard_paths = 1;             // QEC_OPT_HARD_PATHS
     int cycle_jump = 1;             // QEC_OPT_CYCLE_JUMP
+    int near_hard = 1;              // QEC_OPT_NEAR_HARD_JUMP
     int schedule = 1;               // QEC_OPT_SCHEDULE (0 off, 1 auto, 2 always, 3 / 4 always, local / one-launch order)
     int sector_split = 1;           // QEC_OPT_SECTOR_SPLIT (0 off, 1 auto, 2 split waves, 3 sector launches)
     int phase_stats = 0;            // QEC_OPT_PHASE_STATS
@@ -576,6 +579,15 @@ int qec_decoder_describe(const qec_decoder* d, char* buf, size_t len)
     return QEC_OK;
 }
 
+int qec_near_hard_threshold(float pPrime, int R, int L, float* eps0, uint32_t* T)
+{
+    if (!eps0 || !T) return fail(QEC_ERR_ARG, "qec_near_hard_threshold: bad argument");
+    const NearHard t = near_hard_threshold(pPrime, R, L);
+    *eps0 = t.eps0;
+    *T = t.T;
+    return QEC_OK;
+}
+
 int qec_decoder_set_option(qec_decoder* d, int option, int value)
 {
     if (!d) return fail(QEC_ERR_ARG, "qec_decoder_set_option: null decoder");
@@ -586,6 +598,7 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
     switch (option) {
     case QEC_OPT_HARD_PATHS: d->hard_paths = value != 0; return QEC_OK;
     case QEC_OPT_CYCLE_JUMP: d->cycle_jump = value != 0; return QEC_OK;
+    case QEC_OPT_NEAR_HARD_JUMP: d->near_hard = value != 0; return QEC_OK;
     case QEC_OPT_SCHEDULE:
         if (value < 0 || value > 4) return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_SCHEDULE is 0 .. 4");
         d->schedule = value;
@@ -639,6 +652,7 @@ int qec_decoder_get_option(const qec_decoder* d, int option, int* value)
     switch (option) {
     case QEC_OPT_HARD_PATHS: *value = d->hard_paths; return QEC_OK;
     case QEC_OPT_CYCLE_JUMP: *value = d->cycle_jump; return QEC_OK;
+    case QEC_OPT_NEAR_HARD_JUMP: *value = d->near_hard; return QEC_OK;
     case QEC_OPT_SCHEDULE: *value = d->schedule; return QEC_OK;
     case QEC_OPT_SECTOR_SPLIT: *value = d->sector_split; return QEC_OK;
     case QEC_OPT_PHASE_STATS: *value = d->phase_stats; return QEC_OK;
@@ -691,7 +705,8 @@ constexpr long long kSplitOrderedMinBatch = 1LL << 19;
 
 int hard_path_bits(const qec_decoder* d)
 {
-    return (d->hard_paths ? (QEC_HP_FORMS | (d->cycle_jump ? QEC_HP_CYCLE : 0)) : 0) | (d->phase_stats ? QEC_HP_PHASE : 0);
+    return (d->hard_paths ? (QEC_HP_FORMS | (d->cycle_jump ? QEC_HP_CYCLE : 0) | (d->near_hard ? QEC_HP_NEAR : 0)) : 0) |
+           (d->phase_stats ? QEC_HP_PHASE : 0);
 }
 
 // QEC_OPT_TRIAGE: 1 (auto) and 3 (auto, never the fused Monte-Carlo kernel) up to kTriageMaxP, 2 always
@@ -900,7 +915,8 @@ int osd_repair_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t
             cq.resize(cnt * qn);
             cFs.resize(cnt);
             const int rc = cpu_decode_batch(d->cpu, cX.data(), cZ.data(), (long long)cnt, p, d->osd_iters, QEC_STOP_FIXED,
-                                            cEX.data(), cEZ.data(), cFs.data(), nullptr, nullptr, cq.data(), 0);
+                                            cEX.data(), cEZ.data(), cFs.data(), nullptr, nullptr, cq.data(), 0,
+                                            false);
             if (rc) return rc;
             long long swept = 0;
             osd_host_batch(*d->oplan, cX.data(), cZ.data(), (long long)cnt, cq.data(), cEX.data(), cEZ.data(), cF.data(), 0,
@@ -1017,7 +1033,8 @@ int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
     d->osd_cs_sectors = 0;
     if (B == 0) return QEC_OK;
     if (d->cpu) {
-        const int rc = cpu_decode_batch(d->cpu, sX, sZ, (long long)B, p, maxIter, stop, eX, eZ, flags, rec, iters, q, 0);
+        const int rc = cpu_decode_batch(d->cpu, sX, sZ, (long long)B, p, maxIter, stop, eX, eZ, flags, rec, iters, q, 0,
+                                        d->hard_paths && d->near_hard);
         d->last_path = 0;
         return rc || !d->osd ? rc : osd_repair_host(d, sX, sZ, B, p, eX, eZ, flags, rec);
     }
@@ -1366,7 +1383,7 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
         ez.resize((size_t)cnt * n);
         fl.resize(cnt);
         const int rc = cpu_decode_batch(d->cpu, sx.data(), sz.data(), cnt, p, maxIter, QEC_STOP_REF, ex.data(), ez.data(),
-                                        fl.data(), nullptr, nullptr, nullptr, 0);
+                                        fl.data(), nullptr, nullptr, nullptr, 0, d->hard_paths && d->near_hard);
         if (rc) return rc;
         if (d->osd) {  // the counters describe the repaired estimates
             d->osd_sectors = 0;

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "qec_internal.h"
+#include "qec_near.h"
 
 namespace qec {
 
@@ -70,10 +71,39 @@ struct Work {
     std::vector<uint8_t> e;
 };
 
+// The near-hard criterion C(eps0) (qec_near.h) on the messages q after a var pass:
+// every message within eps0 of 0 or 1 (nearT: the compare value of eps0), each variable's messages on one
+// side of 0.5, and the sides' parity on every check equal to its syndrome entry (an entry other than 0 / 1
+// fails, as it fails the syndrome test).
+bool near_hard_state(const CpuSector& S, int n, const uint8_t* syn, const float* q, uint32_t nearT)
+{
+    const int m = S.m, dc = S.dc, dv = S.dv;
+    for (size_t k = 0, E = (size_t)m * dc; k < E; ++k) {
+        const float t = __builtin_fmaf(-q[k], q[k], q[k]);
+        uint32_t b;
+        std::memcpy(&b, &t, sizeof b);
+        if (b > nearT) return false;
+    }
+    for (int v = 0; v < n; ++v) {
+        const int32_t* ve = S.var_edge.data() + (size_t)v * dv;
+        for (int j = 1; j < dv; ++j)
+            if ((q[ve[j]] >= 0.5f) != (q[ve[0]] >= 0.5f)) return false;
+    }
+    for (int c = 0; c < m; ++c) {
+        uint32_t x = 0;
+        for (int k = 0; k < dc; ++k) x ^= (uint32_t)(q[(size_t)c * dc + k] >= 0.5f);
+        if (x != syn[c]) return false;
+    }
+    return true;
+}
+
 // One sector's BeliefPropogation + the Decode post-processing (DecoderCPU.h:249-292, 354-384).
 // Returns the iterations executed; e gets the hard decision, conv / syn_ok the flag tests.
+// nearT != 0 (fixed / reference stop, no final messages requested): the near-hard jump -- once a state
+// meets C(eps0) every later one does, so the post-processing of this state gives the final decisions and
+// flags and the count is where the stop rule ends such a sector.
 int decode_sector(const CpuSector& S, int n, const uint8_t* syn, float errorProbability, int N, int stop, Work& w,
-                  bool& conv_out, bool& syn_ok, float* q_out)
+                  bool& conv_out, bool& syn_ok, float* q_out, uint32_t nearT)
 {
     const int m = S.m, dc = S.dc, dv = S.dv;
     const size_t E = (size_t)m * dc;
@@ -135,7 +165,14 @@ int decode_sector(const CpuSector& S, int n, const uint8_t* syn, float errorProb
                 conv = true;
                 for (size_t k = 0; k < E && conv; ++k) conv = outside(q[k]);
             }
-        } else if (stop == QEC_STOP_SYNDROME) {
+        }
+        if (nearT != 0u && !last && !(stop == QEC_STOP_REF && conv) && near_hard_state(S, n, syn, q, nearT)) {
+            // fixed: every iteration counts; reference: the convergence test passes at the next tested iteration
+            const int next10 = (iter / 10 + 1) * 10;
+            it = (stop == QEC_STOP_REF && next10 < N - 1 ? next10 : N - 1) + 1;
+            break;
+        }
+        if (stop == QEC_STOP_SYNDROME) {
             hard_decision();
             if (syndrome_ok()) break;
         }
@@ -174,12 +211,17 @@ int cpu_threads()
 
 // Batched Decode on host buffers; outputs in byte form (eX, eZ, flags) and/or packed records.
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
-                     uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads)
+                     uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
+                     bool near_hard)
 {
     const CpuPlan& P = *static_cast<const CpuPlan*>(plan);
     const int n = P.n, nb = (n + 7) / 8;
     const int mX = P.sec[0].m, mZ = P.sec[1].m;
     const size_t qper = (size_t)mX * P.sec[0].dc + (size_t)mZ * P.sec[1].dc;
+    // near-hard jump (QEC_OPT_NEAR_HARD_JUMP): per-sector compare values for this p', as the kernels' launch
+    uint32_t nearT[2] = {0u, 0u};
+    if (near_hard && qf == nullptr && stop != QEC_STOP_SYNDROME)
+        for (int sec = 0; sec < 2; ++sec) nearT[sec] = near_hard_threshold((2.0f / 3.0f) * p, P.sec[sec].dv, P.sec[sec].dc).T;
     if (threads <= 0) threads = cpu_threads();
     threads = (int)std::max<long long>(1, std::min<long long>(threads, B));
     auto run = [&](long long lo, long long hi) {
@@ -194,7 +236,8 @@ int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long
                 const CpuSector& S = P.sec[sec];
                 bool conv = false, ok = false;
                 float* qo = qf ? qf + b * qper + (sec ? (size_t)mX * P.sec[0].dc : 0) : nullptr;
-                const int it = decode_sector(S, n, sec ? sZ + b * mZ : sX + b * mX, p, maxIter, stop, w, conv, ok, qo);
+                const int it = decode_sector(S, n, sec ? sZ + b * mZ : sX + b * mX, p, maxIter, stop, w, conv, ok, qo,
+                                             nearT[sec]);
                 if (!ok) f |= sec ? QEC_SYNDROME_FAIL_Z : QEC_SYNDROME_FAIL_X;
                 if (!conv) f |= sec ? QEC_CONVERGENCE_FAIL_Z : QEC_CONVERGENCE_FAIL_X;
                 if (iters) iters[2 * b + sec] = it;

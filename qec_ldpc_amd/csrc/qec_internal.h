@@ -9,8 +9,9 @@
 
 namespace qec {
 
-// BpArgs::hardPaths bits (from QEC_OPT_HARD_PATHS / QEC_OPT_CYCLE_JUMP)
-enum { QEC_HP_FORMS = 1, QEC_HP_CYCLE = 2, QEC_HP_PHASE = 4 /* launch the instrumented kernel */ };
+// BpArgs::hardPaths bits (from QEC_OPT_HARD_PATHS / QEC_OPT_CYCLE_JUMP / QEC_OPT_NEAR_HARD_JUMP)
+enum { QEC_HP_FORMS = 1, QEC_HP_CYCLE = 2, QEC_HP_PHASE = 4 /* launch the instrumented kernel */,
+       QEC_HP_NEAR = 8 /* the near-hard jump (qec_near.h); only with QEC_HP_FORMS */ };
 // dispatch-order method (schedule.hip, launch_schedule): the global counting sort, the one-launch
 // chunk-local order or the global sort in one launch with a software grid barrier (both measured
 // slower; experiments)
