@@ -41,7 +41,28 @@ public:
         return Quantum_LDPC_Code(h);
     }
 
-    // adopt a handle from qec_code_load / qec_code_generate
+    // A general CSS code from its two 0/1 parity-check matrices (qec_code_from_matrices): any row and
+    // column weights; J = K = L = P = sigma = tau = 0.  No reference analogue.  Throws std::string.
+    static Quantum_LDPC_Code createFromMatrices(const IntArray2d_h& HX, const IntArray2d_h& HZ)
+    {
+        if (HX.num_cols != HZ.num_cols) throw std::string("createFromMatrices: HX and HZ differ in columns");
+        std::vector<uint8_t> x(HX.values.size()), z(HZ.values.size());
+        for (size_t k = 0; k < x.size(); ++k) x[k] = (uint8_t)(HX.values[k] == 0 ? 0 : HX.values[k] == 1 ? 1 : 2);
+        for (size_t k = 0; k < z.size(); ++k) z[k] = (uint8_t)(HZ.values[k] == 0 ? 0 : HZ.values[k] == 1 ? 1 : 2);
+        qec_code* h = qec_code_from_matrices(HX.num_cols, HX.num_rows, x.data(), HZ.num_rows, z.data());
+        if (!h) throw std::string(qec_last_error());
+        return Quantum_LDPC_Code(h);
+    }
+
+    // max row weight X, Z, max column weight X, Z, slot stride D of the message layout (qec_code_degrees)
+    std::vector<int> degrees() const
+    {
+        std::vector<int> d(5);
+        qec_code_degrees(handle_.get(), d.data());
+        return d;
+    }
+
+    // adopt a handle from qec_code_load / qec_code_generate / qec_code_from_matrices
     explicit Quantum_LDPC_Code(qec_code* h) : handle_(h, [](qec_code* p) { qec_code_free(p); })
     {
         int v[9];
@@ -101,6 +122,11 @@ private:
 // Quantum_LDPC_Code.h:145-150
 inline std::ostream& operator<<(std::ostream& stream, const Quantum_LDPC_Code& code)
 {
+    if (code.L == 0) {  // a general code: "[[n=..,k=..]]" with k = n - rank HX - rank HZ
+        char buf[128];
+        qec_code_describe(code.handle(), buf, sizeof buf);
+        return stream << buf;
+    }
     stream << "[J=" << code.J << ",K=" << code.K << ",L=" << code.L << ",P=" << code.P << ",s=" << code.sigma
            << ",t=" << code.tau << "][[n=" << code.n << ",k=" << code.numEqsZ - code.numEqsX << "]]";
     return stream;

@@ -100,8 +100,22 @@ const char* qec_build_id(void);
 
 /* ---- code model ----------------------------------------------------------- */
 /* Replaces Quantum_LDPC_Code::createFromFile (QEC_LDPC/Quantum_LDPC_Code.h:26-80):
- * 4-line text file "J K L P sigma tau" / HX / HZ / I-P.  NULL on error. */
+ * 4-line text file "J K L P sigma tau" / HX / HZ / I-P.  NULL on error.
+ * A first line "css n mX mZ" instead reads a general code (qec_code_from_matrices): HX (mX x n), HZ
+ * (mZ x n) and an optional I-P line (2n x 2n) follow in the same matrix syntax. */
 qec_code* qec_code_load(const char* path);
+/* A general CSS code from its two parity-check matrices (no reference analogue), dense row-major 0/1
+ * bytes HX: mX x n, HZ: mZ x n.  Any row and column weights; an all-zero column (a qubit in no check of
+ * that sector) is allowed.  The code has J = K = L = P = sigma = tau = 0, no I-P matrix
+ * (qec_code_with_logical derives one) and no exponent tables.  Its message / q_final layout has one
+ * slot stride D for both sectors, the largest row weight (qec_code_degrees); BP runs each node with its
+ * own degree.  The sparse-graph engine and the CPU engine decode it (D <= 32 and
+ * column weights <= 16 on the GPU).  NULL with QEC_ERR_ARG for an entry other than 0 / 1, an all-zero
+ * row, or n, mX or mZ <= 0; the text names the row or entry. */
+qec_code* qec_code_from_matrices(int n, int mX, const uint8_t* HX, int mZ, const uint8_t* HZ);
+/* out[5] = largest row weight of HX, of HZ, largest column weight of HX, of HZ, and the slot stride
+ * D = the larger row weight.  Any code; a regular one gives L, L, J, K, L. */
+int qec_code_degrees(const qec_code* code, int* out5);
 /* Replaces the QC_LDPC_CSS(J,K,L,P,sigma,tau) generator (QEC_LDPC/QEC_LDPC_CSS.cu:5-131).
  * Generated codes carry no I-P matrix (the reference never generates one); qec_code_with_logical
  * derives the check from the two matrices. */
@@ -114,7 +128,8 @@ int qec_code_params(const qec_code* code, int* out9);
 int qec_code_exponents(const qec_code* code, int sector, int* out);
 /* dense parity-check matrix pcmX / pcmZ (m x n, 0/1) */
 int qec_code_pcm(const qec_code* code, int sector, uint8_t* out);
-/* "[J=..,K=..,L=..,P=..,s=..,t=..][[n=..,k=..]]" (Quantum_LDPC_Code.h:145-150) */
+/* "[J=..,K=..,L=..,P=..,s=..,t=..][[n=..,k=..]]" (Quantum_LDPC_Code.h:145-150); a general code:
+ * "[[n=..,k=..]]" with k = n - rank HX - rank HZ */
 int qec_code_describe(const qec_code* code, char* buf, size_t len);
 /* Quantum_LDPC_Code::GetSyndromeX/Z (Quantum_LDPC_Code.h:94-124) for B error vectors,
  * e: B x n (0/1) -> s: B x m (host memory) */
@@ -191,6 +206,8 @@ int qec_decoder_device(const qec_decoder* dec);         /* HIP device ordinal (o
  *     qec_near_hard_threshold), so the decisions, both flags and the iteration count are known and the
  *     sector jumps to its end.  Every output bit identical either way; 0 runs those iterations (for
  *     measurement).  A call that requests q_final, and the soft decode of the OSD stage, never jump.
+ *     Nor does any decode of a general code (qec_code_from_matrices): the lemma is stated for one
+ *     column weight R and one row weight L; outputs do not depend on the jump either way.
  *   QEC_OPT_SCHEDULE (default 1): dispatch order of the wave-circulant launch.  Two small
  *     kernels (a counting sort) order the batch by syndrome weight and the decode waves take syndromes heaviest
  *     first, so the rare syndromes that run every iteration in full arithmetic start early
@@ -309,7 +326,10 @@ int qec_decoder_describe(const qec_decoder* dec, char* buf, size_t len);
  *   flags: B                           ErrorCode bits per syndrome pair
  *   iters: B x 2 (optional)            BP iterations executed (X, Z)
  *   q_final: B x (numEqsX+numEqsZ) x L (optional) final variable->check messages,
- *            [check][slot] with slots in ascending variable order (X block first)
+ *            [check][slot] with slots in ascending variable order (X block first).
+ *            A general code (qec_code_from_matrices): the stride is D of qec_code_degrees
+ *            instead of L, B x (numEqsX+numEqsZ) x D; a check of lower weight leaves its
+ *            last slots unused, written as +0.0f
  * errorProbability / maxIterations as in Decode; stop = QEC_STOP_*. */
 int qec_decode_batch(qec_decoder* dec, const uint8_t* sX, const uint8_t* sZ, size_t B,
                      float errorProbability, int maxIterations, int stop,

@@ -37,7 +37,8 @@ PATH = {"ordered": 1, "sector_order": 2, "split_waves": 4, "sector_launches": 8,
 # every symbol include/qec_ldpc.h declares
 EXPORTS = (
     "qec_last_error", "qec_abi_version", "qec_build_id",
-    "qec_code_load", "qec_code_generate", "qec_code_free", "qec_code_params", "qec_code_exponents",
+    "qec_code_load", "qec_code_generate", "qec_code_from_matrices", "qec_code_degrees", "qec_code_free",
+    "qec_code_params", "qec_code_exponents",
     "qec_code_pcm", "qec_code_describe", "qec_code_syndrome", "qec_code_check_logical",
     "qec_code_with_logical", "qec_code_logical_mode", "qec_code_logical_rows", "qec_code_imp",
     "qec_decoder_create", "qec_decoder_create_engine", "qec_decoder_create_multi", "qec_decoder_destroy",
@@ -116,6 +117,8 @@ def lib():
             "qec_build_id": (ctypes.c_char_p, []),
             "qec_code_load": (vp, [ctypes.c_char_p]),
             "qec_code_generate": (vp, [i, i, i, i, i, i]),
+            "qec_code_from_matrices": (vp, [i, i, vp, i, vp]),
+            "qec_code_degrees": (i, [vp, vp]),
             "qec_code_free": (i, [vp]),
             "qec_code_params": (i, [vp, vp]),
             "qec_code_exponents": (i, [vp, i, vp]),
@@ -220,6 +223,8 @@ class Quantum_LDPC_Code:
         _check(lib().qec_code_params(self._h, _ptr(v)), "qec_code_params")
         (self.J, self.K, self.L, self.P, self.sigma, self.tau, self.n, self.numEqsX,
          self.numEqsZ) = (int(x) for x in v)
+        # slots per check of the message / q_final layout: L, or D of a general code (degrees()[4])
+        self.stride = self.L if self.L else self.degrees()[4]
 
     @staticmethod
     def createFromFile(path):
@@ -229,6 +234,33 @@ class Quantum_LDPC_Code:
         return Quantum_LDPC_Code(h)
 
     load = createFromFile
+
+    @staticmethod
+    def createFromMatrices(HX, HZ):
+        """A general CSS code from its two 0/1 parity-check matrices (qec_code_from_matrices): any row
+        and column weights, HX [mX, n] and HZ [mZ, n].  J = K = L = P = sigma = tau = 0; with_logical
+        derives its logical check."""
+        HX, HZ = np.asarray(HX), np.asarray(HZ)
+        if HX.ndim != 2 or HZ.ndim != 2 or HX.shape[1] != HZ.shape[1]:
+            raise QecError("createFromMatrices: HX and HZ must be 2-D with the same number of columns")
+        for name, H in (("HX", HX), ("HZ", HZ)):
+            bad = np.argwhere((H != 0) & (H != 1))
+            if len(bad):  # before the cast to bytes folds the value
+                r, v = (int(x) for x in bad[0])
+                raise QecError("createFromMatrices: %s[%d][%d] = %r is not 0 or 1" % (name, r, v, H[r, v].item()))
+        hx = np.ascontiguousarray(HX, dtype=np.uint8)
+        hz = np.ascontiguousarray(HZ, dtype=np.uint8)
+        h = lib().qec_code_from_matrices(hx.shape[1], hx.shape[0], _ptr(hx), hz.shape[0], _ptr(hz))
+        if not h:
+            raise QecError(last_error())
+        return Quantum_LDPC_Code(h)
+
+    def degrees(self):
+        """(max row weight X, max row weight Z, max column weight X, max column weight Z, slot stride D)
+        (qec_code_degrees); a regular code gives (L, L, J, K, L)."""
+        v = np.zeros(5, dtype=np.int32)
+        _check(lib().qec_code_degrees(self._h, _ptr(v)), "qec_code_degrees")
+        return tuple(int(x) for x in v)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -427,7 +459,7 @@ class DecoderGPU:
         eZ = np.empty((B, c.n), dtype=np.uint8)
         flags = np.empty(B, dtype=np.uint8)
         iters = np.empty((B, 2), dtype=np.int32) if want_iters else None
-        q = np.empty((B, (c.numEqsX + c.numEqsZ) * c.L), dtype=np.float32) if want_q else None
+        q = np.empty((B, (c.numEqsX + c.numEqsZ) * c.stride), dtype=np.float32) if want_q else None
         _check(lib().qec_decode_batch(self._h, _ptr(sX), _ptr(sZ), B, float(p), int(max_iter), STOP[stop],
                                       _ptr(eX), _ptr(eZ), _ptr(flags), _ptr(iters), _ptr(q)), "qec_decode_batch")
         return eX, eZ, flags, iters, q
@@ -456,7 +488,7 @@ class DecoderGPU:
         B = sX.shape[0]
         sX = _u8(sX, (B, c.numEqsX))
         sZ = _u8(sZ, (B, c.numEqsZ))
-        q = np.ascontiguousarray(q, dtype=np.float32).reshape(B, (c.numEqsX + c.numEqsZ) * c.L)
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(B, (c.numEqsX + c.numEqsZ) * c.stride)
         eX = _u8(eX, (B, c.n)).copy()
         eZ = _u8(eZ, (B, c.n)).copy()
         flags = _u8(flags, (B,)).copy()
@@ -531,7 +563,7 @@ class DecoderGPU:
                 B, float(p), int(max_iter), STOP[stop],
                 self._t(eX, "eX", u8, (B, c.n)), self._t(eZ, "eZ", u8, (B, c.n)), self._t(flags, "flags", u8, (B,)),
                 self._t(iters, "iters", torch.int32, (B, 2), True),
-                self._t(q, "q", torch.float32, (B, (c.numEqsX + c.numEqsZ) * c.L), True))
+                self._t(q, "q", torch.float32, (B, (c.numEqsX + c.numEqsZ) * c.stride), True))
         return self._issue("qec_decode_batch_dev", (self._h, *args, ctypes.c_void_p(self._stream(stream))))
 
     def decode_batch_packed_dev(self, sX, sZ, p, max_iter, stop, records, iters=None, q=None, stream=None):
@@ -545,7 +577,7 @@ class DecoderGPU:
                 B, float(p), int(max_iter), STOP[stop],
                 self._t(records, "records", u8, (B, self.record_bytes())),
                 self._t(iters, "iters", torch.int32, (B, 2), True),
-                self._t(q, "q", torch.float32, (B, (c.numEqsX + c.numEqsZ) * c.L), True))
+                self._t(q, "q", torch.float32, (B, (c.numEqsX + c.numEqsZ) * c.stride), True))
         return self._issue("qec_decode_batch_packed_dev", (self._h, *args, ctypes.c_void_p(self._stream(stream))))
 
     def decode_bits_packed_dev(self, sXbits, sZbits, p, max_iter, stop, records, iters=None, q=None, stream=None):
@@ -560,7 +592,7 @@ class DecoderGPU:
                 B, float(p), int(max_iter), STOP[stop],
                 self._t(records, "records", torch.uint8, (B, self.record_bytes())),
                 self._t(iters, "iters", torch.int32, (B, 2), True),
-                self._t(q, "q", torch.float32, (B, (c.numEqsX + c.numEqsZ) * c.L), True))
+                self._t(q, "q", torch.float32, (B, (c.numEqsX + c.numEqsZ) * c.stride), True))
         return self._issue("qec_decode_bits_packed_dev", (self._h, *args, ctypes.c_void_p(self._stream(stream))))
 
     def osd_dev(self, sX, sZ, q, eX, eZ, flags, stream=None):
@@ -575,7 +607,7 @@ class DecoderGPU:
         B = sX.shape[0]
         u8 = torch.uint8
         args = (self._t(sX, "sX", u8, (B, c.numEqsX)), self._t(sZ, "sZ", u8, (B, c.numEqsZ)), B,
-                self._t(q, "q", torch.float32, (B, (c.numEqsX + c.numEqsZ) * c.L)),
+                self._t(q, "q", torch.float32, (B, (c.numEqsX + c.numEqsZ) * c.stride)),
                 self._t(eX, "eX", u8, (B, c.n)), self._t(eZ, "eZ", u8, (B, c.n)), self._t(flags, "flags", u8, (B,)))
         return self._issue("qec_osd_dev", (self._h, *args, ctypes.c_void_p(self._stream(stream))))
 

@@ -45,3 +45,22 @@ def write_code_file(path, J, K, L, P, sigma, tau, HX, HZ, IMP=None):
         f.write(row(HZ) + "\n")
         f.write(row(IMP) + "\n")
     return path
+
+
+def write_css_file(path, HX, HZ, IMP=None):
+    """Write a general code in the "css" text form qec_code_load reads: "css n mX mZ" / HX row-major /
+    HZ row-major / optionally I-P (2n x 2n) row-major."""
+    import numpy as np
+
+    HX, HZ = np.asarray(HX, dtype=np.uint8), np.asarray(HZ, dtype=np.uint8)
+
+    def row(a):
+        return " ".join(map(str, np.asarray(a, dtype=np.uint8).ravel().tolist()))
+
+    with open(path, "w") as f:
+        f.write("css %d %d %d\n" % (HX.shape[1], HX.shape[0], HZ.shape[0]))
+        f.write(row(HX) + "\n")
+        f.write(row(HZ) + "\n")
+        if IMP is not None:
+            f.write(row(IMP) + "\n")
+    return path

@@ -238,8 +238,254 @@ __global__ __launch_bounds__(kSparseThreads) void bp_sparse_kernel(const SparseA
     }
 }
 
+// ---- general codes (qec_code_from_matrices) -------------
+// The same kernel plan for a graph whose nodes have their own degrees.  Layout: msg[c * D + k] with
+// one slot stride D (the largest row weight of both sectors); check c uses its first deg(c) slots and
+// the others hold +0.0f from the initialisation to the q_final export.  Tables:
+// chkVar [mX + mZ][D] and varEdge [n][dvX] / [n][dvZ] (the sectors' largest column weights), padded
+// with -1, and one degree byte per check.
+//   * check pass: a padded slot's input is +0.0f, so its factor fma(-2, 0, 1) is exactly 1.0f and
+//     t * 1.0f == t bit for bit (denormals kept, a NaN stays that NaN): the folds run unpredicated over
+//     the uniform stride D, behind the real factors, and only the store asks for the check's degree.
+//     The degree travels in the check's LDS syndrome byte (bits 2..7; bits 0..1 = the entry as 0, 1 or
+//     "other", all the update and the tests distinguish), so the pass reads nothing from global memory;
+//     an unused slot is stored too, as +0.0f again (a select instead of a masked store).
+//   * variable pass: the edge ids of the sector's stride are loaded unconditionally and the sentinel
+//     tells which are real (they come first).  A padded entry enters the folds as g = 1 - g = 1.0f, the
+//     same exact no-op, chosen by selects, so no arithmetic runs under a per-thread predicate: entry j is
+//     skipped by a scalar branch when no thread of the wave has it (the compare's lane mask is that
+//     test), computed by every lane otherwise, and only its store is masked -- and not even that when
+//     every lane has it, which is every wave of a regular code.  A variable in no check touches nothing
+//     and decides 0.
+//   * the convergence test reads every slot: +0.0f is outside (0.01, 0.99), as a real hard message is.
+//   * the syndrome tests and the final hard decision walk the whole stride and select on the sentinel
+//     (an early exit would chain the table loads one behind the other).
+// For a regular code D = L and every stored value equals bp_sparse_kernel's.
+// The workgroup is the smallest of 64 / 128 / 256 threads that covers the wider pass, max(mX + mZ, 2n):
+// a small code then pays for one or two waves at every barrier instead of four.
+template <int MAXDC>
+__device__ __forceinline__ void sp_check_general(float* __restrict__ m, int D, int deg, float h)
+{
+    float av[MAXDC];
+#pragma unroll
+    for (int k = 0; k < MAXDC; ++k)
+        if (k < D) av[k] = __builtin_fmaf(-2.0f, m[k], 1.0f);
+    float pre = 1.0f;
+#pragma unroll
+    for (int i = 0; i < MAXDC; ++i) {
+        if (i < D) {
+            float t = pre;
+#pragma unroll
+            for (int k = i + 1; k < MAXDC; ++k)
+                if (k < D) t = t * av[k];
+            m[i] = i < deg ? __builtin_fmaf(h, t, 0.5f) : 0.0f;  // an unused slot keeps +0.0f
+            pre = pre * av[i];
+        }
+    }
+}
+
+template <int MAXDV>
+__device__ __forceinline__ bool sp_var_general(float* __restrict__ msg, const int32_t* __restrict__ ve, int stride,
+                                               float pp, float omp, bool last)
+{
+    int idx[MAXDV];
+    bool any[MAXDV], all[MAXDV];  // wave-uniform: some / every active lane has entry j
+    float g[MAXDV], bv[MAXDV], qv[MAXDV];
+    const unsigned long long lanes = __builtin_amdgcn_ballot_w64(true);
+#pragma unroll
+    for (int j = 0; j < MAXDV; ++j) {
+        idx[j] = -1;  // past the stride (which differs between the lanes of a wave that spans both sectors)
+        if (j < stride) idx[j] = ve[j];
+        const unsigned long long have = __builtin_amdgcn_ballot_w64(idx[j] >= 0);
+        any[j] = have != 0;
+        all[j] = have == lanes;
+    }
+#pragma unroll
+    for (int j = 0; j < MAXDV; ++j)
+        if (any[j]) {
+            const bool real = idx[j] >= 0;
+            // a padded lane reads slot 0, which its owner may be rewriting in this pass: the value is dropped
+            // by the selects below, and any address inside the array serves
+            const float x = msg[real ? idx[j] : 0];
+            g[j] = real ? x : 1.0f;
+            bv[j] = real ? 1.0f - x : 1.0f;
+        }
+    if (last) {
+        float P0 = omp, P1 = pp;
+#pragma unroll
+        for (int k = 0; k < MAXDV; ++k)
+            if (any[k]) { P0 = P0 * bv[k]; P1 = P1 * g[k]; }
+        const float qq = P1 / (P0 + P1);
+#pragma unroll
+        for (int j = 0; j < MAXDV; ++j) qv[j] = qq;
+    } else {
+        float pre0 = omp, pre1 = pp;
+#pragma unroll
+        for (int j = 0; j < MAXDV; ++j)
+            if (any[j]) {
+                float t0 = pre0, t1 = pre1;
+#pragma unroll
+                for (int k = j + 1; k < MAXDV; ++k)
+                    if (any[k]) { t0 = t0 * bv[k]; t1 = t1 * g[k]; }
+                qv[j] = t1 / (t0 + t1);
+                pre0 = pre0 * bv[j];
+                pre1 = pre1 * g[j];
+            }
+    }
+    bool hd = false;
+#pragma unroll
+    for (int j = 0; j < MAXDV; ++j)
+        if (all[j]) {
+            msg[idx[j]] = qv[j];
+            hd |= qv[j] >= 0.5f;
+        } else if (any[j]) {
+            if (idx[j] >= 0) {
+                msg[idx[j]] = qv[j];
+                hd |= qv[j] >= 0.5f;
+            }
+        }
+    return hd;
+}
+
+struct GeneralArgs {
+    SparseArgs s;            // dc = D, dvX / dvZ = the column strides
+    const uint8_t* chkDeg;   // mX + mZ degree bytes
+};
+
+template <int STOP, int MAXDC, int MAXDV, bool LDS>
+__global__ __launch_bounds__(kSparseThreads) void bp_general_kernel(const GeneralArgs ga)
+{
+    const SparseArgs& a = ga.s;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, D = a.dc;
+    const int EX = mX * D, E = m * D;
+    uint8_t* ws = LDS ? sp_lds : a.scratch + (long long)blockIdx.x * a.ws_bytes;
+    float* msg = reinterpret_cast<float*>(ws);            // E floats
+    uint8_t* syn = ws + (size_t)E * sizeof(float);        // m bytes: sX then sZ
+    uint8_t* hd = syn + m;                                // 2n bytes: X then Z hard decisions
+
+    const float pp = 2.0f / 3.0f * a.errorProbability;
+    const float omp = 1.0f - pp;
+    const int N = a.maxIter < 0 ? 0 : a.maxIter;
+
+    for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
+        // the syndrome entry as 0, 1 or 2 = any other value (truthy in the check update, never equal to a
+        // parity in the syndrome tests) with the check's degree above it
+        for (int c = tid; c < m; c += nt) {
+            const uint32_t s = c < mX ? a.sX[b * mX + c] : a.sZ[b * mZ + (c - mX)];
+            const int deg = ga.chkDeg[c];
+            syn[c] = (uint8_t)((s > 1u ? 2u : s) | ((uint32_t)deg << 2));
+        }
+        // one edge per thread, as the regular kernel's initialisation: the sentinel of the check table tells a
+        // real slot from an unused one (coalesced words that every workgroup reads, so they stay in cache)
+        for (int e = tid; e < E; e += nt) msg[e] = a.chkVar[e] >= 0 ? pp : 0.0f;
+        __syncthreads();
+
+        bool actX = true, actZ = true;  // workgroup-uniform
+        int itX = 0, itZ = 0;
+        for (int it = 0; it < N && (actX || actZ); ++it) {
+            const bool last = it == N - 1;
+            itX += actX;
+            itZ += actZ;
+            for (int c = tid; c < m; c += nt) {
+                if (c < mX ? !actX : !actZ) continue;
+                const uint32_t sd = syn[c];
+                sp_check_general<MAXDC>(msg + (size_t)c * D, D, (int)(sd >> 2), (sd & 3u) ? 0.5f : -0.5f);
+            }
+            __syncthreads();
+            for (int v = tid; v < 2 * n; v += nt) {
+                const bool z = v >= n;
+                if (z ? !actZ : !actX) continue;
+                const int dv = z ? a.dvZ : a.dvX;
+                const int32_t* ve = a.varEdge + (z ? (size_t)n * a.dvX + (size_t)(v - n) * dv : (size_t)v * dv);
+                const bool h = sp_var_general<MAXDV>(msg, ve, dv, pp, omp, last);
+                if (STOP == QEC_STOP_SYNDROME) hd[v] = h;
+            }
+            __syncthreads();
+            if (STOP == QEC_STOP_REF && it % 10 == 0) {
+                bool bx = false, bz = false;
+                for (int e = tid; e < E; e += nt) {
+                    const bool in = sp_inside(msg[e]);
+                    if (e < EX) bx |= in; else bz |= in;
+                }
+                const bool anyx = __syncthreads_or(bx), anyz = __syncthreads_or(bz);
+                if (actX && !anyx) actX = false;
+                if (actZ && !anyz) actZ = false;
+            } else if (STOP == QEC_STOP_SYNDROME) {
+                bool bx = false, bz = false;
+                for (int c = tid; c < m; c += nt) {
+                    const bool z = c >= mX;
+                    const uint8_t* h = hd + (z ? n : 0);
+                    uint32_t x = 0;
+                    for (int k = 0; k < D; ++k) {  // no early exit: the D loads stay independent
+                        const int v = a.chkVar[(size_t)c * D + k];
+                        x ^= v >= 0 ? (uint32_t)h[v < 0 ? 0 : v] : 0u;
+                    }
+                    if (x != (syn[c] & 3u)) { if (z) bz = true; else bx = true; }
+                }
+                const bool badx = __syncthreads_or(bx), badz = __syncthreads_or(bz);
+                if (actX && !badx) actX = false;
+                if (actZ && !badz) actZ = false;
+            }
+        }
+
+        // ---- post-processing of Decode ----
+        bool bx = false, bz = false;
+        for (int e = tid; e < E; e += nt) {
+            const bool in = sp_inside(msg[e]);
+            if (e < EX) bx |= in; else bz |= in;
+        }
+        for (int v = tid; v < 2 * n; v += nt) {
+            const bool z = v >= n;
+            const int dv = z ? a.dvZ : a.dvX;
+            const int32_t* ve = a.varEdge + (z ? (size_t)n * a.dvX + (size_t)(v - n) * dv : (size_t)v * dv);
+            bool h = false;
+            for (int j = 0; j < dv; ++j) {
+                const int ed = ve[j];
+                h |= ed >= 0 && msg[ed < 0 ? 0 : ed] >= 0.5f;
+            }
+            hd[v] = h;
+            if (z) a.eZ[b * n + (v - n)] = h; else a.eX[b * n + v] = h;
+        }
+        const bool convFailX = __syncthreads_or(bx), convFailZ = __syncthreads_or(bz);
+        bool sx = false, sz = false;
+        for (int c = tid; c < m; c += nt) {
+            const bool z = c >= mX;
+            const uint8_t* h = hd + (z ? n : 0);
+            uint32_t x = 0;
+            for (int k = 0; k < D; ++k) {
+                const int v = a.chkVar[(size_t)c * D + k];
+                x ^= v >= 0 ? (uint32_t)h[v < 0 ? 0 : v] : 0u;
+            }
+            if (x != (syn[c] & 3u)) { if (z) sz = true; else sx = true; }
+        }
+        const bool synFailX = __syncthreads_or(sx), synFailZ = __syncthreads_or(sz);
+        if (a.q != nullptr)
+            for (int e = tid; e < E; e += nt) a.q[b * E + e] = msg[e];
+        if (tid == 0) {
+            uint32_t f = 0;
+            if (synFailX) f |= QEC_SYNDROME_FAIL_X;
+            if (synFailZ) f |= QEC_SYNDROME_FAIL_Z;
+            if (convFailX) f |= QEC_CONVERGENCE_FAIL_X;
+            if (convFailZ) f |= QEC_CONVERGENCE_FAIL_Z;
+            a.flags[b] = (uint8_t)f;
+            if (a.iters != nullptr) { a.iters[2 * b] = itX; a.iters[2 * b + 1] = itZ; }
+        }
+        __syncthreads();  // the workspace is reused by the next syndrome pair
+    }
+}
+
 // ---- plan ------------------------------------------------------------------
 using SparseFn = void (*)(const SparseArgs);
+using GeneralFn = void (*)(const GeneralArgs);
+
+template <int MAXDC, int MAXDV, bool LDS>
+static void general_fns(GeneralFn (&f)[3])
+{
+    f[QEC_STOP_REF] = bp_general_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS>;
+    f[QEC_STOP_FIXED] = bp_general_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS>;
+    f[QEC_STOP_SYNDROME] = bp_general_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS>;
+}
 
 template <int MAXDC, int MAXDV, bool LDS>
 static void sparse_fns(SparseFn (&f)[3])
@@ -255,6 +501,11 @@ struct SparsePlan {
     long long ws_bytes = 0;
     int grid = 0;
     SparseFn fn[3] = {nullptr, nullptr, nullptr};
+    // a general code: bp_general_kernel, its degree bytes and its fitted workgroup size
+    bool general = false;
+    GeneralFn gfn[3] = {nullptr, nullptr, nullptr};
+    DeviceArray<uint8_t> chkDeg;
+    int threads = kSparseThreads;
     DeviceArray<int32_t> chkVar, varEdge;
     DeviceArray<uint8_t> scratch;
     std::string name;
@@ -282,6 +533,23 @@ static bool index_sector(const std::vector<uint8_t>& pcm, int m, int n, int dc, 
     return true;
 }
 
+// The padded tables of one sector of a general code (edge id = c D + slot, sector-global through edge0).
+static void index_sector_general(const std::vector<uint8_t>& pcm, int m, int n, int D, int dv, int edge0, int32_t* chkVar,
+                                 uint8_t* chkDeg, int32_t* varEdge)
+{
+    std::vector<int> cnt(n, 0);
+    for (int c = 0; c < m; ++c) {
+        int k = 0;
+        for (int v = 0; v < n; ++v) {
+            if (!pcm[(size_t)c * n + v]) continue;
+            chkVar[(size_t)c * D + k] = v;
+            varEdge[(size_t)v * dv + cnt[v]++] = edge0 + c * D + k;
+            ++k;
+        }
+        chkDeg[c] = (uint8_t)k;
+    }
+}
+
 void sparse_plan_free(void* plan) { delete static_cast<SparsePlan*>(plan); }
 
 const char* sparse_plan_name(const void* plan) { return static_cast<const SparsePlan*>(plan)->name.c_str(); }
@@ -290,28 +558,48 @@ const char* sparse_plan_name(const void* plan) { return static_cast<const Sparse
 // what the reference decodes or what this engine instantiates.
 void* sparse_plan_create(const Code& c, int device)
 {
-    const int dc = c.L, dvX = c.J, dvZ = c.K, n = c.n, mX = c.mX, mZ = c.mZ;
+    const bool general = c.general;
+    const int dc = c.stride(), dvX = c.col_stride(0), dvZ = c.col_stride(1), n = c.n, mX = c.mX, mZ = c.mZ;
     if (dc > 32 || dvX > 16 || dvZ > 16) {
-        fail(QEC_ERR_UNSUPPORTED, "sparse engine: needs L <= 32 and J, K <= 16");
+        fail(QEC_ERR_UNSUPPORTED, general ? "sparse engine: needs row weights <= 32 and column weights <= 16"
+                                          : "sparse engine: needs L <= 32 and J, K <= 16");
         return nullptr;
     }
     const long long m = (long long)mX + mZ, E = m * dc;
-    std::vector<int32_t> chk((size_t)E), ve((size_t)n * (dvX + dvZ));
+    if (general && (E >= (1LL << 31) || 2LL * n >= (1LL << 31))) {
+        fail(QEC_ERR_UNSUPPORTED, "sparse engine: code too large");
+        return nullptr;
+    }
+    std::vector<int32_t> chk((size_t)E, -1), ve((size_t)n * (dvX + dvZ), -1);
+    std::vector<uint8_t> cdeg((size_t)m, 0);
     std::string why;
-    if (!index_sector(c.pcmX, mX, n, dc, dvX, 0, chk.data(), ve.data(), why) ||
+    if (general) {
+        index_sector_general(c.pcmX, mX, n, dc, dvX, 0, chk.data(), cdeg.data(), ve.data());
+        index_sector_general(c.pcmZ, mZ, n, dc, dvZ, mX * dc, chk.data() + (size_t)mX * dc, cdeg.data() + mX,
+                             ve.data() + (size_t)n * dvX);
+    } else if (!index_sector(c.pcmX, mX, n, dc, dvX, 0, chk.data(), ve.data(), why) ||
         !index_sector(c.pcmZ, mZ, n, dc, dvZ, mX * dc, chk.data() + (size_t)mX * dc, ve.data() + (size_t)n * dvX,
                       why)) {
         fail(QEC_ERR_UNSUPPORTED, "sparse engine: " + why + " (DecoderCPU assumes row weight L and column weight J/K)");
         return nullptr;
     }
     auto* p = new SparsePlan;
+    p->general = general;
     p->n = n; p->mX = mX; p->mZ = mZ; p->dc = dc; p->dvX = dvX; p->dvZ = dvZ;
     p->ws_bytes = (E * 4 + m + 2LL * n + 15) / 16 * 16;
     p->lds = p->ws_bytes <= 160 * 1024 - 64;
     const int wdc = dc <= 8 ? 8 : dc <= 16 ? 16 : 32;
     const int wdv = std::max(dvX, dvZ) <= 4 ? 4 : std::max(dvX, dvZ) <= 8 ? 8 : 16;
     // instantiated shapes: (8,4) (16,8) (32,16); pick the smallest that covers the code
-    if (wdc <= 8 && wdv <= 4) { if (p->lds) sparse_fns<8, 4, true>(p->fn); else sparse_fns<8, 4, false>(p->fn); }
+    if (general) {
+        if (wdc <= 8 && wdv <= 4) { if (p->lds) general_fns<8, 4, true>(p->gfn); else general_fns<8, 4, false>(p->gfn); }
+        else if (wdc <= 16 && wdv <= 8) { if (p->lds) general_fns<16, 8, true>(p->gfn); else general_fns<16, 8, false>(p->gfn); }
+        else { if (p->lds) general_fns<32, 16, true>(p->gfn); else general_fns<32, 16, false>(p->gfn); }
+        // the smallest workgroup that gives the wider pass a thread per node
+        const long long wide = std::max<long long>(m, 2LL * n);
+        p->threads = wide <= 64 ? 64 : wide <= 128 ? 128 : kSparseThreads;
+    }
+    else if (wdc <= 8 && wdv <= 4) { if (p->lds) sparse_fns<8, 4, true>(p->fn); else sparse_fns<8, 4, false>(p->fn); }
     else if (wdc <= 16 && wdv <= 8) { if (p->lds) sparse_fns<16, 8, true>(p->fn); else sparse_fns<16, 8, false>(p->fn); }
     else { if (p->lds) sparse_fns<32, 16, true>(p->fn); else sparse_fns<32, 16, false>(p->fn); }
     try {
@@ -320,11 +608,26 @@ void* sparse_plan_create(const Code& c, int device)
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
         int per_cu = 1;
         if (p->lds) {
-            for (SparseFn f : p->fn)
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize,
+            const void* fns[3];
+            for (int k = 0; k < 3; ++k)
+                fns[k] = general ? reinterpret_cast<const void*>(p->gfn[k]) : reinterpret_cast<const void*>(p->fn[k]);
+            for (const void* f : fns)
+                if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)p->ws_bytes) != hipSuccess)
                     throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
             per_cu = std::max(1, std::min(8, (int)((160 * 1024) / p->ws_bytes)));
+            // a general code: the same 32 waves per CU at most, in its fitted workgroups
+            if (general) {
+                per_cu = std::max(1, std::min(8 * (kSparseThreads / p->threads), (int)((160 * 1024) / p->ws_bytes)));
+                // and no more workgroups than the runtime says are resident at once: one beyond that runs its
+                // share of the batch alone behind the others
+                for (const void* f : fns) {
+                    int resident = 0;
+                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, f, p->threads, (size_t)p->ws_bytes) ==
+                            hipSuccess && resident > 0)
+                        per_cu = std::min(per_cu, resident);
+                }
+            }
         } else {
             per_cu = 4;
         }
@@ -333,6 +636,10 @@ void* sparse_plan_create(const Code& c, int device)
         p->varEdge.reserve(ve.size());
         hip_throw(hipMemcpy(p->chkVar.data(), chk.data(), chk.size() * 4, hipMemcpyHostToDevice), "chkVar upload");
         hip_throw(hipMemcpy(p->varEdge.data(), ve.data(), ve.size() * 4, hipMemcpyHostToDevice), "varEdge upload");
+        if (general) {
+            p->chkDeg.reserve(cdeg.size());
+            hip_throw(hipMemcpy(p->chkDeg.data(), cdeg.data(), cdeg.size(), hipMemcpyHostToDevice), "chkDeg upload");
+        }
         if (!p->lds) p->scratch.reserve((size_t)p->grid * p->ws_bytes);
     } catch (const std::exception& ex) {
         delete p;
@@ -340,8 +647,12 @@ void* sparse_plan_create(const Code& c, int device)
         return nullptr;
     }
     char buf[192];
-    snprintf(buf, sizeof buf, "sparse-graph %s n=%d mX=%d mZ=%d dc=%d dv=%d/%d (%s)", p->lds ? "lds" : "hbm", n, mX, mZ,
-             dc, dvX, dvZ, c.describe().c_str());
+    if (general)
+        snprintf(buf, sizeof buf, "sparse-general %s threads=%d n=%d mX=%d mZ=%d D=%d dv=%d/%d grid=%d (%s)",
+                 p->lds ? "lds" : "hbm", p->threads, n, mX, mZ, dc, dvX, dvZ, p->grid, c.describe().c_str());
+    else
+        snprintf(buf, sizeof buf, "sparse-graph %s n=%d mX=%d mZ=%d dc=%d dv=%d/%d (%s)", p->lds ? "lds" : "hbm", n, mX, mZ,
+                 dc, dvX, dvZ, c.describe().c_str());
     p->name = buf;
     return p;
 }
@@ -366,7 +677,12 @@ int launch_decode_sparse(void* plan, const uint8_t* sX, const uint8_t* sZ, long 
     a.errorProbability = errorProbability;
     a.maxIter = maxIter;
     const unsigned grid = (unsigned)std::min<long long>(B, p->grid);
-    hipLaunchKernelGGL(p->fn[stop], dim3(grid), dim3(kSparseThreads), p->lds ? (size_t)p->ws_bytes : 0, stream, a);
+    if (p->general) {
+        GeneralArgs ga{a, p->chkDeg.data()};
+        hipLaunchKernelGGL(p->gfn[stop], dim3(grid), dim3(p->threads), p->lds ? (size_t)p->ws_bytes : 0, stream, ga);
+    } else {
+        hipLaunchKernelGGL(p->fn[stop], dim3(grid), dim3(kSparseThreads), p->lds ? (size_t)p->ws_bytes : 0, stream, a);
+    }
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(QEC_ERR_HIP, std::string("bp_sparse launch: ") + hipGetErrorString(err));
     return QEC_OK;

@@ -312,6 +312,27 @@ qec_code* qec_code_generate(int J, int K, int L, int P, int sigma, int tau)
     return h;
 }
 
+qec_code* qec_code_from_matrices(int n, int mX, const uint8_t* HX, int mZ, const uint8_t* HZ)
+{
+    auto* h = new (std::nothrow) qec_code;
+    if (!h) { fail(QEC_ERR_NOMEM, "qec_code_from_matrices: out of memory"); return nullptr; }
+    try {
+        if (general_code(n, mX, HX, mZ, HZ, nullptr, h->c) != QEC_OK) { delete h; return nullptr; }
+    } catch (const std::bad_alloc&) {
+        delete h;
+        fail(QEC_ERR_NOMEM, "qec_code_from_matrices: out of memory");
+        return nullptr;
+    }
+    return h;
+}
+
+int qec_code_degrees(const qec_code* h, int* out)
+{
+    if (!h || !out) return fail(QEC_ERR_ARG, "qec_code_degrees: null argument");
+    code_degrees(h->c, out);
+    return QEC_OK;
+}
+
 int qec_code_free(qec_code* code)
 {
     delete code;
@@ -439,7 +460,7 @@ qec_decoder* qec_decoder_create_engine(const qec_code* h, int device, size_t max
         return d.release();
     }
     std::string name;
-    const void* v = engine == QEC_ENGINE_SPARSE ? nullptr : select_variant(h->c, name);
+    const void* v = engine == QEC_ENGINE_SPARSE || h->c.general ? nullptr : select_variant(h->c, name);
     if (!v && engine == QEC_ENGINE_CIRCULANT) {
         fail(QEC_ERR_UNSUPPORTED, "no wave-circulant kernel for this code shape (" + h->c.describe() +
                                       "): needs circulant-permutation blocks, P <= 64 and an instantiated (J,K,L)");
@@ -851,7 +872,7 @@ int single_device_only(const qec_decoder* d, const char* what)
 // (mX + mZ) L floats per sample (24 KB for P61), so the q buffer stays within 256 MiB.
 size_t osd_chunk(const Code& c)
 {
-    const size_t per = (size_t)(c.mX + c.mZ) * c.L * sizeof(float);
+    const size_t per = (size_t)(c.mX + c.mZ) * c.stride() * sizeof(float);
     return std::max<size_t>(256, std::min<size_t>(65536, ((size_t)256 << 20) / std::max<size_t>(per, 1)));
 }
 
@@ -862,7 +883,7 @@ int osd_reserve(qec_decoder* d, size_t cnt)
         d->osX.reserve(cnt * c.mX); d->osZ.reserve(cnt * c.mZ);
         d->oeX.reserve(cnt * c.n); d->oeZ.reserve(cnt * c.n);
         d->ofl.reserve(cnt); d->ofl0.reserve(cnt); d->ofs.reserve(cnt);
-        d->oq.reserve(cnt * (size_t)(c.mX + c.mZ) * c.L);
+        d->oq.reserve(cnt * (size_t)(c.mX + c.mZ) * c.stride());
     } catch (const std::exception& ex) {
         return fail(QEC_ERR_NOMEM, std::string("OSD workspace: ") + ex.what());
     }
@@ -892,7 +913,7 @@ int osd_repair_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t
 {
     const Code& c = *d->code;
     const int n = c.n, nb = (n + 7) / 8;
-    const size_t recB = 2 * (size_t)nb + 1, qn = (size_t)(c.mX + c.mZ) * c.L;
+    const size_t recB = 2 * (size_t)nb + 1, qn = (size_t)(c.mX + c.mZ) * c.stride();
     if (!d->cpu && !d->odev) return fail(QEC_ERR_UNSUPPORTED, d->osd_why);
     d->last_path |= QEC_PATH_OSD;
     std::vector<size_t> failed;
@@ -1040,7 +1061,7 @@ int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
     }
     QEC_DEVICE_SCOPE(d->device);
     const Code& c = *d->code;
-    const size_t qn = (size_t)(c.mX + c.mZ) * c.L;
+    const size_t qn = (size_t)(c.mX + c.mZ) * c.stride();
     const size_t recB = 2 * (size_t)((c.n + 7) / 8) + 1;
     hipStream_t st = d->stream;
     try {
@@ -1081,7 +1102,7 @@ int decode_host_parts(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size
     if (parts.size() == 1)
         return decode_host(parts[0], sX, sZ, B, p, maxIter, stop, eX, eZ, flags, rec, iters, q);
     const Code& c = *d->code;
-    const size_t qn = (size_t)(c.mX + c.mZ) * c.L;
+    const size_t qn = (size_t)(c.mX + c.mZ) * c.stride();
     const size_t recB = 2 * (size_t)((c.n + 7) / 8) + 1;
     const int np = (int)parts.size();
     std::vector<int> rcs(np, QEC_OK);
@@ -1708,7 +1729,7 @@ int qec_osd(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, cons
     if (!w->odev) return fail(QEC_ERR_UNSUPPORTED, w->osd_why);
     QEC_DEVICE_SCOPE(w->device);
     const Code& c = *w->code;
-    const size_t qn = (size_t)(c.mX + c.mZ) * c.L;
+    const size_t qn = (size_t)(c.mX + c.mZ) * c.stride();
     hipStream_t st = w->stream;
     std::vector<uint8_t> f0(flags, flags + B);
     uint32_t swept = 0;

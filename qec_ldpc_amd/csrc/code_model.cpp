@@ -54,6 +54,10 @@ const char* last_error_cstr() { return g_last_error.c_str(); }
 std::string Code::describe() const
 {
     std::ostringstream s;
+    if (general) {
+        s << "[[n=" << n << ",k=" << k << "]]";
+        return s.str();
+    }
     s << "[J=" << J << ",K=" << K << ",L=" << L << ",P=" << P << ",s=" << sigma << ",t=" << tau
       << "][[n=" << n << ",k=" << (mZ - mX) << "]]";
     return s.str();
@@ -85,10 +89,12 @@ static bool extract_shifts(const std::vector<uint8_t>& pcm, int R, int L, int P,
 
 void finalize_code(Code& c)
 {
-    c.n = c.L * c.P;
-    c.mX = c.J * c.P;
-    c.mZ = c.K * c.P;
-    c.is_qc = extract_shifts(c.pcmX, c.J, c.L, c.P, c.EX) && extract_shifts(c.pcmZ, c.K, c.L, c.P, c.EZ);
+    if (!c.general) {
+        c.n = c.L * c.P;
+        c.mX = c.J * c.P;
+        c.mZ = c.K * c.P;
+        c.is_qc = extract_shifts(c.pcmX, c.J, c.L, c.P, c.EX) && extract_shifts(c.pcmZ, c.K, c.L, c.P, c.EZ);
+    }
     if (!c.is_qc) { c.EX.clear(); c.EZ.clear(); }
     c.imp_rows.clear();
     c.imp_words = 0;
@@ -131,6 +137,27 @@ int load_code(const char* path, Code& c)
     std::getline(ifs, hd);
     std::getline(ifs, imp);
     std::istringstream ps(params);
+    if (params.compare(0, 3, "css") == 0 && (params.size() == 3 || params[3] == ' ' || params[3] == '\t')) {
+        // "css n mX mZ": a general code, the matrices in the same syntax
+        ps.ignore(3);
+        long n = 0, mX = 0, mZ = 0;
+        if (!(ps >> n >> mX >> mZ))
+            return fail(QEC_ERR_FORMAT, std::string("code file has no 'css n mX mZ' header: ") + path);
+        if (n <= 0 || mX <= 0 || mZ <= 0 || n > (1 << 20) || mX > (1 << 20) || mZ > (1 << 20))
+            return fail(QEC_ERR_FORMAT, "code file header out of range");
+        // the dense matrices are allocated from the header: bound them as the six-number form bounds L P
+        const long kMaxEntries = 1L << 28;
+        if (mX * n > kMaxEntries || mZ * n > kMaxEntries)
+            return fail(QEC_ERR_FORMAT, "code file header out of range (a matrix of more than 2^28 entries)");
+        const bool has_imp = !imp.empty() && imp.find_first_not_of(" \t\r") != std::string::npos;
+        if (has_imp && 4 * n * n > kMaxEntries)
+            return fail(QEC_ERR_FORMAT, "code file: an I-P line of more than 2^28 entries (qec_code_with_logical derives the check)");
+        std::vector<uint8_t> HX, HZ, IMP;
+        parse_matrix(hc, HX, (size_t)mX * n);
+        parse_matrix(hd, HZ, (size_t)mZ * n);
+        if (has_imp) parse_matrix(imp, IMP, 4 * (size_t)n * n);
+        return general_code((int)n, (int)mX, HX.data(), (int)mZ, HZ.data(), IMP.empty() ? nullptr : IMP.data(), c);
+    }
     if (!(ps >> c.J >> c.K >> c.L >> c.P >> c.sigma >> c.tau))
         return fail(QEC_ERR_FORMAT, std::string("code file has no 'J K L P sigma tau' header: ") + path);
     if (c.J <= 0 || c.K <= 0 || c.L <= 0 || c.P <= 0 || (long)c.L * c.P > (1 << 20))
@@ -244,6 +271,63 @@ std::vector<std::vector<uint64_t>> kernel_basis(const std::vector<uint8_t>& H, i
 }
 }  // namespace
 
+void code_degrees(const Code& c, int out[5])
+{
+    for (int sec = 0; sec < 2; ++sec) {
+        const std::vector<uint8_t>& H = sec ? c.pcmZ : c.pcmX;
+        const int m = sec ? c.mZ : c.mX, n = c.n;
+        std::vector<int> col(n, 0);
+        int rw = 0;
+        for (int r = 0; r < m; ++r) {
+            int w = 0;
+            for (int v = 0; v < n; ++v)
+                if (H[(size_t)r * n + v]) { ++w; ++col[v]; }
+            rw = std::max(rw, w);
+        }
+        out[sec] = rw;
+        out[2 + sec] = n ? *std::max_element(col.begin(), col.end()) : 0;
+    }
+    out[4] = std::max(out[0], out[1]);
+}
+
+int general_code(int n, int mX, const uint8_t* HX, int mZ, const uint8_t* HZ, const uint8_t* imp, Code& c)
+{
+    if (n <= 0 || mX <= 0 || mZ <= 0)
+        return fail(QEC_ERR_ARG, "qec_code_from_matrices: n, mX and mZ must be > 0");
+    if (!HX || !HZ) return fail(QEC_ERR_ARG, "qec_code_from_matrices: null matrix");
+    for (int sec = 0; sec < 2; ++sec) {
+        const uint8_t* H = sec ? HZ : HX;
+        const int m = sec ? mZ : mX;
+        const char* name = sec ? "HZ" : "HX";
+        for (int r = 0; r < m; ++r) {
+            bool any = false;
+            for (int v = 0; v < n; ++v) {
+                const uint8_t x = H[(size_t)r * n + v];
+                if (x > 1)
+                    return fail(QEC_ERR_ARG, std::string("qec_code_from_matrices: ") + name + "[" + std::to_string(r) + "][" +
+                                                 std::to_string(v) + "] = " + std::to_string((int)x) + " is not 0 or 1");
+                any |= x != 0;
+            }
+            if (!any)
+                return fail(QEC_ERR_ARG, std::string("qec_code_from_matrices: row ") + std::to_string(r) + " of " + name +
+                                             " is all zero (a check on no qubit)");
+        }
+    }
+    c = Code();
+    c.general = true;
+    c.n = n; c.mX = mX; c.mZ = mZ;
+    c.pcmX.assign(HX, HX + (size_t)mX * n);
+    c.pcmZ.assign(HZ, HZ + (size_t)mZ * n);
+    if (imp) c.imp.assign(imp, imp + 4 * (size_t)n * n);
+    int deg[5];
+    code_degrees(c, deg);
+    c.dvX = deg[2]; c.dvZ = deg[3]; c.D = deg[4];
+    // k = n - rank HX - rank HZ: a kernel basis has n - rank rows
+    c.k = (int)kernel_basis(c.pcmX, mX, n).size() + (int)kernel_basis(c.pcmZ, mZ, n).size() - n;
+    finalize_code(c);
+    return QEC_OK;
+}
+
 int derive_logical(const Code& src, int mode, Code& out)
 {
     if (mode != QEC_LOGICAL_REFERENCE && mode != QEC_LOGICAL_DEGENERATE)
@@ -295,7 +379,8 @@ void host_syndrome(const Code& c, int sector, const uint8_t* e, uint8_t* s)
             }
     } else {
         const std::vector<uint8_t>& H = sector ? c.pcmZ : c.pcmX;
-        for (int eq = 0; eq < R * P; ++eq) {
+        const int m = sector ? c.mZ : c.mX;  // R P for a file code
+        for (int eq = 0; eq < m; ++eq) {
             int x = 0;
             for (int v = 0; v < n; ++v) x += H[(size_t)eq * n + v] * (e[v] & 1);
             s[eq] = (uint8_t)(x % 2);

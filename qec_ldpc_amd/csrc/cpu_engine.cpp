@@ -29,10 +29,14 @@ struct CpuSector {
     int m = 0, dc = 0, dv = 0;
     std::vector<int32_t> chk_var;   // [m][dc] variables of each check, ascending
     std::vector<int32_t> var_edge;  // [n][dv] edges of each variable, ascending check
+    // a general code: dc = the slot stride D and dv = the sector's largest column
+    // weight, both tables padded with -1, and each node's own degree
+    std::vector<uint8_t> chk_deg, var_deg;
 };
 
 struct CpuPlan {
     int n = 0;
+    bool general = false;
     CpuSector sec[2];
 };
 
@@ -62,6 +66,25 @@ bool build_sector(const std::vector<uint8_t>& pcm, int m, int n, CpuSector& s, s
     for (int v = 0; v < n; ++v)
         if (fill[v] != dv) { why = "irregular column weights"; return false; }
     return true;
+}
+
+// The tables of a general code's sector: any row and column weights, slot stride D.
+void build_sector_general(const std::vector<uint8_t>& pcm, int m, int n, int D, int dv, CpuSector& s)
+{
+    s.m = m;
+    s.dc = D;
+    s.dv = dv;
+    s.chk_var.assign((size_t)m * D, -1);
+    s.var_edge.assign((size_t)n * dv, -1);
+    s.chk_deg.assign(m, 0);
+    s.var_deg.assign(n, 0);
+    for (int c = 0; c < m; ++c)
+        for (int v = 0; v < n; ++v) {
+            if (!pcm[(size_t)c * n + v]) continue;
+            const int k = s.chk_deg[c]++;
+            s.chk_var[(size_t)c * D + k] = v;
+            s.var_edge[(size_t)v * dv + s.var_deg[v]++] = c * D + k;  // checks visited in ascending order
+        }
 }
 
 inline bool outside(float x) { return !(x > 0.01f && x < 0.99f); }  // CheckConvergence, DecoderCPU.h:231-246
@@ -186,12 +209,103 @@ int decode_sector(const CpuSector& S, int n, const uint8_t* syn, float errorProb
     return it;
 }
 
+// decode_sector for a general code: the same rules with each node's own degree, over real edges only
+// (DESIGN.md section 2).  Unused slots of q stay +0.0f.  No near-hard jump.
+int decode_sector_general(const CpuSector& S, int n, const uint8_t* syn, float errorProbability, int N, int stop, Work& w,
+                          bool& conv_out, bool& syn_ok, float* q_out)
+{
+    const int m = S.m, D = S.dc, dvs = S.dv;
+    const size_t E = (size_t)m * D;
+    float* q = w.q.data();
+    float* r = w.r.data();
+    uint8_t* e = w.e.data();
+    const float pp = (2.0f / 3.0f) * errorProbability;
+    const float one_minus_pp = 1.0f - pp;
+    for (int c = 0; c < m; ++c)
+        for (int k = 0; k < D; ++k) q[(size_t)c * D + k] = k < S.chk_deg[c] ? pp : 0.0f;
+    auto hard_decision = [&]() {
+        for (int v = 0; v < n; ++v) {
+            bool hd = false;  // a variable in no check decides 0
+            for (int j = 0; j < S.var_deg[v]; ++j) hd |= q[S.var_edge[(size_t)v * dvs + j]] >= 0.5f;
+            e[v] = hd;
+        }
+    };
+    auto syndrome_ok = [&]() {
+        for (int c = 0; c < m; ++c) {
+            uint32_t x = 0;
+            for (int k = 0; k < S.chk_deg[c]; ++k) x ^= e[S.chk_var[(size_t)c * D + k]];
+            if ((x & 1u) != syn[c]) return false;
+        }
+        return true;
+    };
+    auto all_outside = [&]() {
+        for (int c = 0; c < m; ++c)
+            for (int k = 0; k < S.chk_deg[c]; ++k)
+                if (!outside(q[(size_t)c * D + k])) return false;
+        return true;
+    };
+    bool conv = false;
+    int it = 0;
+    for (int iter = 0; iter < N; ++iter) {
+        if (stop == QEC_STOP_REF && conv) break;
+        ++it;
+        for (int c = 0; c < m; ++c) {
+            const float* qc = q + (size_t)c * D;
+            float* rc = r + (size_t)c * D;
+            const int dc = S.chk_deg[c];
+            const bool s = syn[c] != 0;
+            for (int i = 0; i < dc; ++i) {
+                float t = 1.0f;
+                for (int k = 0; k < dc; ++k)
+                    if (k != i) t = t * (1.0f - 2.0f * qc[k]);
+                rc[i] = s ? 0.5f * (1.0f + t) : 0.5f * (1.0f - t);
+            }
+        }
+        const bool last = iter == N - 1;
+        for (int v = 0; v < n; ++v) {
+            const int32_t* ve = S.var_edge.data() + (size_t)v * dvs;
+            const int dv = S.var_deg[v];
+            for (int j = 0; j < dv; ++j) {
+                float P0 = one_minus_pp, P1 = pp;
+                for (int k = 0; k < dv; ++k) {
+                    if (k == j && !last) continue;
+                    const float rk = r[ve[k]];
+                    P0 = P0 * (1.0f - rk);
+                    P1 = P1 * rk;
+                }
+                q[ve[j]] = P1 / (P0 + P1);
+            }
+        }
+        if (stop == QEC_STOP_REF && iter % 10 == 0) conv = all_outside();
+        if (stop == QEC_STOP_SYNDROME) {
+            hard_decision();
+            if (syndrome_ok()) break;
+        }
+    }
+    hard_decision();
+    conv_out = all_outside();
+    syn_ok = syndrome_ok();
+    if (q_out) std::memcpy(q_out, q, E * sizeof(float));
+    return it;
+}
+
 }  // namespace
 
 void* cpu_plan_create(const Code& c)
 {
     auto* p = new CpuPlan;
     p->n = c.n;
+    if (c.general) {
+        if (c.D > 255 || c.dvX > 255 || c.dvZ > 255) {
+            delete p;
+            fail(QEC_ERR_UNSUPPORTED, "CPU engine: row and column weights above 255");
+            return nullptr;
+        }
+        p->general = true;
+        build_sector_general(c.pcmX, c.mX, c.n, c.D, c.dvX, p->sec[0]);
+        build_sector_general(c.pcmZ, c.mZ, c.n, c.D, c.dvZ, p->sec[1]);
+        return p;
+    }
     std::string why;
     if (!build_sector(c.pcmX, c.mX, c.n, p->sec[0], why) || !build_sector(c.pcmZ, c.mZ, c.n, p->sec[1], why)) {
         delete p;
@@ -220,7 +334,7 @@ int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long
     const size_t qper = (size_t)mX * P.sec[0].dc + (size_t)mZ * P.sec[1].dc;
     // near-hard jump (QEC_OPT_NEAR_HARD_JUMP): per-sector compare values for this p', as the kernels' launch
     uint32_t nearT[2] = {0u, 0u};
-    if (near_hard && qf == nullptr && stop != QEC_STOP_SYNDROME)
+    if (near_hard && !P.general && qf == nullptr && stop != QEC_STOP_SYNDROME)
         for (int sec = 0; sec < 2; ++sec) nearT[sec] = near_hard_threshold((2.0f / 3.0f) * p, P.sec[sec].dv, P.sec[sec].dc).T;
     if (threads <= 0) threads = cpu_threads();
     threads = (int)std::max<long long>(1, std::min<long long>(threads, B));
@@ -236,8 +350,9 @@ int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long
                 const CpuSector& S = P.sec[sec];
                 bool conv = false, ok = false;
                 float* qo = qf ? qf + b * qper + (sec ? (size_t)mX * P.sec[0].dc : 0) : nullptr;
-                const int it = decode_sector(S, n, sec ? sZ + b * mZ : sX + b * mX, p, maxIter, stop, w, conv, ok, qo,
-                                             nearT[sec]);
+                const uint8_t* syn = sec ? sZ + b * mZ : sX + b * mX;
+                const int it = P.general ? decode_sector_general(S, n, syn, p, maxIter, stop, w, conv, ok, qo)
+                                         : decode_sector(S, n, syn, p, maxIter, stop, w, conv, ok, qo, nearT[sec]);
                 if (!ok) f |= sec ? QEC_SYNDROME_FAIL_Z : QEC_SYNDROME_FAIL_X;
                 if (!conv) f |= sec ? QEC_CONVERGENCE_FAIL_Z : QEC_CONVERGENCE_FAIL_X;
                 if (iters) iters[2 * b + sec] = it;

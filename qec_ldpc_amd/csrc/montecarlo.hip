@@ -162,7 +162,8 @@ struct McArgs {
     uint8_t* sX;                               // [B][mX]
     uint8_t* sZ;                               // [B][mZ]
     uint8_t* errp;                             // [B][2 nb] (nullable)
-    const int32_t* chkVar;                     // non-QC codes: [(mX + mZ) L] variables per check
+    const int32_t* chkVar;                     // non-QC codes: [(mX + mZ) L] variables per check (L = the slot
+                                               // stride; a general code pads short checks with -1)
     long long B;
     int n, nb, L, P, J, K, mX, mZ;
     int S;                                     // samples per wave
@@ -224,7 +225,11 @@ __global__ __launch_bounds__(64 * kMcWaves) void mc_errors_syndrome_kernel(const
             const uint8_t* e = stage + (size_t)sI * 2 * npad + (zs ? npad : 0);
             const int32_t* vars = a.chkVar + (size_t)c * a.L;
             uint32_t x = 0;
-            for (int k = 0; k < a.L; ++k) x ^= e[vars[k]];
+            for (int k = 0; k < a.L; ++k) {
+                const int v = vars[k];
+                if (v < 0) break;  // a general code's padding
+                x ^= e[v];
+            }
             const long long b = b0 + sI;
             if (zs) a.sZ[b * a.mZ + (c - a.mX)] = (uint8_t)(x & 1u); else a.sX[b * a.mX + c] = (uint8_t)(x & 1u);
         }
@@ -314,7 +319,8 @@ struct GapArgs {
     uint32_t* sXp;     // bit rows (nullable)
     uint32_t* sZp;
     uint8_t* errp;     // nullable
-    const int32_t* varEdge;  // non-QC codes: n x dvX then n x dvZ edge ids; check = edge / dc
+    const int32_t* varEdge;  // non-QC codes: n x dvX then n x dvZ edge ids; check = edge / dc (a general code
+                             // pads a variable in fewer checks with -1)
     int dc, dvX, dvZ;
     int EX[128], EZ[128];    // QC codes
 };
@@ -389,13 +395,17 @@ __global__ __launch_bounds__(64 * kGapWaves) void mc_gap_kernel(const GapArgs a)
             } else {
                 if (ex)
                     for (int k = 0; k < a.dvX; ++k) {
-                        const int c = a.varEdge[(size_t)v * a.dvX + k] / a.dc;
+                        const int ed = a.varEdge[(size_t)v * a.dvX + k];
+                        if (ed < 0) break;
+                        const int c = ed / a.dc;
                         atomicXor(&synX[c >> 5], 1u << (c & 31));
                     }
                 if (ez)
                     for (int k = 0; k < a.dvZ; ++k) {
                         // Z edge ids are offset by mX dc: check mX + c
-                        const int c = a.varEdge[(size_t)n * a.dvX + (size_t)v * a.dvZ + k] / a.dc - a.mX;
+                        const int ed = a.varEdge[(size_t)n * a.dvX + (size_t)v * a.dvZ + k];
+                        if (ed < 0) break;
+                        const int c = ed / a.dc - a.mX;
                         atomicXor(&synZ[c >> 5], 1u << (c & 31));
                     }
             }
@@ -722,7 +732,7 @@ static int launch_mc_gap(const McArgsHost& h, hipStream_t st)
     a.n = c.n; a.nb = (c.n + 7) / 8; a.mX = c.mX; a.mZ = c.mZ; a.P = c.P; a.L = c.L; a.J = c.J; a.K = c.K;
     a.sX = h.sX; a.sZ = h.sZ; a.sXp = h.sXp; a.sZp = h.sZp; a.errp = h.errp;
     a.varEdge = h.varEdge;
-    a.dc = c.L; a.dvX = c.J; a.dvZ = c.K;
+    a.dc = c.stride(); a.dvX = c.col_stride(0); a.dvZ = c.col_stride(1);
     if (a.varEdge == nullptr) {
         if (!c.is_qc || c.J * c.L > 128 || c.K * c.L > 128)
             return fail(QEC_ERR_UNSUPPORTED, "mc front end: needs a QC code or a check table");
@@ -764,7 +774,7 @@ int launch_mc_errors_syndrome(int src, const McArgsHost& h, hipStream_t st)
     a.sX = h.sX; a.sZ = h.sZ; a.errp = h.errp;
     a.chkVar = h.chkVar;
     a.B = h.B;
-    a.n = c.n; a.nb = (c.n + 7) / 8; a.L = c.L; a.P = c.P; a.J = c.J; a.K = c.K; a.mX = c.mX; a.mZ = c.mZ;
+    a.n = c.n; a.nb = (c.n + 7) / 8; a.L = c.stride(); a.P = c.P; a.J = c.J; a.K = c.K; a.mX = c.mX; a.mZ = c.mZ;
     if (a.chkVar == nullptr) {
         if (!c.is_qc || c.J * c.L > 128 || c.K * c.L > 128) return fail(QEC_ERR_UNSUPPORTED, "mc front end: needs a QC code or a check table");
         for (size_t k = 0; k < c.EX.size(); ++k) a.EX[k] = c.EX[k];

@@ -50,9 +50,10 @@ void build_sector(const std::vector<uint8_t>& pcm, int m, int n, int L, size_t q
 
 void osd_plan_build(const Code& c, OsdPlan& out)
 {
-    out.qn = (size_t)(c.mX + c.mZ) * c.L;
-    build_sector(c.pcmX, c.mX, c.n, c.L, 0, out.sec[0]);
-    build_sector(c.pcmZ, c.mZ, c.n, c.L, (size_t)c.mX * c.L, out.sec[1]);
+    const int L = c.stride();  // slots per check of the q_final layout (a general code: D)
+    out.qn = (size_t)(c.mX + c.mZ) * L;
+    build_sector(c.pcmX, c.mX, c.n, L, 0, out.sec[0]);
+    build_sector(c.pcmZ, c.mZ, c.n, L, (size_t)c.mX * L, out.sec[1]);
 }
 
 bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8_t* e, int order_cs, bool* swept)

@@ -31,6 +31,13 @@ struct Code {
     std::vector<uint8_t> imp;          // 2n x 2n dense I-P (empty for generated codes without a derived check)
     int logical_mode = 0;              // QEC_LOGICAL_*: imp from the file (or none), or derived (derive_logical)
     bool is_qc = false;                // every block a circulant permutation matrix
+    // A general code (general_code: two 0/1 matrices, any degrees): J = K = L = P = sigma = tau = 0 and the
+    // sizes are the matrices'.  D is the slot stride of its message / q_final layout (the largest row weight of
+    // both sectors), dvX / dvZ its largest column weights, k = n - rank HX - rank HZ.
+    bool general = false;
+    int D = 0, dvX = 0, dvZ = 0, k = 0;
+    int stride() const { return general ? D : L; }                         // slots per check
+    int col_stride(int sector) const { return general ? (sector ? dvZ : dvX) : (sector ? K : J); }
     std::vector<int> EX, EZ;           // J x L / K x L shifts in [0, P): row i -> col (E + i) mod P
     // Bit-packed I-P rows that are not all-zero (for CheckLogicalError).
     int imp_words = 0;                 // u64 words per packed 2n-bit row
@@ -44,6 +51,10 @@ struct Code {
 
 int load_code(const char* path, Code& out);
 int generate_code(int J, int K, int L, int P, int sigma, int tau, Code& out);
+// A general code from dense row-major 0/1 bytes (qec_code_from_matrices); imp (nullable) is a 2n x 2n I-P matrix.
+int general_code(int n, int mX, const uint8_t* HX, int mZ, const uint8_t* HZ, const uint8_t* imp, Code& out);
+// max row weight X, Z, max column weight X, Z, slot stride (qec_code_degrees); any code
+void code_degrees(const Code& c, int out[5]);
 // Generator exponent tables (QEC_LDPC/QEC_LDPC_CSS.cu:37-90); returns false if sigma has no inverse.
 bool generator_exponents(int J, int K, int L, int P, int sigma, int tau, std::vector<int>& EX, std::vector<int>& EZ);
 void finalize_code(Code& c);  // derive circulant tables + packed I-P from the dense matrices
