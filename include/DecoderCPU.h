@@ -68,6 +68,16 @@ public:
         check(qec_decoder_set_option(dec_, QEC_OPT_OSD_ITERATIONS, iterations));
         check(qec_decoder_set_option(dec_, QEC_OPT_OSD, order >= 0 ? 1 : 0));
     }
+    // Per-qubit priors (qec_decoder_set_priors): priorX[v] / priorZ[v] is the prior that bit v of the X / Z
+    // estimate is 1 (n entries each, 0 <= pi <= 1).  While set, BP uses them and the errorProbability argument
+    // of Decode, DecodeBatch and GetStatistics is not used.
+    void SetPriors(const std::vector<float>& priorX, const std::vector<float>& priorZ)
+    {
+        if (priorX.size() != (size_t)_code.n || priorZ.size() != (size_t)_code.n)
+            throw std::string("SetPriors: priorX and priorZ need n entries each");
+        check(qec_decoder_set_priors(dec_, priorX.data(), priorZ.data()));
+    }
+    void ClearPriors() { check(qec_decoder_set_priors(dec_, nullptr, nullptr)); }
     qec_decoder* handle() { return dec_; }
 
 private:

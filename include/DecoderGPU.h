@@ -25,6 +25,12 @@ public:
         dec_ = qec_decoder_create(_code.handle(), device, 0);
         if (!dec_) throw std::string(qec_last_error());
     }
+    // an explicit engine (QEC_ENGINE_*), e.g. QEC_ENGINE_SPARSE for a circulant code that is to take priors
+    DecoderGPU(Quantum_LDPC_Code code, int device, int engine) : Decoder(code)
+    {
+        dec_ = qec_decoder_create_engine(_code.handle(), device, 0, engine);
+        if (!dec_) throw std::string(qec_last_error());
+    }
     // several GPUs of this node (a device may repeat); every call shards its samples over them
     DecoderGPU(Quantum_LDPC_Code code, const std::vector<int>& devices) : Decoder(code)
     {
@@ -140,6 +146,17 @@ public:
         check(qec_decoder_set_option(dec_, QEC_OPT_OSD_ITERATIONS, iterations));
         check(qec_decoder_set_option(dec_, QEC_OPT_OSD, order >= 0 ? 1 : 0));
     }
+    // Per-qubit priors (qec_decoder_set_priors): priorX[v] / priorZ[v] is the prior that bit v of the X / Z
+    // estimate is 1 (n entries each, 0 <= pi <= 1).  While set, BP uses them and the errorProbability argument
+    // of Decode, DecodeBatch and GetStatistics is not used.  The sparse-graph engine takes them; a decoder
+    // on the wave-circulant engine throws the library's message (construct it with QEC_ENGINE_SPARSE).
+    void SetPriors(const std::vector<float>& priorX, const std::vector<float>& priorZ)
+    {
+        if (priorX.size() != (size_t)_code.n || priorZ.size() != (size_t)_code.n)
+            throw std::string("SetPriors: priorX and priorZ need n entries each");
+        check(qec_decoder_set_priors(dec_, priorX.data(), priorZ.data()));
+    }
+    void ClearPriors() { check(qec_decoder_set_priors(dec_, nullptr, nullptr)); }
     qec_decoder* handle() { return dec_; }
 
 private:

@@ -316,6 +316,41 @@ enum {
 int qec_near_hard_threshold(float pPrime, int R, int L, float* eps0, uint32_t* T);
 int qec_decoder_set_option(qec_decoder* dec, int option, int value);
 int qec_decoder_get_option(const qec_decoder* dec, int option, int* value);
+/* Per-qubit error priors ("prior form"): biased noise, qubits of different quality,
+ * erasures (prior 1/2), measurement-error columns with their own rate.  priorX, priorZ: HOST arrays of n
+ * floats; priorX[v] is the prior that bit v of the X-sector estimate (eX) is 1, priorZ[v] the same for eZ.
+ * While priors are set, a sector's BP starts every real slot of variable v at pi_v (unused slots of a general
+ * code stay +0.0f) and starts v's two running products from 1.0f - pi_v and pi_v, where the scalar form uses
+ * 1 - p' and p' = (2/3) errorProbability; operation order, check update, stop rules, flags, iteration counts,
+ * decisions and the q_final layout are untouched.  With every pi_v equal to the float 2.0f / 3.0f * p every
+ * output bit equals the scalar call at p.
+ *   - The errorProbability argument of EVERY decode entry point (qec_decode_batch, _dev, _packed, _packed_dev,
+ *     qec_get_statistics, qec_monte_carlo, the OSD stage's soft decode) is then NOT USED by BP; it must still
+ *     be a valid float.
+ *   - Both NULL clears the priors: the handle behaves exactly as one that never had any (the same kernels).
+ *     Exactly one NULL: QEC_ERR_ARG.  Every entry must satisfy 0 <= pi <= 1 (0, 0.5 and 1 are legal; NaN is
+ *     not): QEC_ERR_ARG otherwise, and the error text names the sector and index ("priorZ[17] = ...").
+ *   - Synchronous: waits for the handle's last launch, then copies the priors to the device.  The device
+ *     buffer is allocated by the first set and rewritten in place afterwards, so the _dev decode entry points
+ *     keep their contract (no allocation, no synchronisation) and stay graph-capturable with priors set; a
+ *     captured graph replayed after a later set decodes with the new values.
+ *   - Engines: the sparse-graph engine (regular and general codes) and the CPU engine take priors.  A
+ *     wave-circulant handle refuses with QEC_ERR_UNSUPPORTED -- its hard-message shortcuts and their thresholds
+ *     are proven for one p' -- and the text says to create the decoder with QEC_ENGINE_SPARSE.
+ *     qec_decode_bits_packed_dev is wave-circulant only and so never sees priors.  On a group the priors apply
+ *     to every part.
+ *   - The near-hard jump (QEC_OPT_NEAR_HARD_JUMP) of the CPU engine never fires while priors are set (its lemma
+ *     is stated for one p'); outputs do not depend on the jump either way.
+ *   - OSD (QEC_OPT_OSD, QEC_OPT_OSD_ORDER): the soft decode that orders the columns runs with the priors.  The
+ *     combination sweep still scores its candidates by plain Hamming weight, NOT by likelihood under the
+ *     priors.  The stage's result depends on (code, syndrome, priors, QEC_OPT_OSD_ITERATIONS, lambda) only.
+ *   - qec_sample_syndrome_dev and qec_monte_carlo then draw their errors from the independent sampler of
+ *     qec_sample_independent_dev (their scalar p is not used), and qec_monte_carlo takes the unfused pipeline
+ *     with byte syndromes (sample + syndromes + packed errors, packed decode, OSD stage if on, statistics),
+ *     the sequence QEC_OPT_OSD already forces; the counters describe that run. */
+int qec_decoder_set_priors(qec_decoder* dec, const float* priorX, const float* priorZ);
+/* 1 and the arrays filled (n floats each; a NULL array is skipped) if priors are set, 0 if not. */
+int qec_decoder_get_priors(const qec_decoder* dec, float* priorX, float* priorZ);
 /* which kernel variant serves this code: writes a short name (e.g. "wave-circulant P=61 G=1") */
 int qec_decoder_describe(const qec_decoder* dec, char* buf, size_t len);
 
@@ -330,7 +365,10 @@ int qec_decoder_describe(const qec_decoder* dec, char* buf, size_t len);
  *            A general code (qec_code_from_matrices): the stride is D of qec_code_degrees
  *            instead of L, B x (numEqsX+numEqsZ) x D; a check of lower weight leaves its
  *            last slots unused, written as +0.0f
- * errorProbability / maxIterations as in Decode; stop = QEC_STOP_*. */
+ * errorProbability / maxIterations as in Decode; stop = QEC_STOP_*.
+ * On a handle with priors (qec_decoder_set_priors) BP uses them and errorProbability is NOT USED, here and
+ * in qec_decode_batch_dev, qec_decode_batch_packed, qec_decode_batch_packed_dev, qec_get_statistics and
+ * qec_monte_carlo (it must still be a valid float). */
 int qec_decode_batch(qec_decoder* dec, const uint8_t* sX, const uint8_t* sZ, size_t B,
                      float errorProbability, int maxIterations, int stop,
                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, int32_t* iters, float* q_final);
@@ -397,11 +435,21 @@ typedef struct {
  * w: 0 = X, 1 = Y, 2 = Z (Y sets both bits).  Any shard of the index space can be drawn alone. */
 int qec_sample_depolarizing_dev(qec_decoder* dec, uint64_t seed, uint64_t start, size_t B, float p, uint8_t* x,
                                 uint8_t* z, void* stream);
+/* Independent X / Z errors over the handle's priors (qec_decoder_set_priors; QEC_ERR_ARG without them) for
+ * samples [start, start+B) of stream `seed` (device buffers x, z: B x n bytes).  Sample b makes
+ * Philox4x32-10 calls k = 0, 1, ... with counter (b lo, b hi, k, 0x51ED270B) and key (seed lo, seed hi); word
+ * 4k + j is output word j of call k; x[v] = (word 2v < thrX[v]) and z[v] = (word 2v + 1 < thrZ[v]) with
+ * thr = floor(pi 2^32), evaluated in double from the float, as a 64-bit value: pi = 1 gives 2^32 and always
+ * hits, pi = 0 never hits.  Any shard of the index space can be drawn alone.  Enqueued on `stream`; no
+ * synchronisation, no allocation.  Single-device GPU handle. */
+int qec_sample_independent_dev(qec_decoder* dec, uint64_t seed, uint64_t start, size_t B, uint8_t* x, uint8_t* z,
+                               void* stream);
 /* Fused front end: the depolarising errors of qec_sample_depolarizing_dev (same stream, same
  * bits) go straight to their syndromes (GetSyndromeX/Z, Quantum_LDPC_Code.h:94-124) without
  * leaving the chip: sX B x numEqsX, sZ B x numEqsZ, and optionally errp B x 2 ceil(n/8), the
  * errors bit-packed in the decision-record layout (x bits then z bits) for
- * qec_statistics_packed_dev.  One wave per sample. */
+ * qec_statistics_packed_dev.  One wave per sample.  On a handle with priors the errors are those of
+ * qec_sample_independent_dev instead (same stream, same bits) and p is not used. */
 int qec_sample_syndrome_dev(qec_decoder* dec, uint64_t seed, uint64_t start, size_t B, float p, uint8_t* sX,
                             uint8_t* sZ, uint8_t* errp, void* stream);
 /* GetSyndromeX/Z (Quantum_LDPC_Code.h:94-124) of device error vectors: x, z B x n -> sX B x numEqsX, sZ B x numEqsZ */
@@ -450,7 +498,9 @@ int qec_pack_decisions_dev(qec_decoder* dec, const uint8_t* eX, const uint8_t* e
  * `seed`, in batches of `batch`: fused sample + syndrome -> packed decode (stop rule `stop`) ->
  * statistics with iteration sums, all on the device with no per-batch host synchronisation.
  * A multi-device decoder shards [start, start + count) contiguously over its parts.
- * Synchronous; fills *out (decodeSeconds: decode-kernel time, the largest over parts). */
+ * Synchronous; fills *out (decodeSeconds: decode-kernel time, the largest over parts).
+ * On a handle with priors: the samples of qec_sample_independent_dev, decoded with the priors, through the
+ * unfused byte-syndrome pipeline; errorProbability is not used (qec_decoder_set_priors). */
 int qec_monte_carlo(qec_decoder* dec, uint64_t seed, uint64_t start, uint64_t count, float errorProbability,
                     int maxIterations, int stop, size_t batch, qec_mc_result* out);
 

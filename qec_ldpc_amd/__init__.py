@@ -44,6 +44,7 @@ EXPORTS = (
     "qec_decoder_create", "qec_decoder_create_engine", "qec_decoder_create_multi", "qec_decoder_destroy",
     "qec_decoder_num_parts", "qec_decoder_part", "qec_decoder_device", "qec_decoder_describe",
     "qec_decoder_set_option", "qec_decoder_get_option", "qec_near_hard_threshold",
+    "qec_decoder_set_priors", "qec_decoder_get_priors", "qec_sample_independent_dev",
     "qec_decode_batch", "qec_decode_batch_dev", "qec_decode_batch_packed", "qec_decode_batch_packed_dev",
     "qec_decode_bits_packed_dev",
     "qec_sample_fixed_weight", "qec_get_statistics",
@@ -141,6 +142,9 @@ def lib():
             "qec_decoder_set_option": (i, [vp, i, i]),
             "qec_decoder_get_option": (i, [vp, i, vp]),
             "qec_near_hard_threshold": (i, [f, i, i, vp, vp]),
+            "qec_decoder_set_priors": (i, [vp, vp, vp]),
+            "qec_decoder_get_priors": (i, [vp, vp, vp]),
+            "qec_sample_independent_dev": (i, [vp, ctypes.c_uint64, ctypes.c_uint64, sz, vp, vp, vp]),
             "qec_decode_batch": (i, [vp, vp, vp, sz, f, i, i, vp, vp, vp, vp, vp]),
             "qec_decode_batch_dev": (i, [vp, vp, vp, sz, f, i, i, vp, vp, vp, vp, vp, vp]),
             "qec_decode_batch_packed": (i, [vp, vp, vp, sz, f, i, i, vp, vp]),
@@ -437,6 +441,38 @@ class DecoderGPU:
         _check(lib().qec_decoder_get_option(self._h, OPTION[name], ctypes.byref(v)), "qec_decoder_get_option")
         return v.value
 
+    def set_priors(self, priorX, priorZ):
+        """Per-qubit priors (qec_decoder_set_priors): priorX[v] / priorZ[v] is the prior that bit v of eX / eZ
+        is 1 -- array-likes of length n (float32 values are taken as they are), or a scalar for every qubit;
+        set_priors(None, None) clears them.  While set, BP uses them in place of p' = (2/3) p and the `p`
+        argument of every decode call, GetStatistics, sample_syndrome_dev and monte_carlo is not used (the
+        latter two draw sample_independent_dev's errors).  Sparse-graph and CPU engines; a wave-circulant
+        decoder refuses (create it with engine="sparse").  OSD-CS still scores by Hamming weight."""
+        if (priorX is None) != (priorZ is None):
+            raise QecError("set_priors: priorX and priorZ must both be given, or both be None (clear)")
+        if priorX is None:
+            _check(lib().qec_decoder_set_priors(self._h, None, None), "qec_decoder_set_priors")
+            return
+        arrs = []
+        for name, pr in (("priorX", priorX), ("priorZ", priorZ)):
+            a = np.asarray(pr, dtype=np.float32)
+            if a.ndim == 0:
+                a = np.full(self.code.n, a, dtype=np.float32)
+            if a.shape != (self.code.n,):
+                raise QecError("set_priors: %s must be a scalar or have length n = %d, has shape %s"
+                               % (name, self.code.n, a.shape))
+            arrs.append(np.ascontiguousarray(a))
+        _check(lib().qec_decoder_set_priors(self._h, _ptr(arrs[0]), _ptr(arrs[1])), "qec_decoder_set_priors")
+
+    def get_priors(self):
+        """(priorX, priorZ) as float32 arrays (qec_decoder_get_priors), or None when no priors are set."""
+        pX = np.empty(self.code.n, dtype=np.float32)
+        pZ = np.empty(self.code.n, dtype=np.float32)
+        rc = lib().qec_decoder_get_priors(self._h, _ptr(pX), _ptr(pZ))
+        if rc < 0:
+            raise QecError("qec_decoder_get_priors failed (%d): %s" % (rc, last_error()))
+        return (pX, pZ) if rc == 1 else None
+
     def last_path(self):
         """The launch sequence of this handle's last decode call (QEC_OPT_LAST_PATH) as a set of
         PATH names, e.g. {"bit_rows", "records", "ordered", "sector_order", "sector_launches"}."""
@@ -449,7 +485,8 @@ class DecoderGPU:
 
     # ---- host buffers ------------------------------------------------------------------
     def decode_batch(self, sX, sZ, p, max_iter, stop="ref", want_iters=False, want_q=False):
-        """Host-buffer batch decode -> (eX, eZ, flags, iters|None, q|None)."""
+        """Host-buffer batch decode -> (eX, eZ, flags, iters|None, q|None).  With priors set (set_priors)
+        BP uses them and p is not used, here and in every other decode call."""
         c = self.code
         sX = np.atleast_2d(sX)
         B = sX.shape[0]
@@ -623,9 +660,24 @@ class DecoderGPU:
                                                  ctypes.c_void_p(self._stream(stream))),
                "qec_sample_depolarizing_dev")
 
+    def sample_independent_dev(self, seed, start, x, z, stream=None):
+        """Device errors drawn independently per qubit and sector with the decoder's priors
+        (qec_sample_independent_dev; needs set_priors) for samples [start, start + x.shape[0]):
+        x[b, v] = word 2v of sample b's Philox stream < floor(priorX[v] 2^32), z[b, v] likewise from
+        word 2v + 1 and priorZ."""
+        import torch
+        self._single("sample_independent_dev")
+        B, n = x.shape[0], self.code.n
+        _check(lib().qec_sample_independent_dev(self._h, seed & (2 ** 64 - 1), start, B,
+                                                self._t(x, "x", torch.uint8, (B, n)),
+                                                self._t(z, "z", torch.uint8, (B, n)),
+                                                ctypes.c_void_p(self._stream(stream))),
+               "qec_sample_independent_dev")
+
     def sample_syndrome_dev(self, seed, start, p, sX, sZ, errp=None, stream=None):
         """Fused front end: syndromes of the depolarising errors of samples [start, start + B)
-        (the sample_depolarizing_dev stream), optionally the errors bit-packed (errp [B, 2 ceil(n/8)])."""
+        (the sample_depolarizing_dev stream), optionally the errors bit-packed (errp [B, 2 ceil(n/8)]).
+        With priors set the errors are sample_independent_dev's and p is not used."""
         import torch
         self._single("sample_syndrome_dev")
         c = self.code
@@ -701,7 +753,8 @@ class DecoderGPU:
 
     # ---- Monte-Carlo ---------------------------------------------------------------------
     def monte_carlo(self, seed, start, count, p, max_iter, stop="syndrome", batch=1 << 20):
-        """Device Monte-Carlo run (sample -> syndrome -> decode -> statistics); returns a dict."""
+        """Device Monte-Carlo run (sample -> syndrome -> decode -> statistics); returns a dict.  With priors
+        set: sample_independent_dev's errors decoded with the priors, p not used."""
         r = MCResult()
         _check(lib().qec_monte_carlo(self._h, seed & (2 ** 64 - 1), start, count, float(p), int(max_iter),
                                      STOP[stop], batch, ctypes.byref(r)), "qec_monte_carlo")

@@ -54,6 +54,7 @@ struct SparseArgs {
     int n, mX, mZ, dc, dvX, dvZ;
     float errorProbability;
     int maxIter;
+    const float* prior;      // PRIORS kernels: pi of sector X [n], then of sector Z [n] (qec_decoder_set_priors)
 };
 
 constexpr int kSparseThreads = 256;
@@ -131,7 +132,11 @@ __device__ __forceinline__ bool sp_var(float* __restrict__ msg, const int32_t* _
 
 extern __shared__ __attribute__((aligned(16))) uint8_t sp_lds[];
 
-template <int STOP, int MAXDC, int MAXDV, bool LDS>
+// PRIORS: the per-variable prior form of DESIGN.md section 2 -- the initial message of a slot is the prior of
+// its variable (through chkVar) and a variable's two running products start from 1 - pi_v and pi_v, read
+// from global memory once per pass (8n bytes that every workgroup shares, so they stay in cache);
+// errorProbability is unused.  Without it the kernel is the scalar one, instruction for instruction.
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false>
 __global__ __launch_bounds__(kSparseThreads) void bp_sparse_kernel(const SparseArgs a)
 {
     const int tid = threadIdx.x, nt = blockDim.x;
@@ -151,7 +156,10 @@ __global__ __launch_bounds__(kSparseThreads) void bp_sparse_kernel(const SparseA
         // the entry as given: the check update takes its truthiness, the syndrome tests compare it
         // exactly (DecoderCPU.h:178, :381), so an entry other than 0/1 never matches a parity
         for (int c = tid; c < m; c += nt) syn[c] = c < mX ? a.sX[b * mX + c] : a.sZ[b * mZ + (c - mX)];
-        for (int e = tid; e < E; e += nt) msg[e] = pp;
+        if (PRIORS)
+            for (int e = tid; e < E; e += nt) msg[e] = a.prior[(e < EX ? 0 : n) + a.chkVar[e]];
+        else
+            for (int e = tid; e < E; e += nt) msg[e] = pp;
         __syncthreads();
 
         bool actX = true, actZ = true;  // workgroup-uniform
@@ -170,7 +178,8 @@ __global__ __launch_bounds__(kSparseThreads) void bp_sparse_kernel(const SparseA
                 if (z ? !actZ : !actX) continue;
                 const int dv = z ? a.dvZ : a.dvX;
                 const int32_t* ve = a.varEdge + (z ? (size_t)n * a.dvX + (size_t)(v - n) * dv : (size_t)v * dv);
-                const bool h = sp_var<MAXDV>(msg, ve, dv, pp, omp, last);
+                const float pv = PRIORS ? a.prior[v] : pp;  // v runs over [X | Z], as the prior array does
+                const bool h = sp_var<MAXDV>(msg, ve, dv, pv, PRIORS ? 1.0f - pv : omp, last);
                 if (STOP == QEC_STOP_SYNDROME) hd[v] = h;
             }
             __syncthreads();
@@ -352,7 +361,7 @@ struct GeneralArgs {
     const uint8_t* chkDeg;   // mX + mZ degree bytes
 };
 
-template <int STOP, int MAXDC, int MAXDV, bool LDS>
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false>
 __global__ __launch_bounds__(kSparseThreads) void bp_general_kernel(const GeneralArgs ga)
 {
     const SparseArgs& a = ga.s;
@@ -378,7 +387,13 @@ __global__ __launch_bounds__(kSparseThreads) void bp_general_kernel(const Genera
         }
         // one edge per thread, as the regular kernel's initialisation: the sentinel of the check table tells a
         // real slot from an unused one (coalesced words that every workgroup reads, so they stay in cache)
-        for (int e = tid; e < E; e += nt) msg[e] = a.chkVar[e] >= 0 ? pp : 0.0f;
+        if (PRIORS)
+            for (int e = tid; e < E; e += nt) {
+                const int v = a.chkVar[e];
+                msg[e] = v >= 0 ? a.prior[(e < EX ? 0 : n) + v] : 0.0f;
+            }
+        else
+            for (int e = tid; e < E; e += nt) msg[e] = a.chkVar[e] >= 0 ? pp : 0.0f;
         __syncthreads();
 
         bool actX = true, actZ = true;  // workgroup-uniform
@@ -398,7 +413,8 @@ __global__ __launch_bounds__(kSparseThreads) void bp_general_kernel(const Genera
                 if (z ? !actZ : !actX) continue;
                 const int dv = z ? a.dvZ : a.dvX;
                 const int32_t* ve = a.varEdge + (z ? (size_t)n * a.dvX + (size_t)(v - n) * dv : (size_t)v * dv);
-                const bool h = sp_var_general<MAXDV>(msg, ve, dv, pp, omp, last);
+                const float pv = PRIORS ? a.prior[v] : pp;
+                const bool h = sp_var_general<MAXDV>(msg, ve, dv, pv, PRIORS ? 1.0f - pv : omp, last);
                 if (STOP == QEC_STOP_SYNDROME) hd[v] = h;
             }
             __syncthreads();
@@ -479,20 +495,27 @@ __global__ __launch_bounds__(kSparseThreads) void bp_general_kernel(const Genera
 using SparseFn = void (*)(const SparseArgs);
 using GeneralFn = void (*)(const GeneralArgs);
 
+// f: the scalar kernels per stop rule; fp: the same shapes with PRIORS
 template <int MAXDC, int MAXDV, bool LDS>
-static void general_fns(GeneralFn (&f)[3])
+static void general_fns(GeneralFn (&f)[3], GeneralFn (&fp)[3])
 {
     f[QEC_STOP_REF] = bp_general_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS>;
     f[QEC_STOP_FIXED] = bp_general_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS>;
     f[QEC_STOP_SYNDROME] = bp_general_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS>;
+    fp[QEC_STOP_REF] = bp_general_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS, true>;
+    fp[QEC_STOP_FIXED] = bp_general_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS, true>;
+    fp[QEC_STOP_SYNDROME] = bp_general_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, true>;
 }
 
 template <int MAXDC, int MAXDV, bool LDS>
-static void sparse_fns(SparseFn (&f)[3])
+static void sparse_fns(SparseFn (&f)[3], SparseFn (&fp)[3])
 {
     f[QEC_STOP_REF] = bp_sparse_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS>;
     f[QEC_STOP_FIXED] = bp_sparse_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS>;
     f[QEC_STOP_SYNDROME] = bp_sparse_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS>;
+    fp[QEC_STOP_REF] = bp_sparse_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS, true>;
+    fp[QEC_STOP_FIXED] = bp_sparse_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS, true>;
+    fp[QEC_STOP_SYNDROME] = bp_sparse_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, true>;
 }
 
 struct SparsePlan {
@@ -501,9 +524,11 @@ struct SparsePlan {
     long long ws_bytes = 0;
     int grid = 0;
     SparseFn fn[3] = {nullptr, nullptr, nullptr};
+    SparseFn pfn[3] = {nullptr, nullptr, nullptr};    // the PRIORS kernels of the same shape
     // a general code: bp_general_kernel, its degree bytes and its fitted workgroup size
     bool general = false;
     GeneralFn gfn[3] = {nullptr, nullptr, nullptr};
+    GeneralFn gpfn[3] = {nullptr, nullptr, nullptr};
     DeviceArray<uint8_t> chkDeg;
     int threads = kSparseThreads;
     DeviceArray<int32_t> chkVar, varEdge;
@@ -592,16 +617,16 @@ void* sparse_plan_create(const Code& c, int device)
     const int wdv = std::max(dvX, dvZ) <= 4 ? 4 : std::max(dvX, dvZ) <= 8 ? 8 : 16;
     // instantiated shapes: (8,4) (16,8) (32,16); pick the smallest that covers the code
     if (general) {
-        if (wdc <= 8 && wdv <= 4) { if (p->lds) general_fns<8, 4, true>(p->gfn); else general_fns<8, 4, false>(p->gfn); }
-        else if (wdc <= 16 && wdv <= 8) { if (p->lds) general_fns<16, 8, true>(p->gfn); else general_fns<16, 8, false>(p->gfn); }
-        else { if (p->lds) general_fns<32, 16, true>(p->gfn); else general_fns<32, 16, false>(p->gfn); }
+        if (wdc <= 8 && wdv <= 4) { if (p->lds) general_fns<8, 4, true>(p->gfn, p->gpfn); else general_fns<8, 4, false>(p->gfn, p->gpfn); }
+        else if (wdc <= 16 && wdv <= 8) { if (p->lds) general_fns<16, 8, true>(p->gfn, p->gpfn); else general_fns<16, 8, false>(p->gfn, p->gpfn); }
+        else { if (p->lds) general_fns<32, 16, true>(p->gfn, p->gpfn); else general_fns<32, 16, false>(p->gfn, p->gpfn); }
         // the smallest workgroup that gives the wider pass a thread per node
         const long long wide = std::max<long long>(m, 2LL * n);
         p->threads = wide <= 64 ? 64 : wide <= 128 ? 128 : kSparseThreads;
     }
-    else if (wdc <= 8 && wdv <= 4) { if (p->lds) sparse_fns<8, 4, true>(p->fn); else sparse_fns<8, 4, false>(p->fn); }
-    else if (wdc <= 16 && wdv <= 8) { if (p->lds) sparse_fns<16, 8, true>(p->fn); else sparse_fns<16, 8, false>(p->fn); }
-    else { if (p->lds) sparse_fns<32, 16, true>(p->fn); else sparse_fns<32, 16, false>(p->fn); }
+    else if (wdc <= 8 && wdv <= 4) { if (p->lds) sparse_fns<8, 4, true>(p->fn, p->pfn); else sparse_fns<8, 4, false>(p->fn, p->pfn); }
+    else if (wdc <= 16 && wdv <= 8) { if (p->lds) sparse_fns<16, 8, true>(p->fn, p->pfn); else sparse_fns<16, 8, false>(p->fn, p->pfn); }
+    else { if (p->lds) sparse_fns<32, 16, true>(p->fn, p->pfn); else sparse_fns<32, 16, false>(p->fn, p->pfn); }
     try {
         if (hipSetDevice(device) != hipSuccess) throw std::runtime_error("hipSetDevice");
         int cus = 0;
@@ -615,6 +640,12 @@ void* sparse_plan_create(const Code& c, int device)
                 if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)p->ws_bytes) != hipSuccess)
                     throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+            // the PRIORS kernels take the same dynamic LDS (the grid stays the scalar kernels')
+            for (int k = 0; k < 3; ++k) {
+                const void* f = general ? reinterpret_cast<const void*>(p->gpfn[k]) : reinterpret_cast<const void*>(p->pfn[k]);
+                if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->ws_bytes) != hipSuccess)
+                    throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+            }
             per_cu = std::max(1, std::min(8, (int)((160 * 1024) / p->ws_bytes)));
             // a general code: the same 32 waves per CU at most, in its fitted workgroups
             if (general) {
@@ -660,9 +691,10 @@ void* sparse_plan_create(const Code& c, int device)
 const int32_t* sparse_plan_chkvar(const void* plan) { return static_cast<const SparsePlan*>(plan)->chkVar.data(); }
 const int32_t* sparse_plan_varedge(const void* plan) { return static_cast<const SparsePlan*>(plan)->varEdge.data(); }
 
+// prior: nullptr (the scalar kernels, errorProbability), or the device array of 2n priors (the PRIORS kernels)
 int launch_decode_sparse(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float errorProbability,
                          int maxIter, int stop, uint8_t* eX, uint8_t* eZ, uint8_t* flags, int32_t* iters, float* q,
-                         hipStream_t stream)
+                         hipStream_t stream, const float* prior)
 {
     auto* p = static_cast<SparsePlan*>(plan);
     if (B <= 0) return QEC_OK;
@@ -676,12 +708,13 @@ int launch_decode_sparse(void* plan, const uint8_t* sX, const uint8_t* sZ, long 
     a.n = p->n; a.mX = p->mX; a.mZ = p->mZ; a.dc = p->dc; a.dvX = p->dvX; a.dvZ = p->dvZ;
     a.errorProbability = errorProbability;
     a.maxIter = maxIter;
+    a.prior = prior;
     const unsigned grid = (unsigned)std::min<long long>(B, p->grid);
     if (p->general) {
         GeneralArgs ga{a, p->chkDeg.data()};
-        hipLaunchKernelGGL(p->gfn[stop], dim3(grid), dim3(p->threads), p->lds ? (size_t)p->ws_bytes : 0, stream, ga);
+        hipLaunchKernelGGL(prior ? p->gpfn[stop] : p->gfn[stop], dim3(grid), dim3(p->threads), p->lds ? (size_t)p->ws_bytes : 0, stream, ga);
     } else {
-        hipLaunchKernelGGL(p->fn[stop], dim3(grid), dim3(kSparseThreads), p->lds ? (size_t)p->ws_bytes : 0, stream, a);
+        hipLaunchKernelGGL(prior ? p->pfn[stop] : p->fn[stop], dim3(grid), dim3(kSparseThreads), p->lds ? (size_t)p->ws_bytes : 0, stream, a);
     }
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(QEC_ERR_HIP, std::string("bp_sparse launch: ") + hipGetErrorString(err));

@@ -78,13 +78,15 @@ const int32_t* sparse_plan_chkvar(const void* plan);
 const int32_t* sparse_plan_varedge(const void* plan);
 int launch_decode_sparse(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float errorProbability,
                          int maxIter, int stop, uint8_t* eX, uint8_t* eZ, uint8_t* flags, int32_t* iters, float* q,
-                         hipStream_t stream);
+                         hipStream_t stream, const float* prior);
+int launch_sample_independent(uint64_t seed, uint64_t start, long long B, int n, const float* prior, uint8_t* x,
+                              uint8_t* z, hipStream_t st);
 void* cpu_plan_create(const Code& c);
 void cpu_plan_free(void* plan);
 int cpu_threads();
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
-                     bool near_hard);
+                     bool near_hard, const float* prior);
 int launch_pack_decisions(const uint8_t* eX, const uint8_t* eZ, const uint8_t* flags, long long B, int n, uint8_t* out,
                           hipStream_t st);
 int launch_statistics(const Code& c, const uint64_t* imp_cols, const uint8_t* x, const uint8_t* z, const uint8_t* eX,
@@ -152,6 +154,14 @@ struct qec_decoder {
     unsigned long long osd_sectors = 0;  // QEC_OPT_OSD_SECTORS: sectors repaired in the last call
     int osd_order = 0;              // QEC_OPT_OSD_ORDER: lambda of the combination sweep, 0 = OSD-0
     unsigned long long osd_cs_sectors = 0;  // QEC_OPT_OSD_CS_SECTORS: of those, the winner was not the OSD-0 estimate
+    // per-qubit priors (qec_decoder_set_priors): the host copy (sector X [n], then Z [n]) and, on a GPU handle,
+    // the device copy the PRIORS kernels and the independent sampler read (allocated on the first set,
+    // rewritten in place afterwards); a group keeps the host copy and every part its own
+    bool has_priors = false;
+    std::vector<float> priors;
+    DeviceArray<float> dpri;
+    const float* prior_host() const { return has_priors ? priors.data() : nullptr; }
+    const float* prior_dev() const { return has_priors ? dpri.data() : nullptr; }
     // OSD stage: the elimination tables (host; device copy for the GPU engines), the compact
     // batch of failed samples (syndromes, estimates, flags, soft output) and the failed-record list
     std::shared_ptr<const OsdPlan> oplan;
@@ -667,6 +677,62 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
     }
 }
 
+int qec_decoder_set_priors(qec_decoder* d, const float* priorX, const float* priorZ)
+{
+    if (!d) return fail(QEC_ERR_ARG, "qec_decoder_set_priors: null decoder");
+    if ((priorX == nullptr) != (priorZ == nullptr))
+        return fail(QEC_ERR_ARG, "qec_decoder_set_priors: priorX and priorZ must both be given, or both be NULL (clear)");
+    if (!priorX) {  // clear: the handle behaves as one that never had priors (the device buffer is kept)
+        for (qec_decoder* p : d->parts) p->has_priors = false;
+        d->has_priors = false;
+        return QEC_OK;
+    }
+    if (!d->cpu && d->engine != QEC_ENGINE_SPARSE)
+        return fail(QEC_ERR_UNSUPPORTED,
+                    "qec_decoder_set_priors: the wave-circulant engine decodes with one error probability (its hard-message "
+                    "shortcuts are proven for one p'); create the decoder with QEC_ENGINE_SPARSE (engine \"sparse\")");
+    const int n = d->code->n;
+    for (int sec = 0; sec < 2; ++sec) {
+        const float* pr = sec ? priorZ : priorX;
+        for (int v = 0; v < n; ++v)
+            if (!(pr[v] >= 0.0f && pr[v] <= 1.0f))  // a NaN fails both comparisons
+                return fail(QEC_ERR_ARG, std::string("qec_decoder_set_priors: prior") + (sec ? "Z[" : "X[") + std::to_string(v) +
+                                             "] = " + std::to_string(pr[v]) + " is not in [0, 1]");
+    }
+    std::vector<float> host(2 * (size_t)n);
+    std::memcpy(host.data(), priorX, n * sizeof(float));
+    std::memcpy(host.data() + n, priorZ, n * sizeof(float));
+    for (qec_decoder* p : d->parts) {
+        const int rc = qec_decoder_set_priors(p, priorX, priorZ);
+        if (rc) return rc;
+    }
+    if (d->parts.empty() && !d->cpu) {
+        QEC_DEVICE_SCOPE(d->device);
+        // synchronous: the handle's last launch may still read the buffer this call rewrites
+        QEC_HIP_CHECK(hipStreamSynchronize(d->stream));
+        if (d->ws_used) QEC_HIP_CHECK(hipEventSynchronize(d->ws_ev));
+        try {
+            d->dpri.reserve(host.size());
+        } catch (const std::exception& ex) {
+            return fail(QEC_ERR_NOMEM, std::string("qec_decoder_set_priors: ") + ex.what());
+        }
+        QEC_HIP_CHECK(hipMemcpy(d->dpri.data(), host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    d->priors.swap(host);
+    d->has_priors = true;
+    return QEC_OK;
+}
+
+int qec_decoder_get_priors(const qec_decoder* d, float* priorX, float* priorZ)
+{
+    if (!d) return fail(QEC_ERR_ARG, "qec_decoder_get_priors: null decoder");
+    if (!d->has_priors) return 0;
+    const int n = d->code->n;
+    if (priorX) std::memcpy(priorX, d->priors.data(), n * sizeof(float));
+    if (priorZ) std::memcpy(priorZ, d->priors.data() + n, n * sizeof(float));
+    return 1;
+}
+
 int qec_decoder_get_option(const qec_decoder* d, int option, int* value)
 {
     if (!d || !value) return fail(QEC_ERR_ARG, "qec_decoder_get_option: bad argument");
@@ -762,7 +828,7 @@ int dispatch_decode(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, long l
                 return rc;
             eX = d->eX.data(); eZ = d->eZ.data(); flags = d->flags.data();
         }
-        rc = launch_decode_sparse(d->sparse, sX, sZ, B, p, maxIter, stop, eX, eZ, flags, iters, q, st);
+        rc = launch_decode_sparse(d->sparse, sX, sZ, B, p, maxIter, stop, eX, eZ, flags, iters, q, st, d->prior_dev());
         if (!rc && rec != nullptr) rc = launch_pack_decisions(eX, eZ, flags, B, c.n, rec, st);
         if (rc) return rc;
         return ws_release(d, st);
@@ -937,7 +1003,7 @@ int osd_repair_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t
             cFs.resize(cnt);
             const int rc = cpu_decode_batch(d->cpu, cX.data(), cZ.data(), (long long)cnt, p, d->osd_iters, QEC_STOP_FIXED,
                                             cEX.data(), cEZ.data(), cFs.data(), nullptr, nullptr, cq.data(), 0,
-                                            false);
+                                            false, d->prior_host());
             if (rc) return rc;
             long long swept = 0;
             osd_host_batch(*d->oplan, cX.data(), cZ.data(), (long long)cnt, cq.data(), cEX.data(), cEZ.data(), cF.data(), 0,
@@ -1055,7 +1121,7 @@ int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
     if (B == 0) return QEC_OK;
     if (d->cpu) {
         const int rc = cpu_decode_batch(d->cpu, sX, sZ, (long long)B, p, maxIter, stop, eX, eZ, flags, rec, iters, q, 0,
-                                        d->hard_paths && d->near_hard);
+                                        d->hard_paths && d->near_hard, d->prior_host());
         d->last_path = 0;
         return rc || !d->osd ? rc : osd_repair_host(d, sX, sZ, B, p, eX, eZ, flags, rec);
     }
@@ -1356,8 +1422,10 @@ int monte_carlo_part(qec_decoder* d, uint64_t seed, uint64_t start, uint64_t cou
         if (d->mc_time && k >= kRing && (rc = harvest(slot))) return rc;
         McArgsHost h;
         h.seed = seed; h.start = start + base; h.p = p;
+        h.prior = d->prior_dev();
         h.B = (long long)std::min<uint64_t>(batch, count - base);
-        rc = mc_batch(d, h, MC_SRC_PHILOX, p, maxIter, stop, true, d->mc_time ? ev.ev[2 * slot] : nullptr,
+        // priors set: the independent sampler over them; mc_batch then takes the unfused byte-syndrome pipeline
+        rc = mc_batch(d, h, d->has_priors ? MC_SRC_INDEPENDENT : MC_SRC_PHILOX, p, maxIter, stop, true, d->mc_time ? ev.ev[2 * slot] : nullptr,
                       d->mc_time ? ev.ev[2 * slot + 1] : nullptr, k == 0);
         if (rc) return rc;
     }
@@ -1404,7 +1472,8 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
         ez.resize((size_t)cnt * n);
         fl.resize(cnt);
         const int rc = cpu_decode_batch(d->cpu, sx.data(), sz.data(), cnt, p, maxIter, QEC_STOP_REF, ex.data(), ez.data(),
-                                        fl.data(), nullptr, nullptr, nullptr, 0, d->hard_paths && d->near_hard);
+                                        fl.data(), nullptr, nullptr, nullptr, 0, d->hard_paths && d->near_hard,
+                                        d->prior_host());
         if (rc) return rc;
         if (d->osd) {  // the counters describe the repaired estimates
             d->osd_sectors = 0;
@@ -1616,6 +1685,17 @@ int qec_sample_depolarizing_dev(qec_decoder* d, uint64_t seed, uint64_t start, s
     return launch_sample_depolarizing(seed, start, (long long)B, d->code->n, p, x, z, static_cast<hipStream_t>(stream));
 }
 
+int qec_sample_independent_dev(qec_decoder* d, uint64_t seed, uint64_t start, size_t B, uint8_t* x, uint8_t* z, void* stream)
+{
+    if (!d || (B && (!x || !z))) return fail(QEC_ERR_ARG, "qec_sample_independent_dev: bad argument");
+    int rc = single_device_only(d, "qec_sample_independent_dev");
+    if (rc) return rc;
+    if (!d->has_priors) return fail(QEC_ERR_ARG, "qec_sample_independent_dev: the decoder has no priors (qec_decoder_set_priors)");
+    QEC_DEVICE_SCOPE(d->device);
+    return launch_sample_independent(seed, start, (long long)B, d->code->n, d->dpri.data(), x, z,
+                                     static_cast<hipStream_t>(stream));
+}
+
 int qec_sample_syndrome_dev(qec_decoder* d, uint64_t seed, uint64_t start, size_t B, float p, uint8_t* sX, uint8_t* sZ,
                             uint8_t* errp, void* stream)
 {
@@ -1630,7 +1710,8 @@ int qec_sample_syndrome_dev(qec_decoder* d, uint64_t seed, uint64_t start, size_
     h.chkVar = syndrome_table(d);
     h.varEdge = variable_table(d);
     h.B = (long long)B;
-    return launch_mc_errors_syndrome(MC_SRC_PHILOX, h, static_cast<hipStream_t>(stream));
+    h.prior = d->prior_dev();
+    return launch_mc_errors_syndrome(d->has_priors ? MC_SRC_INDEPENDENT : MC_SRC_PHILOX, h, static_cast<hipStream_t>(stream));
 }
 
 int qec_syndrome_dev(qec_decoder* d, const uint8_t* x, const uint8_t* z, size_t B, uint8_t* sX, uint8_t* sZ,

@@ -125,8 +125,11 @@ bool near_hard_state(const CpuSector& S, int n, const uint8_t* syn, const float*
 // nearT != 0 (fixed / reference stop, no final messages requested): the near-hard jump -- once a state
 // meets C(eps0) every later one does, so the post-processing of this state gives the final decisions and
 // flags and the count is where the stop rule ends such a sector.
-int decode_sector(const CpuSector& S, int n, const uint8_t* syn, float errorProbability, int N, int stop, Work& w,
-                  bool& conv_out, bool& syn_ok, float* q_out, uint32_t nearT)
+// pri != nullptr (qec_decoder_set_priors): the sector's per-variable priors pi_v take the place of p' -- the
+// initial message of v's edges and the start of its two running products; the caller
+// then passes nearT = 0 (the jump's lemma is stated for one p').
+int decode_sector(const CpuSector& S, int n, const uint8_t* syn, float errorProbability, const float* pri, int N,
+                  int stop, Work& w, bool& conv_out, bool& syn_ok, float* q_out, uint32_t nearT)
 {
     const int m = S.m, dc = S.dc, dv = S.dv;
     const size_t E = (size_t)m * dc;
@@ -135,7 +138,10 @@ int decode_sector(const CpuSector& S, int n, const uint8_t* syn, float errorProb
     uint8_t* e = w.e.data();
     const float pp = (2.0f / 3.0f) * errorProbability;  // DecoderCPU.h:259
     const float one_minus_pp = 1.0f - pp;
-    std::fill(q, q + E, pp);  // InitVarNodes (:135-148, 265-267)
+    if (pri)
+        for (size_t k = 0; k < E; ++k) q[k] = pri[S.chk_var[k]];
+    else
+        std::fill(q, q + E, pp);  // InitVarNodes (:135-148, 265-267)
     auto hard_decision = [&]() {
         for (int v = 0; v < n; ++v) {
             bool hd = false;
@@ -172,8 +178,9 @@ int decode_sector(const CpuSector& S, int n, const uint8_t* syn, float errorProb
         const bool last = iter == N - 1;
         for (int v = 0; v < n; ++v) {
             const int32_t* ve = S.var_edge.data() + (size_t)v * dv;
+            const float pv = pri ? pri[v] : pp, omv = pri ? 1.0f - pri[v] : one_minus_pp;
             for (int j = 0; j < dv; ++j) {
-                float P0 = one_minus_pp, P1 = pp;
+                float P0 = omv, P1 = pv;
                 for (int k = 0; k < dv; ++k) {
                     if (k == j && !last) continue;
                     const float rk = r[ve[k]];
@@ -210,9 +217,9 @@ int decode_sector(const CpuSector& S, int n, const uint8_t* syn, float errorProb
 }
 
 // decode_sector for a general code: the same rules with each node's own degree, over real edges only
-// (DESIGN.md section 2).  Unused slots of q stay +0.0f.  No near-hard jump.
-int decode_sector_general(const CpuSector& S, int n, const uint8_t* syn, float errorProbability, int N, int stop, Work& w,
-                          bool& conv_out, bool& syn_ok, float* q_out)
+// (DESIGN.md section 2).  Unused slots of q stay +0.0f.  No near-hard jump.  pri: as decode_sector's.
+int decode_sector_general(const CpuSector& S, int n, const uint8_t* syn, float errorProbability, const float* pri, int N,
+                          int stop, Work& w, bool& conv_out, bool& syn_ok, float* q_out)
 {
     const int m = S.m, D = S.dc, dvs = S.dv;
     const size_t E = (size_t)m * D;
@@ -222,7 +229,8 @@ int decode_sector_general(const CpuSector& S, int n, const uint8_t* syn, float e
     const float pp = (2.0f / 3.0f) * errorProbability;
     const float one_minus_pp = 1.0f - pp;
     for (int c = 0; c < m; ++c)
-        for (int k = 0; k < D; ++k) q[(size_t)c * D + k] = k < S.chk_deg[c] ? pp : 0.0f;
+        for (int k = 0; k < D; ++k)
+            q[(size_t)c * D + k] = k < S.chk_deg[c] ? (pri ? pri[S.chk_var[(size_t)c * D + k]] : pp) : 0.0f;
     auto hard_decision = [&]() {
         for (int v = 0; v < n; ++v) {
             bool hd = false;  // a variable in no check decides 0
@@ -265,8 +273,9 @@ int decode_sector_general(const CpuSector& S, int n, const uint8_t* syn, float e
         for (int v = 0; v < n; ++v) {
             const int32_t* ve = S.var_edge.data() + (size_t)v * dvs;
             const int dv = S.var_deg[v];
+            const float pv = pri ? pri[v] : pp, omv = pri ? 1.0f - pri[v] : one_minus_pp;
             for (int j = 0; j < dv; ++j) {
-                float P0 = one_minus_pp, P1 = pp;
+                float P0 = omv, P1 = pv;
                 for (int k = 0; k < dv; ++k) {
                     if (k == j && !last) continue;
                     const float rk = r[ve[k]];
@@ -324,9 +333,10 @@ int cpu_threads()
 }
 
 // Batched Decode on host buffers; outputs in byte form (eX, eZ, flags) and/or packed records.
+// prior: nullptr, or the handle's priors (n floats of sector X, then n of sector Z); p is then unused.
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
-                     bool near_hard)
+                     bool near_hard, const float* prior)
 {
     const CpuPlan& P = *static_cast<const CpuPlan*>(plan);
     const int n = P.n, nb = (n + 7) / 8;
@@ -334,7 +344,7 @@ int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long
     const size_t qper = (size_t)mX * P.sec[0].dc + (size_t)mZ * P.sec[1].dc;
     // near-hard jump (QEC_OPT_NEAR_HARD_JUMP): per-sector compare values for this p', as the kernels' launch
     uint32_t nearT[2] = {0u, 0u};
-    if (near_hard && !P.general && qf == nullptr && stop != QEC_STOP_SYNDROME)
+    if (near_hard && !prior && !P.general && qf == nullptr && stop != QEC_STOP_SYNDROME)
         for (int sec = 0; sec < 2; ++sec) nearT[sec] = near_hard_threshold((2.0f / 3.0f) * p, P.sec[sec].dv, P.sec[sec].dc).T;
     if (threads <= 0) threads = cpu_threads();
     threads = (int)std::max<long long>(1, std::min<long long>(threads, B));
@@ -351,8 +361,9 @@ int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long
                 bool conv = false, ok = false;
                 float* qo = qf ? qf + b * qper + (sec ? (size_t)mX * P.sec[0].dc : 0) : nullptr;
                 const uint8_t* syn = sec ? sZ + b * mZ : sX + b * mX;
-                const int it = P.general ? decode_sector_general(S, n, syn, p, maxIter, stop, w, conv, ok, qo)
-                                         : decode_sector(S, n, syn, p, maxIter, stop, w, conv, ok, qo, nearT[sec]);
+                const float* pri = prior ? prior + (size_t)sec * n : nullptr;
+                const int it = P.general ? decode_sector_general(S, n, syn, p, pri, maxIter, stop, w, conv, ok, qo)
+                                         : decode_sector(S, n, syn, p, pri, maxIter, stop, w, conv, ok, qo, nearT[sec]);
                 if (!ok) f |= sec ? QEC_SYNDROME_FAIL_Z : QEC_SYNDROME_FAIL_X;
                 if (!conv) f |= sec ? QEC_CONVERGENCE_FAIL_Z : QEC_CONVERGENCE_FAIL_X;
                 if (iters) iters[2 * b + sec] = it;

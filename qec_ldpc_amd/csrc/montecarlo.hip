@@ -144,7 +144,9 @@ __global__ void pack_decisions_kernel(const uint8_t* __restrict__ eX, const uint
 // One wave per sample, errors staged in LDS (this wave's x and z rows, each zero-padded to
 // npad = 8 nb bytes):
 //   source DRAWS:  the reference's W (index, type) draws of the sample (DecoderCPU.h:452-457);
-//   source BYTES:  x, z rows [B][n] from HBM.
+//   source BYTES:  x, z rows [B][n] from HBM;
+//   source INDEPENDENT: the independent X / Z sampler over the handle's priors (qec_mc.h, indep_call):
+//                  lanes go over the sample's Philox calls, each call covers two qubits.
 // Then, from LDS: the syndromes sX, sZ (QC: s(r, i) = XOR_l e[l P + (E[r][l] + i) mod P]; any other
 // regular code: the check's variables from the sparse engine's table), and the bit-packed errors
 // errp [B][2 nb] in the decision-record layout (x bits, then z bits) for the statistics kernel.
@@ -158,6 +160,8 @@ struct McArgs {
     int W;
     const uint8_t* x;                          // BYTES: [B][n]
     const uint8_t* z;
+    const float* prior;                        // INDEPENDENT: priors of sector X [n], then Z [n]
+    uint64_t seed, start;                      //              sample b0 + s is index start + b0 + s of stream seed
     // outputs
     uint8_t* sX;                               // [B][mX]
     uint8_t* sZ;                               // [B][mZ]
@@ -202,6 +206,15 @@ __global__ __launch_bounds__(64 * kMcWaves) void mc_errors_syndrome_kernel(const
             uint8_t* ex = stage + (size_t)sI * 2 * npad;
             if (ty == 0 || ty == 1) ex[v] = 1;  // several draws may hit one qubit: they all store 1
             if (ty == 2 || ty == 1) ex[npad + v] = 1;
+        }
+    } else if constexpr (SRC == MC_SRC_INDEPENDENT) {
+        const int nc = npad / 2;  // calls per staged row pair: the padding qubits (>= n) come out 0
+        for (int t = lane; t < ns * nc; t += 64) {
+            const int sI = qdiv(t, a.magicG2), k = t - sI * nc;
+            const uint32_t r = indep_call(a.seed, a.start + (uint64_t)(b0 + sI), k, n, a.prior, a.prior + n);
+            uint8_t* ex = stage + (size_t)sI * 2 * npad;
+            *reinterpret_cast<uint16_t*>(ex + 2 * k) = (uint16_t)((r & 1u) | ((r >> 2) & 1u) << 8);
+            *reinterpret_cast<uint16_t*>(ex + npad + 2 * k) = (uint16_t)(((r >> 1) & 1u) | ((r >> 3) & 1u) << 8);
         }
     } else {
         for (int t = lane; t < ns * npad; t += 64) {
@@ -689,6 +702,31 @@ __global__ __launch_bounds__(64 * kOutcomeWaves) void logical_outcome_kernel(
     }
 }
 
+// byte form of the independent sampler (qec_sample_independent_dev): one wave per sample at a time, lanes
+// over its Philox calls; call k writes x[2k], x[2k + 1] and z[2k], z[2k + 1] of the sample's HBM rows
+constexpr int kIndepWaves = 4;
+__global__ __launch_bounds__(64 * kIndepWaves) void sample_independent_kernel(uint64_t seed, uint64_t start, long long B,
+                                                                             int n, const float* __restrict__ prior,
+                                                                             uint8_t* __restrict__ x,
+                                                                             uint8_t* __restrict__ z)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nc = (n + 1) / 2;
+    for (long long s = (long long)blockIdx.x * kIndepWaves + wv; s < B; s += (long long)gridDim.x * kIndepWaves) {
+        uint8_t* __restrict__ xr = x + s * n;
+        uint8_t* __restrict__ zr = z + s * n;
+        for (int k = lane; k < nc; k += 64) {
+            const uint32_t r = indep_call(seed, start + (uint64_t)s, k, n, prior, prior + n);
+            xr[2 * k] = (uint8_t)(r & 1u);
+            zr[2 * k] = (uint8_t)((r >> 1) & 1u);
+            if (2 * k + 1 < n) {
+                xr[2 * k + 1] = (uint8_t)((r >> 2) & 1u);
+                zr[2 * k + 1] = (uint8_t)((r >> 3) & 1u);
+            }
+        }
+    }
+}
+
 // ---- launchers --------------------------------------------------------------
 static int launch_check(const char* what)
 {
@@ -706,6 +744,16 @@ int launch_sample_depolarizing(uint64_t seed, uint64_t start, long long B, int n
     hipLaunchKernelGGL(sample_depolarizing_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256),
                        (size_t)(n + 1) * sizeof(uint32_t), st, make_gap(seed, p), start, B, n, x, z);
     return launch_check("sample_depolarizing");
+}
+
+int launch_sample_independent(uint64_t seed, uint64_t start, long long B, int n, const float* prior, uint8_t* x,
+                              uint8_t* z, hipStream_t st)
+{
+    if (B <= 0) return QEC_OK;
+    const long long blocks = std::min<long long>((B + kIndepWaves - 1) / kIndepWaves, 1 << 16);
+    hipLaunchKernelGGL(sample_independent_kernel, dim3((unsigned)blocks), dim3(64 * kIndepWaves), 0, st, seed, start, B, n,
+                       prior, x, z);
+    return launch_check("sample_independent");
 }
 
 static uint32_t magic_of(long long d) { return d > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d) : 0u; }
@@ -771,6 +819,8 @@ int launch_mc_errors_syndrome(int src, const McArgsHost& h, hipStream_t st)
     McArgs a{};
     a.idx = h.idx; a.type = h.type; a.W = h.W;
     a.x = h.x; a.z = h.z;
+    a.prior = h.prior; a.seed = h.seed; a.start = h.start;
+    if (src == MC_SRC_INDEPENDENT && h.prior == nullptr) return fail(QEC_ERR_ARG, "mc front end: the independent sampler needs priors");
     a.sX = h.sX; a.sZ = h.sZ; a.errp = h.errp;
     a.chkVar = h.chkVar;
     a.B = h.B;
@@ -800,6 +850,8 @@ int launch_mc_errors_syndrome(int src, const McArgsHost& h, hipStream_t st)
               : lt == 6 ? launch(mc_errors_syndrome_kernel<S, 6>) : launch(mc_errors_syndrome_kernel<S, 0>))
     if (src == MC_SRC_DRAWS)
         QEC_MC_LAUNCH(MC_SRC_DRAWS);
+    else if (src == MC_SRC_INDEPENDENT)
+        QEC_MC_LAUNCH(MC_SRC_INDEPENDENT);
     else
         QEC_MC_LAUNCH(MC_SRC_BYTES);
 #undef QEC_MC_LAUNCH

@@ -119,6 +119,30 @@ __device__ __forceinline__ void gap_table(const GapParams& gp, int n, uint32_t* 
     if (threadIdx.x == 0) T[0] = 0xFFFFFFFFu;
 }
 
+// Independent X / Z sampler (qec_sample_independent_dev; a handle with priors).  Sample b makes Philox calls
+// k = 0, 1, ... with counter (b_lo, b_hi, k, kIndepSalt), key (seed_lo, seed_hi); word 4k + j = output word j
+// of call k; x[v] = word 2v < thrX[v], z[v] = word 2v + 1 < thrZ[v], so call k decides qubits 2k and 2k + 1.
+constexpr uint32_t kIndepSalt = 0x51ED270Bu;
+
+// thr = floor(pi 2^32) for 0 <= pi <= 1, in double from the float (exact: 24 significant bits times 2^32) as a
+// 64-bit value: pi = 1 gives 2^32, above every word; pi = 0 gives 0, above none.
+__host__ __device__ inline uint64_t indep_threshold(float pi) { return (uint64_t)((double)pi * 4294967296.0); }
+
+// Call k of sample b: the x and z bits of qubits 2k and 2k + 1 (priX / priZ: n floats each; a qubit >= n gives
+// 0) as bits 0..3 = x[2k], z[2k], x[2k + 1], z[2k + 1].
+__device__ __forceinline__ uint32_t indep_call(uint64_t seed, uint64_t b, int k, int n, const float* __restrict__ priX,
+                                               const float* __restrict__ priZ)
+{
+    const int v0 = 2 * k, v1 = v0 + 1;
+    if (v0 >= n) return 0u;
+    const U4 o = philox4x32_10(U4{(uint32_t)b, (uint32_t)(b >> 32), (uint32_t)k, kIndepSalt}, (uint32_t)seed,
+                               (uint32_t)(seed >> 32));
+    uint32_t r = (uint32_t)((uint64_t)o.x < indep_threshold(priX[v0])) | (uint32_t)((uint64_t)o.y < indep_threshold(priZ[v0])) << 1;
+    if (v1 < n)
+        r |= (uint32_t)((uint64_t)o.z < indep_threshold(priX[v1])) << 2 | (uint32_t)((uint64_t)o.w < indep_threshold(priZ[v1])) << 3;
+    return r;
+}
+
 // counters, in qec_mc_counters order
 enum { C_WITHX, C_WITHZ, C_SYNX, C_SYNZ, C_LOGICAL, C_CORRECTED, C_CONVX, C_CONVZ, C_N };
 

@@ -5,7 +5,8 @@
 // The only change vs main.cu is the engine: DecoderGPU instead of DecoderCPU.
 // Exit status is 0 on success (main.cu returns 1).
 // Optional flags before the init file ("Config / flags"):
-//   --engine gpu|cpu   the decoder: DecoderGPU (default) or DecoderCPU (host threads, no GPU needed)
+//   --engine gpu|sparse|cpu   the decoder: DecoderGPU (default; the library's choice of GPU engine), DecoderGPU on
+//                      the sparse-graph engine (one GPU), or DecoderCPU (host threads, no GPU needed)
 //   --gpus N           GPUs 0..N-1 of this node, one decoder spanning them (counters identical to one GPU)
 //   --devices 0,3,5    the same for a list of GPUs
 //   --rng msvc|philox  msvc (default): main.cu's loop, fixed-weight errors w..W from the reference's
@@ -27,6 +28,11 @@
 //   --osd-order L      with --osd 0: the combination sweep OSD-CS over the L most suspicious non-pivot
 //                      columns (QEC_OPT_OSD_ORDER, 0 .. 64; default 0 = OSD-0)
 //   --osd-iterations K iterations of the soft decode that orders OSD's columns (default 3; needs --osd)
+//   --priors FILE      per-qubit priors (qec_decoder_set_priors) for whatever mode runs: FILE holds two lines of n
+//                      decimal floats, sector X then sector Z.  BP then uses them and the init file's p is not
+//                      used; --rng philox draws its errors independently per qubit from them.  Sparse-graph and
+//                      CPU engines: on a code the default engine decodes with wave-circulant kernels the run
+//                      fails with the library's message (use --engine sparse)
 // Unknown or inconsistent flags exit with status 2.
 #include <algorithm>
 #include <chrono>
@@ -72,11 +78,27 @@ void write_mc_block(std::ostream& out, const Quantum_LDPC_Code& code, unsigned l
 int usage(const std::string& why)
 {
     std::cerr << why << std::endl
-              << "usage: qec_ldpc [--engine gpu|cpu] [--gpus N | --devices i,j,...] [--rng msvc|philox]"
+              << "usage: qec_ldpc [--engine gpu|sparse|cpu] [--gpus N | --devices i,j,...] [--rng msvc|philox]"
                  " [--stop ref|fixed|syndrome] [--batch B] [--seed S] [--logical file|reference|degenerate]"
-                 " [--osd 0 [--osd-order L] [--osd-iterations K]] initFile"
+                 " [--osd 0 [--osd-order L] [--osd-iterations K]] [--priors FILE] initFile"
               << std::endl;
     return 2;
+}
+
+// --priors FILE: two lines of n decimal floats (sector X, then sector Z)
+void read_priors(const std::string& path, int n, std::vector<float>& pX, std::vector<float>& pZ)
+{
+    std::ifstream in(path);
+    if (!in.is_open()) throw std::string("--priors: unable to open " + path);
+    std::string line;
+    for (std::vector<float>* out : {&pX, &pZ}) {
+        if (!std::getline(in, line)) throw std::string("--priors: " + path + " needs two lines of n floats (X, then Z)");
+        std::stringstream ss(line);
+        float v;
+        while (ss >> v) out->push_back(v);
+        if (!ss.eof() || (int)out->size() != n)
+            throw std::string("--priors: each line of " + path + " needs n = " + std::to_string(n) + " decimal floats");
+    }
 }
 
 }  // namespace
@@ -91,7 +113,7 @@ int main(int argc, char** argv)
     std::time_t ts = std::chrono::system_clock::to_time_t(std::chrono::system_clock::now());
     log << std::endl << std::ctime(&ts);
     std::vector<int> devices{0};
-    std::string engine = "gpu", rng = "msvc", stopName = "ref", logical = "file";
+    std::string engine = "gpu", rng = "msvc", stopName = "ref", logical = "file", priorsFile;
     bool deviceFlag = false, stopFlag = false, batchFlag = false, seedFlag = false, osd = false, osdIterFlag = false;
     bool osdOrderFlag = false;
     int osdIterations = 3, osdOrder = 0;
@@ -113,7 +135,7 @@ int main(int argc, char** argv)
                 }
             } else if (flag == "--engine") {
                 engine = val;
-                if (engine != "gpu" && engine != "cpu") return usage("--engine: gpu or cpu");
+                if (engine != "gpu" && engine != "sparse" && engine != "cpu") return usage("--engine: gpu, sparse or cpu");
             } else if (flag == "--rng") {
                 rng = val;
                 if (rng != "msvc" && rng != "philox") return usage("--rng: msvc or philox");
@@ -143,6 +165,8 @@ int main(int argc, char** argv)
                 osdIterations = std::stoi(val);
                 osdIterFlag = true;
                 if (osdIterations < 1) return usage("--osd-iterations: at least 1");
+            } else if (flag == "--priors") {
+                priorsFile = val;
             } else if (flag == "--seed") {
                 seed = std::stoull(val, nullptr, 0);
                 seedFlag = true;
@@ -153,7 +177,7 @@ int main(int argc, char** argv)
     } catch (const std::exception&) {
         return usage("unreadable flag value");
     }
-    if (engine == "cpu" && deviceFlag) return usage("--gpus / --devices need --engine gpu");
+    if (engine != "gpu" && deviceFlag) return usage("--gpus / --devices need --engine gpu");
     if (rng == "philox" && engine == "cpu") return usage("--rng philox runs on the GPU engine only");
     if (rng == "msvc" && (stopFlag || batchFlag))
         return usage("--stop / --batch apply to --rng philox (GetStatistics keeps the reference stop rule)");
@@ -189,9 +213,14 @@ int main(int argc, char** argv)
             std::cerr << initFile << ": expected 'codeFile w W COUNT MAX p' with COUNT >= 0 and MAX >= 0" << std::endl;
             return 2;
         }
+        std::vector<float> priorX, priorZ;
+        if (!priorsFile.empty()) read_priors(priorsFile, code.n, priorX, priorZ);
         if (rng == "philox") {
-            DecoderGPU decoder(code, devices);
+            std::unique_ptr<DecoderGPU> dp(engine == "sparse" ? new DecoderGPU(code, 0, QEC_ENGINE_SPARSE)
+                                                               : new DecoderGPU(code, devices));
+            DecoderGPU& decoder = *dp;
             if (osd) decoder.SetOsd(osdOrder, osdIterations);
+            if (!priorsFile.empty()) decoder.SetPriors(priorX, priorZ);
             std::cout << "Engine: " << decoder.Describe() << std::endl;
             const int stop = stopName == "ref" ? QEC_STOP_REF : stopName == "fixed" ? QEC_STOP_FIXED : QEC_STOP_SYNDROME;
             std::stringstream fileName;
@@ -214,11 +243,13 @@ int main(int argc, char** argv)
             DecoderCPU* c = new DecoderCPU(code);
             decoder.reset(c);
             if (osd) c->SetOsd(osdOrder, osdIterations);
+            if (!priorsFile.empty()) c->SetPriors(priorX, priorZ);
             std::cout << "Engine: CPU (" << std::thread::hardware_concurrency() << " threads)" << std::endl;
         } else {
-            DecoderGPU* g = new DecoderGPU(code, devices);
+            DecoderGPU* g = engine == "sparse" ? new DecoderGPU(code, 0, QEC_ENGINE_SPARSE) : new DecoderGPU(code, devices);
             decoder.reset(g);
             if (osd) g->SetOsd(osdOrder, osdIterations);
+            if (!priorsFile.empty()) g->SetPriors(priorX, priorZ);
             std::cout << "Engine: " << g->Describe() << std::endl;
         }
         for (; w <= W; ++w) {
