@@ -146,6 +146,10 @@ public:
         check(qec_decoder_set_option(dec_, QEC_OPT_OSD_ITERATIONS, iterations));
         check(qec_decoder_set_option(dec_, QEC_OPT_OSD, order >= 0 ? 1 : 0));
     }
+    // How the combination sweep scores its candidates (QEC_OPT_OSD_SCORE): 0 by Hamming weight (the default),
+    // 1 by likelihood under the priors of SetPriors (the sum of the flipped qubits' integer log-likelihood
+    // weights; without priors the value has no effect).  Any other value throws the library's message.
+    void SetOsdScore(int rule) { check(qec_decoder_set_option(dec_, QEC_OPT_OSD_SCORE, rule)); }
     // Per-qubit priors (qec_decoder_set_priors): priorX[v] / priorZ[v] is the prior that bit v of the X / Z
     // estimate is 1 (n entries each, 0 <= pi <= 1).  While set, BP uses them and the errorProbability argument
     // of Decode, DecodeBatch and GetStatistics is not used.  The sparse-graph engine takes them; a decoder

@@ -292,11 +292,30 @@ int qec_decoder_device(const qec_decoder* dec);         /* HIP device ordinal (o
  *     the checks in LDS: QEC_ERR_UNSUPPORTED if the sum passes one workgroup's 64 KiB.
  *   QEC_OPT_OSD_CS_SECTORS (read only): of the sectors counted by QEC_OPT_OSD_SECTORS, those whose
  *     lightest candidate was not the OSD-0 estimate (index > 0), in the handle's last synchronous call
- *     (saturating; summed over the parts of a group; zeroed and collected where QEC_OPT_OSD_SECTORS is). */
+ *     (saturating; summed over the parts of a group; zeroed and collected where QEC_OPT_OSD_SECTORS is).
+ *   QEC_OPT_OSD_SCORE (default 0; 0 or 1, other values QEC_ERR_ARG): how the combination sweep scores its
+ *     candidates.  0 = Hamming weight, as above.  1 = on a handle with priors
+ *     (qec_decoder_set_priors) the sum, over the qubits a candidate flips, of that qubit's integer weight
+ *     w(pi) = 0 for pi >= 1/2, 4095 for pi = 0, else min(4095, llrint(16 log2((1 - pi) / pi))) (sixteenths
+ *     of a bit of log-likelihood ratio, the float pi taken exactly to double; one table per sector, built by
+ *     qec_decoder_set_priors, read back with qec_decoder_get_osd_weights).  The least score wins, among
+ *     equals the lowest candidate index; candidates, their order, the column order, the pivots, the flags
+ *     and both counters are as under 0 (QEC_OPT_OSD_CS_SECTORS still counts winners of index > 0).  With
+ *     effect wherever the OSD stage runs with lambda > 0 (the synchronous calls under QEC_OPT_OSD = 1,
+ *     qec_osd, qec_osd_dev, which reads it at the call as it reads QEC_OPT_OSD_ORDER); at lambda = 0 there
+ *     is one candidate and the order-0 kernel runs.  On a handle WITHOUT priors the value has no effect:
+ *     every weight would be equal, score = w |e|, so the Hamming kernel runs and the winner is the same.
+ *     The wave-circulant engine cannot hold priors and so never runs the weighted kernel.  A group applies
+ *     the value (and the tables) to every part.  On a GPU handle the weighted sweep keeps 12 more bit
+ *     vectors over the checks and one 16-bit weight per check in LDS: where a code fits at lambda under
+ *     the Hamming score but not with these, the call that would make the weighted sweep run (this option,
+ *     QEC_OPT_OSD_ORDER or qec_decoder_set_priors, whichever comes last) returns QEC_ERR_UNSUPPORTED and
+ *     the text says so.  The result depends only on (code, syndrome, priors, QEC_OPT_OSD_ITERATIONS,
+ *     lambda, this rule). */
 enum { QEC_OPT_HARD_PATHS = 1, QEC_OPT_CYCLE_JUMP = 2, QEC_OPT_SCHEDULE = 3, QEC_OPT_SECTOR_SPLIT = 4,
        QEC_OPT_PHASE_STATS = 5, QEC_OPT_TRIAGE = 6, QEC_OPT_LAST_PATH = 7, QEC_OPT_MC_DECODE_TIME = 8,
        QEC_OPT_OSD = 9, QEC_OPT_OSD_ITERATIONS = 10, QEC_OPT_OSD_SECTORS = 11, QEC_OPT_OSD_SWEEP = 12,
-       QEC_OPT_OSD_ORDER = 13, QEC_OPT_OSD_CS_SECTORS = 14, QEC_OPT_NEAR_HARD_JUMP = 15 };
+       QEC_OPT_OSD_ORDER = 13, QEC_OPT_OSD_CS_SECTORS = 14, QEC_OPT_NEAR_HARD_JUMP = 15, QEC_OPT_OSD_SCORE = 16 };
 enum {
     QEC_PATH_ORDERED = 1,          /* dispatch order pass (schedule.hip) */
     QEC_PATH_SECTOR_ORDER = 2,     /* ... in the per-sector form (each sector's waves by its own weight) */
@@ -342,8 +361,13 @@ int qec_decoder_get_option(const qec_decoder* dec, int option, int* value);
  *   - The near-hard jump (QEC_OPT_NEAR_HARD_JUMP) of the CPU engine never fires while priors are set (its lemma
  *     is stated for one p'); outputs do not depend on the jump either way.
  *   - OSD (QEC_OPT_OSD, QEC_OPT_OSD_ORDER): the soft decode that orders the columns runs with the priors.  The
- *     combination sweep still scores its candidates by plain Hamming weight, NOT by likelihood under the
- *     priors.  The stage's result depends on (code, syndrome, priors, QEC_OPT_OSD_ITERATIONS, lambda) only.
+ *     combination sweep scores its candidates by Hamming weight by default (QEC_OPT_OSD_SCORE = 0) and, with
+ *     QEC_OPT_OSD_SCORE = 1, by likelihood under the priors: the sum of the integer weights w(pi_v) of the
+ *     flipped qubits, least sum first.  Every set rebuilds the two weight tables (and rewrites their device
+ *     copy in place, allocated by the first set as the priors' own buffer is, so qec_osd_dev stays free of
+ *     allocation and synchronisation and a captured graph replayed after a later set scores with the new
+ *     tables).  The stage's result depends on (code, syndrome, priors, QEC_OPT_OSD_ITERATIONS, lambda,
+ *     QEC_OPT_OSD_SCORE) only.
  *   - qec_sample_syndrome_dev and qec_monte_carlo then draw their errors from the independent sampler of
  *     qec_sample_independent_dev (their scalar p is not used), and qec_monte_carlo takes the unfused pipeline
  *     with byte syndromes (sample + syndromes + packed errors, packed decode, OSD stage if on, statistics),
@@ -351,6 +375,10 @@ int qec_decoder_get_option(const qec_decoder* dec, int option, int* value);
 int qec_decoder_set_priors(qec_decoder* dec, const float* priorX, const float* priorZ);
 /* 1 and the arrays filled (n floats each; a NULL array is skipped) if priors are set, 0 if not. */
 int qec_decoder_get_priors(const qec_decoder* dec, float* priorX, float* priorZ);
+/* The combination sweep's weight tables under QEC_OPT_OSD_SCORE = 1 (built by qec_decoder_set_priors whatever
+ * the option's value): 1 and the arrays filled (n entries each, 0 .. 4095; a NULL array is skipped) if
+ * priors are set, 0 if not. */
+int qec_decoder_get_osd_weights(const qec_decoder* dec, int32_t* wX, int32_t* wZ);
 /* which kernel variant serves this code: writes a short name (e.g. "wave-circulant P=61 G=1") */
 int qec_decoder_describe(const qec_decoder* dec, char* buf, size_t len);
 

@@ -28,7 +28,7 @@ STOP = {"ref": 0, "fixed": 1, "syndrome": 2}
 ENGINE = {"auto": 0, "circulant": 1, "sparse": 2, "cpu": 3}
 OPTION = {"hard_paths": 1, "cycle_jump": 2, "schedule": 3, "sector_split": 4, "phase_stats": 5, "triage": 6,
           "last_path": 7, "mc_decode_time": 8, "osd": 9, "osd_iterations": 10, "osd_sectors": 11,
-          "osd_sweep": 12, "osd_order": 13, "osd_cs_sectors": 14, "near_hard": 15}
+          "osd_sweep": 12, "osd_order": 13, "osd_cs_sectors": 14, "near_hard": 15, "osd_score": 16}
 OPTIONS = OPTION
 # QEC_PATH_* bits of QEC_OPT_LAST_PATH (include/qec_ldpc.h): the launch sequence of the last decode call
 PATH = {"ordered": 1, "sector_order": 2, "split_waves": 4, "sector_launches": 8, "triage": 16, "bit_rows": 32,
@@ -44,7 +44,7 @@ EXPORTS = (
     "qec_decoder_create", "qec_decoder_create_engine", "qec_decoder_create_multi", "qec_decoder_destroy",
     "qec_decoder_num_parts", "qec_decoder_part", "qec_decoder_device", "qec_decoder_describe",
     "qec_decoder_set_option", "qec_decoder_get_option", "qec_near_hard_threshold",
-    "qec_decoder_set_priors", "qec_decoder_get_priors", "qec_sample_independent_dev",
+    "qec_decoder_set_priors", "qec_decoder_get_priors", "qec_decoder_get_osd_weights", "qec_sample_independent_dev",
     "qec_decode_batch", "qec_decode_batch_dev", "qec_decode_batch_packed", "qec_decode_batch_packed_dev",
     "qec_decode_bits_packed_dev",
     "qec_sample_fixed_weight", "qec_get_statistics",
@@ -144,6 +144,7 @@ def lib():
             "qec_near_hard_threshold": (i, [f, i, i, vp, vp]),
             "qec_decoder_set_priors": (i, [vp, vp, vp]),
             "qec_decoder_get_priors": (i, [vp, vp, vp]),
+            "qec_decoder_get_osd_weights": (i, [vp, vp, vp]),
             "qec_sample_independent_dev": (i, [vp, ctypes.c_uint64, ctypes.c_uint64, sz, vp, vp, vp]),
             "qec_decode_batch": (i, [vp, vp, vp, sz, f, i, i, vp, vp, vp, vp, vp]),
             "qec_decode_batch_dev": (i, [vp, vp, vp, sz, f, i, i, vp, vp, vp, vp, vp, vp]),
@@ -447,7 +448,9 @@ class DecoderGPU:
         set_priors(None, None) clears them.  While set, BP uses them in place of p' = (2/3) p and the `p`
         argument of every decode call, GetStatistics, sample_syndrome_dev and monte_carlo is not used (the
         latter two draw sample_independent_dev's errors).  Sparse-graph and CPU engines; a wave-circulant
-        decoder refuses (create it with engine="sparse").  OSD-CS still scores by Hamming weight."""
+        decoder refuses (create it with engine="sparse").  OSD-CS scores its candidates by Hamming weight
+        unless set_option("osd_score", 1) asks for the prior-weighted score; every set rebuilds the weight
+        tables that score reads (osd_weights)."""
         if (priorX is None) != (priorZ is None):
             raise QecError("set_priors: priorX and priorZ must both be given, or both be None (clear)")
         if priorX is None:
@@ -472,6 +475,17 @@ class DecoderGPU:
         if rc < 0:
             raise QecError("qec_decoder_get_priors failed (%d): %s" % (rc, last_error()))
         return (pX, pZ) if rc == 1 else None
+
+    def osd_weights(self):
+        """(wX, wZ) as int32 arrays (qec_decoder_get_osd_weights): the integer weights, 0 .. 4095 in
+        sixteenths of a bit of log-likelihood ratio, that OSD-CS sums over a candidate's flips under
+        set_option("osd_score", 1); None when no priors are set."""
+        wX = np.empty(self.code.n, dtype=np.int32)
+        wZ = np.empty(self.code.n, dtype=np.int32)
+        rc = lib().qec_decoder_get_osd_weights(self._h, _ptr(wX), _ptr(wZ))
+        if rc < 0:
+            raise QecError("qec_decoder_get_osd_weights failed (%d): %s" % (rc, last_error()))
+        return (wX, wZ) if rc == 1 else None
 
     def last_path(self):
         """The launch sequence of this handle's last decode call (QEC_OPT_LAST_PATH) as a set of
@@ -519,7 +533,9 @@ class DecoderGPU:
         Returns repaired copies (eX, eZ, flags); sectors without their SYNDROME_FAIL bit are untouched.
         set_option("osd_order", lam) chooses OSD-0 (0, the default) or the combination sweep OSD-CS over
         the lam <= 64 most suspicious non-pivot columns; get_option("osd_sectors") / ("osd_cs_sectors")
-        then give the sectors repaired and those whose lightest candidate was not the OSD-0 estimate."""
+        then give the sectors repaired and those whose lightest candidate was not the OSD-0 estimate.
+        With priors set, set_option("osd_score", 1) makes the sweep pick the candidate of least
+        prior-weighted score (osd_weights) instead of the lightest; the default 0 is Hamming weight."""
         c = self.code
         sX = np.atleast_2d(sX)
         B = sX.shape[0]
@@ -636,7 +652,8 @@ class DecoderGPU:
         """OSD (qec_osd_dev) in place on a decoded device batch: repairs the sectors of eX / eZ whose
         SYNDROME_FAIL bit is set in flags from the soft input q (decode_batch_dev's q layout) and clears
         the bit.  The handle's "osd_order" option (read at the call) chooses OSD-0 or the combination
-        sweep.  Async on `stream`; no allocation (graph-capturable); updates neither "osd_sectors" nor
+        sweep, and "osd_score" (read at the call too) whether, with priors set, the sweep scores by the
+        prior-weighted sum (1) or by Hamming weight (0, the default).  Async on `stream`; no allocation (graph-capturable); updates neither "osd_sectors" nor
         "osd_cs_sectors"."""
         import torch
         self._single("osd_dev")

@@ -92,11 +92,12 @@ int launch_pack_decisions(const uint8_t* eX, const uint8_t* eZ, const uint8_t* f
 int launch_statistics(const Code& c, const uint64_t* imp_cols, const uint8_t* x, const uint8_t* z, const uint8_t* eX,
                       const uint8_t* eZ, const uint8_t* flags, long long B, unsigned long long* counters, hipStream_t st);
 struct OsdDevPlan;
-std::string osd_dev_unsupported(const OsdPlan& P, int order);
+std::string osd_dev_unsupported(const OsdPlan& P, int order, bool weighted);
 OsdDevPlan* osd_dev_create(const OsdPlan& P);
 void osd_dev_free(OsdDevPlan* D);
 int launch_osd(const OsdDevPlan* D, int sweep, int order, const uint8_t* sX, const uint8_t* sZ, long long B, const float* q,
-               uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint32_t* repaired, uint32_t* swept, hipStream_t st);
+               uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint32_t* repaired, uint32_t* swept, const int32_t* w,
+               hipStream_t st);
 int launch_osd_collect(const uint8_t* rec, int rstride, int n, long long B, int32_t* list, uint32_t* count,
                        hipStream_t st);
 int launch_osd_gather(const int32_t* list, long long cnt, const uint8_t* sX, const uint8_t* sZ, bool bits, int mX,
@@ -162,6 +163,15 @@ struct qec_decoder {
     DeviceArray<float> dpri;
     const float* prior_host() const { return has_priors ? priors.data() : nullptr; }
     const float* prior_dev() const { return has_priors ? dpri.data() : nullptr; }
+    // QEC_OPT_OSD_SCORE: the rule, and the sweep's weight tables (sector X [n], then Z [n]), rebuilt by
+    // every qec_decoder_set_priors; the device copy is allocated and rewritten as dpri is.  The sweep takes
+    // the tables only with the rule at 1 and priors set (else the pointers are null: Hamming weight)
+    int osd_score = 0;
+    std::vector<int32_t> osw;
+    DeviceArray<int32_t> dosw;
+    bool osd_weighted() const { return osd_score == 1 && has_priors; }
+    const int32_t* osw_host() const { return osd_weighted() ? osw.data() : nullptr; }
+    const int32_t* osw_dev() const { return osd_weighted() ? dosw.data() : nullptr; }
     // OSD stage: the elimination tables (host; device copy for the GPU engines), the compact
     // batch of failed samples (syndromes, estimates, flags, soft output) and the failed-record list
     std::shared_ptr<const OsdPlan> oplan;
@@ -529,7 +539,7 @@ qec_decoder* qec_decoder_create_engine(const qec_code* h, int device, size_t max
         auto op = std::make_shared<OsdPlan>();
         osd_plan_build(*d->code, *op);
         d->oplan = op;
-        d->osd_why = osd_dev_unsupported(*op, 0);
+        d->osd_why = osd_dev_unsupported(*op, 0, false);
         if (d->osd_why.empty()) {
             d->odev = osd_dev_create(*op);
             if (!d->odev) return nullptr;
@@ -665,10 +675,19 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
     case QEC_OPT_OSD_ORDER:
         if (value < 0 || value > kOsdMaxOrder) return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD_ORDER is 0 .. 64");
         if (value && d->odev) {  // the sweep's column vectors share the workgroup's LDS with [H | s]
-            const std::string why = osd_dev_unsupported(*d->oplan, value);
+            const std::string why = osd_dev_unsupported(*d->oplan, value, d->osd_weighted());
             if (!why.empty()) return fail(QEC_ERR_UNSUPPORTED, why);
         }
         d->osd_order = value;
+        return QEC_OK;
+    case QEC_OPT_OSD_SCORE:
+        if (value != 0 && value != 1)
+            return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD_SCORE is 0 (Hamming weight) or 1 (prior-weighted)");
+        if (value && d->odev && d->has_priors && d->osd_order > 0) {  // the weighted sweep's arrays need LDS of their own
+            const std::string why = osd_dev_unsupported(*d->oplan, d->osd_order, true);
+            if (!why.empty()) return fail(QEC_ERR_UNSUPPORTED, why);
+        }
+        d->osd_score = value;
         return QEC_OK;
     case QEC_OPT_OSD_CS_SECTORS:
         return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD_CS_SECTORS is read only");
@@ -699,9 +718,15 @@ int qec_decoder_set_priors(qec_decoder* d, const float* priorX, const float* pri
                 return fail(QEC_ERR_ARG, std::string("qec_decoder_set_priors: prior") + (sec ? "Z[" : "X[") + std::to_string(v) +
                                              "] = " + std::to_string(pr[v]) + " is not in [0, 1]");
     }
+    if (d->odev && d->osd_score == 1 && d->osd_order > 0) {  // the weighted sweep would run from here on
+        const std::string why = osd_dev_unsupported(*d->oplan, d->osd_order, true);
+        if (!why.empty()) return fail(QEC_ERR_UNSUPPORTED, why);
+    }
     std::vector<float> host(2 * (size_t)n);
     std::memcpy(host.data(), priorX, n * sizeof(float));
     std::memcpy(host.data() + n, priorZ, n * sizeof(float));
+    std::vector<int32_t> wts(host.size());  // the sweep's weight tables (QEC_OPT_OSD_SCORE = 1)
+    for (size_t i = 0; i < host.size(); ++i) wts[i] = osd_weight(host[i]);
     for (qec_decoder* p : d->parts) {
         const int rc = qec_decoder_set_priors(p, priorX, priorZ);
         if (rc) return rc;
@@ -713,12 +738,15 @@ int qec_decoder_set_priors(qec_decoder* d, const float* priorX, const float* pri
         if (d->ws_used) QEC_HIP_CHECK(hipEventSynchronize(d->ws_ev));
         try {
             d->dpri.reserve(host.size());
+            d->dosw.reserve(wts.size());
         } catch (const std::exception& ex) {
             return fail(QEC_ERR_NOMEM, std::string("qec_decoder_set_priors: ") + ex.what());
         }
         QEC_HIP_CHECK(hipMemcpy(d->dpri.data(), host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+        QEC_HIP_CHECK(hipMemcpy(d->dosw.data(), wts.data(), wts.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     d->priors.swap(host);
+    d->osw.swap(wts);
     d->has_priors = true;
     return QEC_OK;
 }
@@ -730,6 +758,16 @@ int qec_decoder_get_priors(const qec_decoder* d, float* priorX, float* priorZ)
     const int n = d->code->n;
     if (priorX) std::memcpy(priorX, d->priors.data(), n * sizeof(float));
     if (priorZ) std::memcpy(priorZ, d->priors.data() + n, n * sizeof(float));
+    return 1;
+}
+
+int qec_decoder_get_osd_weights(const qec_decoder* d, int32_t* wX, int32_t* wZ)
+{
+    if (!d) return fail(QEC_ERR_ARG, "qec_decoder_get_osd_weights: null decoder");
+    if (!d->has_priors) return 0;
+    const int n = d->code->n;
+    if (wX) std::memcpy(wX, d->osw.data(), n * sizeof(int32_t));
+    if (wZ) std::memcpy(wZ, d->osw.data() + n, n * sizeof(int32_t));
     return 1;
 }
 
@@ -756,6 +794,7 @@ int qec_decoder_get_option(const qec_decoder* d, int option, int* value)
         return QEC_OK;
     }
     case QEC_OPT_OSD_ORDER: *value = d->osd_order; return QEC_OK;
+    case QEC_OPT_OSD_SCORE: *value = d->osd_score; return QEC_OK;
     case QEC_OPT_OSD_CS_SECTORS: {
         unsigned long long t = d->osd_cs_sectors;
         for (const qec_decoder* p : d->parts) t += p->osd_cs_sectors;
@@ -969,7 +1008,7 @@ int osd_compact_dev(qec_decoder* d, long long cnt, float p, bool count, hipStrea
     d->last_path = path;
     if (rc) return rc;
     return launch_osd(d->odev, d->osd_sweep, d->osd_order, d->osX.data(), d->osZ.data(), cnt, d->oq.data(), d->oeX.data(),
-                      d->oeZ.data(), d->ofl.data(), count ? d->ocnt.data() + 1 : nullptr, d->ocnt.data() + 2, st);
+                      d->oeZ.data(), d->ofl.data(), count ? d->ocnt.data() + 1 : nullptr, d->ocnt.data() + 2, d->osw_dev(), st);
 }
 
 // The whole stage on a decoded host batch of one single-device handle (byte form, or records): find
@@ -1007,7 +1046,7 @@ int osd_repair_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t
             if (rc) return rc;
             long long swept = 0;
             osd_host_batch(*d->oplan, cX.data(), cZ.data(), (long long)cnt, cq.data(), cEX.data(), cEZ.data(), cF.data(), 0,
-                           d->osd_order, &swept);
+                           d->osd_order, &swept, d->osw_host());
             d->osd_cs_sectors += (unsigned long long)swept;
         } else {
             hipStream_t st = d->stream;
@@ -1789,7 +1828,7 @@ int qec_osd_dev(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
     QEC_DEVICE_SCOPE(d->device);
     // the kernel reads only the handle's tables: no workspace, no allocation, nothing to order
     return launch_osd(d->odev, d->osd_sweep, d->osd_order, sX, sZ, (long long)B, q, eX, eZ, flags, nullptr, nullptr,
-                      static_cast<hipStream_t>(stream));
+                      d->osw_dev(), static_cast<hipStream_t>(stream));
 }
 
 int qec_osd(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, const float* q, uint8_t* eX, uint8_t* eZ,
@@ -1802,7 +1841,7 @@ int qec_osd(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, cons
     if (d->cpu) {
         long long swept = 0;
         d->osd_sectors = (unsigned long long)osd_host_batch(*d->oplan, sX, sZ, (long long)B, q, eX, eZ, flags, 0,
-                                                            d->osd_order, &swept);
+                                                            d->osd_order, &swept, d->osw_host());
         d->osd_cs_sectors = (unsigned long long)swept;
         return QEC_OK;
     }
@@ -1825,7 +1864,7 @@ int qec_osd(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, cons
         QEC_HIP_CHECK(hipMemcpyAsync(dq.data(), q, B * qn * sizeof(float), hipMemcpyHostToDevice, st));
         QEC_HIP_CHECK(hipMemsetAsync(w->ocnt.data() + 2, 0, sizeof(uint32_t), st));
         const int rc = launch_osd(w->odev, w->osd_sweep, w->osd_order, dsX.data(), dsZ.data(), (long long)B, dq.data(),
-                                  deX.data(), deZ.data(), dfl.data(), nullptr, w->ocnt.data() + 2, st);
+                                  deX.data(), deZ.data(), dfl.data(), nullptr, w->ocnt.data() + 2, w->osw_dev(), st);
         if (rc) return rc;
         QEC_HIP_CHECK(hipMemcpyAsync(&swept, w->ocnt.data() + 2, sizeof swept, hipMemcpyDeviceToHost, st));
         QEC_HIP_CHECK(hipMemcpyAsync(eX, deX.data(), B * c.n, hipMemcpyDeviceToHost, st));

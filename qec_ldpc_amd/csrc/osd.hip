@@ -59,11 +59,14 @@ __host__ __device__ inline int osd_rws(int mmax) { return (2 * ((mmax + 63) >> 6
 // LDS image of one wave (32-bit words): rows [mmax][Ws] | keys [n] (later the estimate's bytes [n]
 // and, for the sweep, T [n] u16 behind them: ceil(n / 4) + ceil(n / 2) <= n words for n >= 2) |
 // order [n] u16 | pivcol [mmax] u16 | for lambda > 0 the bit vectors of the first lambda columns of T
-// and of s': [lambda + 1][RWs]
-__host__ __device__ inline uint32_t osd_lds_words(int mmax, int n, int Ws, int order)
+// and of s': [lambda + 1][RWs] | for the weighted sweep (section 1.4) the bit-planes of the rows'
+// weights [kOsdPlanes][RWs] and the weights themselves, wp [mmax] u16
+constexpr int kOsdPlanes = 12;  // bits of a weight (kOsdMaxWeight = 4095)
+__host__ __device__ inline uint32_t osd_lds_words(int mmax, int n, int Ws, int order, bool weighted = false)
 {
     return (uint32_t)mmax * Ws + n + (n + 1) / 2 + (mmax + 1) / 2 +
-           (order > 0 ? (uint32_t)(order + 1) * osd_rws(mmax) : 0u);
+           (order > 0 ? (uint32_t)(order + 1) * osd_rws(mmax) : 0u) +
+           (order > 0 && weighted ? (uint32_t)kOsdPlanes * osd_rws(mmax) + (mmax + 1) / 2 : 0u);
 }
 
 // Block t: sample t / 2, sector t % 2.  A sector without its SYNDROME_FAIL bit exits at once, so the
@@ -73,14 +76,17 @@ __host__ __device__ inline uint32_t osd_lds_words(int mmax, int n, int Ws, int o
 // whose lightest candidate is not the OSD-0 estimate.
 // The kernel itself is the template (osd_kernel<false> is the order-0 kernel, instruction for
 // instruction what it was before the sweep existed: a shared body inlined into two kernels compiled
-// to a slower elimination loop).
-template <bool CS>
+// to a slower elimination loop).  WEIGHTED (with CS): the sweep scores a candidate by the sum of
+// wt[v] over its flips (section 1.4; wt = the two sectors' tables, [2][n]) instead of their number;
+// the other two instantiations never read wt.
+template <bool CS, bool WEIGHTED = false>
 __global__ __launch_bounds__(64) void osd_kernel(OsdDev P, const uint8_t* __restrict__ sX,
                                                  const uint8_t* __restrict__ sZ, long long B,
                                                  const float* __restrict__ q, uint8_t* __restrict__ eX,
                                                  uint8_t* __restrict__ eZ, uint8_t* flags, uint32_t* repaired,
-                                                 OsdCs C, uint32_t* swept)
+                                                 OsdCs C, uint32_t* swept, const int32_t* __restrict__ wt)
 {
+    static_assert(CS || !WEIGHTED, "the weighted score belongs to the sweep");
     extern __shared__ uint32_t lds[];
     const long long b = (long long)(blockIdx.x >> 1);
     const int sec = (int)(blockIdx.x & 1u);
@@ -235,46 +241,125 @@ __global__ __launch_bounds__(64) void osd_kernel(OsdDev P, const uint8_t* __rest
             }
         }
         wave_sync();
-        // packed (weight, index): weights <= rank + 2 <= 2050, indices < 1 + 2048 + 2016 < 2^12
-        uint32_t best = (uint32_t)w0 << 12;
-        // singles, lanes across the columns of T: flipping t changes the weight by one for t itself, by
-        // +1 for each row with R[r][t] = 1 and s'[r] = 0, by -1 for each with s'[r] = 1
-        for (int j0 = 0; j0 < f; j0 += 64) {
-            const int j = j0 + lane;
-            const int v = j < f ? T[j] : 0;
-            const int w = v >> 5, sh = v & 31;
-            int d = 0;
-            for (int x = 0; x < RW; ++x) {
-                const uint32_t sword = sv[x];  // a broadcast
-                const int r0 = x << 5;
-                const int r1 = r0 + 32 < m ? r0 + 32 : m;
-                for (int r = r0; r < r1; ++r) {
-                    const int cb = (int)((rows[r * Ws + w] >> sh) & 1u);
-                    d += cb - 2 * (cb & (int)((sword >> (r - r0)) & 1u));
+        int idx;
+        if constexpr (WEIGHTED) {
+            // section 1.4: wp[r] = the weight of row r's pivot column (0 without a pivot), and its bit-planes
+            // stored as s' is: plane q holds bit q of every row's weight, so that the weight of a bit vector x
+            // over the rows is the sum over q of 2^q popc(x & plane q).  Only the planes up to the highest
+            // set bit of any weight are built and read (nq, wave-uniform).
+            const int32_t* wsec = wt + (size_t)sec * n;
+            uint32_t* pl = sv + RWs;
+            uint16_t* wp = reinterpret_cast<uint16_t*>(pl + kOsdPlanes * RWs);
+            uint32_t s0 = 0, wor = 0;  // this lane's share of the OSD-0 estimate's score; OR of its rows' weights
+            for (int k = 0; k < nchunk; ++k) {
+                const int r = (k << 6) + lane;
+                const bool piv = r < m && ((used >> k) & 1u);
+                const uint32_t wr = piv ? (uint32_t)wsec[pivcol[r]] : 0u;
+                if (r < m) wp[r] = (uint16_t)wr;
+                if (piv && (rows[r * Ws + sw] & sbit)) s0 += wr;
+                wor |= wr;
+                for (int q = 0; q < kOsdPlanes; ++q) {
+                    const unsigned long long bal = __ballot((wr >> q) & 1u);
+                    if (lane < 2) pl[q * RWs + 2 * k + lane] = (uint32_t)(bal >> (32 * lane));
                 }
             }
-            if (j < f) {
-                const uint32_t c = ((uint32_t)(w0 + 1 + d) << 12) | (uint32_t)(1 + j);
-                best = c < best ? c : best;
+            for (int o = 32; o; o >>= 1) {
+                s0 += (uint32_t)__shfl_xor((int)s0, o);
+                wor |= (uint32_t)__shfl_xor((int)wor, o);
             }
-        }
-        // pairs {t_i, t_j}, i < j < lam <= 64: a wave-uniform loop over i, lanes across j
-        int pidx = 1 + f;  // index of the pair (i, i + 1)
-        for (int i = 0; i + 1 < lam; ++i) {
-            const int j = i + 1 + lane;
-            if (j < lam) {
-                int wt = 2;
-                for (int x = 0; x < RW; ++x) wt += __popc(cv[i * RWs + x] ^ sv[x] ^ cv[j * RWs + x]);
-                const uint32_t c = ((uint32_t)wt << 12) | (uint32_t)(pidx + lane);
-                best = c < best ? c : best;
+            const int nq = 32 - __clz(wor);  // __clz(0) = 32: no plane at all
+            wave_sync();
+            // (score, index) keys: scores <= (rank + 2) 4095 < 2^23, indices < 2^12
+            unsigned long long best = (unsigned long long)s0 << 12;
+            // singles: flipping t adds its own weight, and wp[r] for each row with R[r][t] = 1 and s'[r] = 0,
+            // and takes wp[r] away for each with s'[r] = 1
+            for (int j0 = 0; j0 < f; j0 += 64) {
+                const int j = j0 + lane;
+                const int v = j < f ? T[j] : 0;
+                const int w = v >> 5, sh = v & 31;
+                int d = 0;
+                for (int x = 0; x < RW; ++x) {
+                    const uint32_t sword = sv[x];  // a broadcast
+                    const int r0 = x << 5;
+                    const int r1 = r0 + 32 < m ? r0 + 32 : m;
+                    for (int r = r0; r < r1; ++r) {
+                        const int cb = (int)((rows[r * Ws + w] >> sh) & 1u);
+                        const int wr = (int)wp[r];  // a broadcast
+                        d += cb * (((sword >> (r - r0)) & 1u) ? -wr : wr);
+                    }
+                }
+                if (j < f) {
+                    const unsigned long long c =
+                        ((unsigned long long)(uint32_t)((int)s0 + wsec[v] + d) << 12) | (unsigned long long)(1 + j);
+                    best = c < best ? c : best;
+                }
             }
-            pidx += lam - 1 - i;
+            // pairs, as below, the popcount taken plane by plane.  w[t_i] and w[t_j] come from the table in
+            // global memory (232 B per sector here, cache hits): keeping them in a register per lane and
+            // shuffling measured slower inside qec_monte_carlo
+            int pidx = 1 + f;
+            for (int i = 0; i + 1 < lam; ++i) {
+                const int j = i + 1 + lane;
+                if (j < lam) {
+                    uint32_t sc = (uint32_t)(wsec[T[i]] + wsec[T[j]]);
+                    for (int x = 0; x < RW; ++x) {
+                        const uint32_t xv = cv[i * RWs + x] ^ sv[x] ^ cv[j * RWs + x];
+                        for (int q = 0; q < nq; ++q) sc += (uint32_t)__popc(xv & pl[q * RWs + x]) << q;
+                    }
+                    const unsigned long long c = ((unsigned long long)sc << 12) | (unsigned long long)(pidx + lane);
+                    best = c < best ? c : best;
+                }
+                pidx += lam - 1 - i;
+            }
+            for (int o = 32; o; o >>= 1) {
+                const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)best, o);
+                const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(best >> 32), o);
+                const unsigned long long other = ((unsigned long long)hi << 32) | lo;
+                best = other < best ? other : best;
+            }
+            idx = (int)(best & 0xFFFull);
+        } else {
+            // packed (weight, index): weights <= rank + 2 <= 2050, indices < 1 + 2048 + 2016 < 2^12
+            uint32_t best = (uint32_t)w0 << 12;
+            // singles, lanes across the columns of T: flipping t changes the weight by one for t itself, by
+            // +1 for each row with R[r][t] = 1 and s'[r] = 0, by -1 for each with s'[r] = 1
+            for (int j0 = 0; j0 < f; j0 += 64) {
+                const int j = j0 + lane;
+                const int v = j < f ? T[j] : 0;
+                const int w = v >> 5, sh = v & 31;
+                int d = 0;
+                for (int x = 0; x < RW; ++x) {
+                    const uint32_t sword = sv[x];  // a broadcast
+                    const int r0 = x << 5;
+                    const int r1 = r0 + 32 < m ? r0 + 32 : m;
+                    for (int r = r0; r < r1; ++r) {
+                        const int cb = (int)((rows[r * Ws + w] >> sh) & 1u);
+                        d += cb - 2 * (cb & (int)((sword >> (r - r0)) & 1u));
+                    }
+                }
+                if (j < f) {
+                    const uint32_t c = ((uint32_t)(w0 + 1 + d) << 12) | (uint32_t)(1 + j);
+                    best = c < best ? c : best;
+                }
+            }
+            // pairs {t_i, t_j}, i < j < lam <= 64: a wave-uniform loop over i, lanes across j
+            int pidx = 1 + f;  // index of the pair (i, i + 1)
+            for (int i = 0; i + 1 < lam; ++i) {
+                const int j = i + 1 + lane;
+                if (j < lam) {
+                    int wt = 2;
+                    for (int x = 0; x < RW; ++x) wt += __popc(cv[i * RWs + x] ^ sv[x] ^ cv[j * RWs + x]);
+                    const uint32_t c = ((uint32_t)wt << 12) | (uint32_t)(pidx + lane);
+                    best = c < best ? c : best;
+                }
+                pidx += lam - 1 - i;
+            }
+            for (int o = 32; o; o >>= 1) {
+                const uint32_t other = (uint32_t)__shfl_xor((int)best, o);
+                best = other < best ? other : best;
+            }
+            idx = (int)(best & 0xFFFu);
         }
-        for (int o = 32; o; o >>= 1) {
-            const uint32_t other = (uint32_t)__shfl_xor((int)best, o);
-            best = other < best ? other : best;
-        }
-        const int idx = (int)(best & 0xFFFu);
         if (idx > 0 && idx <= f) {
             fa = T[idx - 1];
         } else if (idx > f) {
@@ -385,7 +470,7 @@ __global__ void osd_scatter_kernel(const int32_t* __restrict__ list, long long c
 
 // ---- host side ----------------------------------------------------------------------------------
 // Why this code cannot take the kernel at QEC_OPT_OSD_ORDER = order (empty: it can).
-std::string osd_dev_unsupported(const OsdPlan& P, int order)
+std::string osd_dev_unsupported(const OsdPlan& P, int order, bool weighted)
 {
     const int n = P.sec[0].n, mmax = std::max(P.sec[0].m, P.sec[1].m);
     if (n > kOsdMaxN || mmax > kOsdMaxN)
@@ -393,10 +478,15 @@ std::string osd_dev_unsupported(const OsdPlan& P, int order)
                std::to_string(kOsdMaxN) + " of each";
     if (order > 0 && n < 2) return "OSD: the combination sweep takes codes of n >= 2";
     const int W = P.sec[0].W;
-    const size_t bytes = 4 * (size_t)osd_lds_words(mmax, n, W | 1, order);
-    if (bytes > kOsdMaxLds)
+    const size_t bytes = 4 * (size_t)osd_lds_words(mmax, n, W | 1, order, weighted);
+    if (bytes > kOsdMaxLds) {
+        if (order > 0 && weighted && 4 * (size_t)osd_lds_words(mmax, n, W | 1, order) <= kOsdMaxLds)
+            return "OSD: the sweep fits in LDS at QEC_OPT_OSD_ORDER = " + std::to_string(order) +
+                   " under the Hamming score, but not with the weighted score's arrays (QEC_OPT_OSD_SCORE = 1 with priors): " +
+                   std::to_string(bytes) + " B, one workgroup has " + std::to_string(kOsdMaxLds);
         return "OSD: the augmented matrix" + std::string(order > 0 ? " and the sweep's column vectors need " : " needs ") +
                std::to_string(bytes) + " B of LDS, one workgroup has " + std::to_string(kOsdMaxLds);
+    }
     return std::string();
 }
 
@@ -448,7 +538,7 @@ void osd_dev_free(OsdDevPlan* D)
 
 int launch_osd(const OsdDevPlan* D, int sweep, int order, const uint8_t* sX, const uint8_t* sZ, long long B,
                const float* q, uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint32_t* repaired, uint32_t* swept,
-               hipStream_t st)
+               const int32_t* w, hipStream_t st)
 {
     if (B <= 0) return QEC_OK;
     if (B >= (1LL << 30)) return fail(QEC_ERR_ARG, "OSD: batch too large");
@@ -456,16 +546,23 @@ int launch_osd(const OsdDevPlan* D, int sweep, int order, const uint8_t* sX, con
     P.sweep = sweep;
     if (order <= 0) {
         hipLaunchKernelGGL(osd_kernel<false>, dim3((unsigned)(2 * B)), dim3(64), D->lds_bytes, st, P, sX, sZ, B, q, eX,
-                           eZ, flags, repaired, OsdCs{}, nullptr);
+                           eZ, flags, repaired, OsdCs{}, nullptr, nullptr);
         return launch_check("osd0");
     }
     // the sweep's column vectors behind the elimination's image (QEC_OPT_OSD_ORDER is refused where
     // the sum does not fit: osd_dev_unsupported)
-    const uint32_t lds = 4 * osd_lds_words(D->mmax, P.n, P.Ws, order);
-    if (order > kOsdMaxOrder || lds > kOsdMaxLds) return fail(QEC_ERR_UNSUPPORTED, "OSD: the sweep does not fit in LDS");
+    const uint32_t lds = 4 * osd_lds_words(D->mmax, P.n, P.Ws, order, w != nullptr);
+    if (order > kOsdMaxOrder || lds > kOsdMaxLds)
+        return fail(QEC_ERR_UNSUPPORTED, w ? "OSD: the sweep with the weighted score's arrays does not fit in LDS"
+                                           : "OSD: the sweep does not fit in LDS");
     const OsdCs C{order, osd_rws(D->mmax)};
+    if (w) {  // QEC_OPT_OSD_SCORE = 1 with priors set: the weight tables [2][n]
+        hipLaunchKernelGGL((osd_kernel<true, true>), dim3((unsigned)(2 * B)), dim3(64), lds, st, P, sX, sZ, B, q, eX, eZ,
+                           flags, repaired, C, swept, w);
+        return launch_check("osd_cs_weighted");
+    }
     hipLaunchKernelGGL(osd_kernel<true>, dim3((unsigned)(2 * B)), dim3(64), lds, st, P, sX, sZ, B, q, eX, eZ, flags,
-                       repaired, C, swept);
+                       repaired, C, swept, nullptr);
     return launch_check("osd_cs");
 }
 

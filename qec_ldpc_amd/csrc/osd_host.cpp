@@ -2,6 +2,7 @@
 // post-processing stage and the in-library cross-check of the kernel (osd.hip).  Plain C++ on
 // bit-packed rows; no GPU.
 #include <algorithm>
+#include <cmath>
 #include <thread>
 
 #include "qec_osd.h"
@@ -56,7 +57,16 @@ void osd_plan_build(const Code& c, OsdPlan& out)
     build_sector(c.pcmZ, c.mZ, c.n, L, (size_t)c.mX * L, out.sec[1]);
 }
 
-bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8_t* e, int order_cs, bool* swept)
+int32_t osd_weight(float prior)
+{
+    const double pi = (double)prior;
+    if (pi >= 0.5) return 0;
+    if (pi == 0.0) return kOsdMaxWeight;
+    return (int32_t)std::min<long long>(kOsdMaxWeight, std::llrint(16.0 * std::log2((1.0 - pi) / pi)));
+}
+
+bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8_t* e, int order_cs, bool* swept,
+                     const int32_t* wt_tab)
 {
     if (swept) *swept = false;
     const int m = S.m, n = S.n, W = S.W;
@@ -100,6 +110,7 @@ bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8
         if (pivcol[c] < 0 && (A[(size_t)c * W + sw] & sbit)) return false;
     // section 1.3: T = the non-pivot columns in the walk's order; a candidate flips a set F of them, and
     // its weight is |F| plus the pivot rows whose s' bit, XOR their bits in the columns of F, is set
+    // (section 1.4, with a weight table: each flip counts its qubit's weight instead of one)
     int F[2] = {-1, -1};
     if (order_cs > 0) {
         std::vector<uint8_t> is_piv(n, 0);
@@ -111,13 +122,14 @@ bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8
         const int f = (int)T.size(), lam = std::min(order_cs, f);
         auto bit_at = [&](int c, int v) { return (A[(size_t)c * W + (v >> 5)] >> (v & 31)) & 1u; };
         auto weight = [&](int a, int b) {
-            int wt = (a >= 0) + (b >= 0);
+            auto cost = [&](int v) { return wt_tab ? (int)wt_tab[v] : 1; };
+            int wt = (a >= 0 ? cost(a) : 0) + (b >= 0 ? cost(b) : 0);
             for (int c = 0; c < m; ++c) {
                 if (pivcol[c] < 0) continue;
                 uint32_t x = bit_at(c, n);
                 if (a >= 0) x ^= bit_at(c, a);
                 if (b >= 0) x ^= bit_at(c, b);
-                wt += (int)x;
+                if (x) wt += cost(pivcol[c]);
             }
             return wt;
         };
@@ -147,7 +159,8 @@ bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8
 }
 
 long long osd_host_batch(const OsdPlan& P, const uint8_t* sX, const uint8_t* sZ, long long B, const float* q,
-                         uint8_t* eX, uint8_t* eZ, uint8_t* flags, int threads, int order, long long* swept)
+                         uint8_t* eX, uint8_t* eZ, uint8_t* flags, int threads, int order, long long* swept,
+                         const int32_t* w)
 {
     if (swept) *swept = 0;
     if (B <= 0) return 0;
@@ -165,7 +178,8 @@ long long osd_host_batch(const OsdPlan& P, const uint8_t* sX, const uint8_t* sZ,
                 const OsdSector& S = P.sec[sec];
                 bool sw = false;
                 if (osd_host_sector(S, q + (size_t)b * P.qn, (sec ? sZ : sX) + (size_t)b * S.m,
-                                    (sec ? eZ : eX) + (size_t)b * S.n, order, &sw)) {
+                                    (sec ? eZ : eX) + (size_t)b * S.n, order, &sw,
+                                    w ? w + (size_t)sec * S.n : nullptr)) {
                     flags[b] &= (uint8_t)~fbit;
                     ++fixed[t];
                     cs[t] += sw;

@@ -41,17 +41,25 @@ void osd_plan_build(const Code& c, OsdPlan& out);
 
 constexpr int kOsdMaxOrder = 64;  // QEC_OPT_OSD_ORDER: lambda of the combination sweep, 0 .. 64
 
+// QEC_OPT_OSD_SCORE = 1: the sweep's integer weight of a flip on a qubit of prior pi, in
+// sixteenths of a bit of log-likelihood ratio: 0 for pi >= 1/2, 4095 for pi = 0, else
+// min(4095, llrint(16 log2((1 - pi) / pi))), the float taken exactly to double.
+constexpr int kOsdMaxWeight = 4095;
+int32_t osd_weight(float prior);
+
 // Steps 2-6 for one sector of one sample: q = the sample's q_final block, s = the sector's syndrome
 // bytes, e = the sector's estimate (n bytes), rewritten only if [H | s] is consistent.  Returns
 // whether it was.  order = lambda of section 1.3 (0: the OSD-0 estimate); *swept (nullable) tells
-// whether the lightest candidate was another than the OSD-0 estimate (index > 0).
+// whether the lightest candidate was another than the OSD-0 estimate (index > 0).  w (nullable): the
+// sector's n weights of section 1.4; the candidate of least score wins instead of the lightest.
 bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8_t* e, int order = 0,
-                     bool* swept = nullptr);
+                     bool* swept = nullptr, const int32_t* w = nullptr);
 
 // Steps 2-7 on a decoded host batch, in place; returns the number of sectors repaired, and in
-// *swept (nullable) how many of them took a candidate of index > 0.
+// *swept (nullable) how many of them took a candidate of index > 0.  w (nullable): the weight tables
+// of section 1.4, sector X [n] then sector Z [n].
 long long osd_host_batch(const OsdPlan& P, const uint8_t* sX, const uint8_t* sZ, long long B, const float* q,
                          uint8_t* eX, uint8_t* eZ, uint8_t* flags, int threads, int order = 0,
-                         long long* swept = nullptr);
+                         long long* swept = nullptr, const int32_t* w = nullptr);
 
 }  // namespace qec

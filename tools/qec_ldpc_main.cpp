@@ -28,6 +28,8 @@
 //   --osd-order L      with --osd 0: the combination sweep OSD-CS over the L most suspicious non-pivot
 //                      columns (QEC_OPT_OSD_ORDER, 0 .. 64; default 0 = OSD-0)
 //   --osd-iterations K iterations of the soft decode that orders OSD's columns (default 3; needs --osd)
+//   --osd-score hamming|priors   with --osd 0: how the sweep scores its candidates (QEC_OPT_OSD_SCORE): by Hamming
+//                      weight (default), or by likelihood under the priors of --priors FILE, which it then needs
 //   --priors FILE      per-qubit priors (qec_decoder_set_priors) for whatever mode runs: FILE holds two lines of n
 //                      decimal floats, sector X then sector Z.  BP then uses them and the init file's p is not
 //                      used; --rng philox draws its errors independently per qubit from them.  Sparse-graph and
@@ -80,7 +82,7 @@ int usage(const std::string& why)
     std::cerr << why << std::endl
               << "usage: qec_ldpc [--engine gpu|sparse|cpu] [--gpus N | --devices i,j,...] [--rng msvc|philox]"
                  " [--stop ref|fixed|syndrome] [--batch B] [--seed S] [--logical file|reference|degenerate]"
-                 " [--osd 0 [--osd-order L] [--osd-iterations K]] [--priors FILE] initFile"
+                 " [--osd 0 [--osd-order L] [--osd-iterations K] [--osd-score hamming|priors]] [--priors FILE] initFile"
               << std::endl;
     return 2;
 }
@@ -115,7 +117,8 @@ int main(int argc, char** argv)
     std::vector<int> devices{0};
     std::string engine = "gpu", rng = "msvc", stopName = "ref", logical = "file", priorsFile;
     bool deviceFlag = false, stopFlag = false, batchFlag = false, seedFlag = false, osd = false, osdIterFlag = false;
-    bool osdOrderFlag = false;
+    bool osdOrderFlag = false, osdScoreFlag = false;
+    int osdScore = 0;
     int osdIterations = 3, osdOrder = 0;
     size_t batch = size_t(1) << 20;
     unsigned long long seed = 0x51EC0DE;
@@ -165,6 +168,10 @@ int main(int argc, char** argv)
                 osdIterations = std::stoi(val);
                 osdIterFlag = true;
                 if (osdIterations < 1) return usage("--osd-iterations: at least 1");
+            } else if (flag == "--osd-score") {
+                if (val != "hamming" && val != "priors") return usage("--osd-score: hamming or priors");
+                osdScore = val == "priors" ? 1 : 0;
+                osdScoreFlag = true;
             } else if (flag == "--priors") {
                 priorsFile = val;
             } else if (flag == "--seed") {
@@ -183,6 +190,8 @@ int main(int argc, char** argv)
         return usage("--stop / --batch apply to --rng philox (GetStatistics keeps the reference stop rule)");
     if (osdIterFlag && !osd) return usage("--osd-iterations needs --osd 0");
     if (osdOrderFlag && !osd) return usage("--osd-order needs --osd 0");
+    if (osdScoreFlag && !osd) return usage("--osd-score needs --osd 0");
+    if (osdScore == 1 && priorsFile.empty()) return usage("--osd-score priors needs --priors FILE");
     if (argc - a != 1 || devices.empty()) {
         log << "Must provide initialization file." << std::endl;
         return 0;
@@ -220,6 +229,7 @@ int main(int argc, char** argv)
                                                                : new DecoderGPU(code, devices));
             DecoderGPU& decoder = *dp;
             if (osd) decoder.SetOsd(osdOrder, osdIterations);
+            if (osd) decoder.SetOsdScore(osdScore);
             if (!priorsFile.empty()) decoder.SetPriors(priorX, priorZ);
             std::cout << "Engine: " << decoder.Describe() << std::endl;
             const int stop = stopName == "ref" ? QEC_STOP_REF : stopName == "fixed" ? QEC_STOP_FIXED : QEC_STOP_SYNDROME;
@@ -243,12 +253,14 @@ int main(int argc, char** argv)
             DecoderCPU* c = new DecoderCPU(code);
             decoder.reset(c);
             if (osd) c->SetOsd(osdOrder, osdIterations);
+            if (osd) c->SetOsdScore(osdScore);
             if (!priorsFile.empty()) c->SetPriors(priorX, priorZ);
             std::cout << "Engine: CPU (" << std::thread::hardware_concurrency() << " threads)" << std::endl;
         } else {
             DecoderGPU* g = engine == "sparse" ? new DecoderGPU(code, 0, QEC_ENGINE_SPARSE) : new DecoderGPU(code, devices);
             decoder.reset(g);
             if (osd) g->SetOsd(osdOrder, osdIterations);
+            if (osd) g->SetOsdScore(osdScore);
             if (!priorsFile.empty()) g->SetPriors(priorX, priorZ);
             std::cout << "Engine: " << g->Describe() << std::endl;
         }
