@@ -50,6 +50,10 @@ public:
     {
         return SUCCESS;
     }
+    // The correlated form (QEC_OPT_CORRELATED of qec_ldpc.h; no reference analogue): 0 off, 1 X first, 2 Z first
+    virtual void SetCorrelated(int order) = 0;
+    // Per-qubit Pauli channel (qec_decoder_set_pauli_channel; no reference analogue), n entries each
+    virtual void SetPauliChannel(const std::vector<float>& pX, const std::vector<float>& pY, const std::vector<float>& pZ) = 0;
     virtual CodeStatistics GetStatistics(int errorWeight, int numErrors, float errorProbability, int maxIterations) = 0;
     virtual CodeStatistics GetStatistics(int errorWeight, int numErrors, float errorProbability, int maxIterations,
                                          unsigned int seed) = 0;

@@ -82,6 +82,18 @@ public:
         check(qec_decoder_set_priors(dec_, priorX.data(), priorZ.data()));
     }
     void ClearPriors() { check(qec_decoder_set_priors(dec_, nullptr, nullptr)); }
+    // The correlated form (QEC_OPT_CORRELATED): 0 = both sectors independently (the default), 1 = sector X first and
+    // sector Z under priors conditioned on the X estimate, 2 = Z first.  Any other value throws the library's message.
+    void SetCorrelated(int order) override { check(qec_decoder_set_option(dec_, QEC_OPT_CORRELATED, order)); }
+    // Per-qubit Pauli channel (qec_decoder_set_pauli_channel): qubit v suffers X, Y or Z with probabilities pX[v],
+    // pY[v], pZ[v] (n entries each; Y sets both bits).  Installs the marginal priors, the conditional tables of
+    // SetCorrelated and the noise of the device Monte-Carlo run; a later SetPriors or ClearPriors drops it.
+    void SetPauliChannel(const std::vector<float>& pX, const std::vector<float>& pY, const std::vector<float>& pZ) override
+    {
+        if (pX.size() != (size_t)_code.n || pY.size() != (size_t)_code.n || pZ.size() != (size_t)_code.n)
+            throw std::string("SetPauliChannel: pX, pY and pZ need n = " + std::to_string(_code.n) + " entries each");
+        check(qec_decoder_set_pauli_channel(dec_, pX.data(), pY.data(), pZ.data()));
+    }
     qec_decoder* handle() { return dec_; }
 
 private:

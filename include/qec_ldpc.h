@@ -311,11 +311,29 @@ int qec_decoder_device(const qec_decoder* dec);         /* HIP device ordinal (o
  *     the Hamming score but not with these, the call that would make the weighted sweep run (this option,
  *     QEC_OPT_OSD_ORDER or qec_decoder_set_priors, whichever comes last) returns QEC_ERR_UNSUPPORTED and
  *     the text says so.  The result depends only on (code, syndrome, priors, QEC_OPT_OSD_ITERATIONS,
- *     lambda, this rule). */
+ *     lambda, this rule).
+ *   QEC_OPT_CORRELATED (default 0; 0, 1 or 2, other values QEC_ERR_ARG): the correlated form of DESIGN.md
+ *     section 2.  A Y error sets both bits of a qubit, so one sector's estimate says something about the other's
+ *     bits.  0 = both sectors under their marginal priors, independently, as ever (the same kernels).  1 = the
+ *     first sector F = X, the second S = Z; 2 = F = Z, S = X.  F is decoded exactly as under 0 (its estimate,
+ *     its two flag bits, its iters entry and its block of q_final are the option-0 call's bit for bit); with
+ *     d = F's final estimate (the bytes of eX / eZ), S is decoded by the prior form with
+ *     pi_v = d[v] ? c1_S[v] : c0_S[v], its own iteration counter, last iteration and stop tests.  The tables:
+ *     without priors c1 = 0.5f and c0 = (p / 3.0f) / (1.0f - 2.0f / 3.0f * p) in fp32 for both directions
+ *     (qec_correlated_priors); with qec_decoder_set_priors alone c0_S = c1_S = S's marginal prior (independent
+ *     marginals carry no correlation: every output bit equals the option-0 call); with a Pauli channel
+ *     (qec_decoder_set_pauli_channel) its four conditional tables.  Sparse-graph engine (the CORR kernels of
+ *     bp_sparse.hip; the plan, the workspace and the describe string are unchanged) and CPU engine (whose
+ *     near-hard jump may fire for F and never fires for S); a wave-circulant handle refuses 1 and 2 with
+ *     QEC_ERR_UNSUPPORTED and the text says to create the decoder with QEC_ENGINE_SPARSE.  Every decode entry
+ *     point honours it, the _dev ones read it at the call (a captured graph keeps the kernels it captured), the
+ *     OSD stage's soft decode goes through the same path; QEC_OPT_OSD_SCORE = 1 keeps scoring with the marginal
+ *     tables and S is not decoded again after OSD repairs F.  A group applies the value to every part. */
 enum { QEC_OPT_HARD_PATHS = 1, QEC_OPT_CYCLE_JUMP = 2, QEC_OPT_SCHEDULE = 3, QEC_OPT_SECTOR_SPLIT = 4,
        QEC_OPT_PHASE_STATS = 5, QEC_OPT_TRIAGE = 6, QEC_OPT_LAST_PATH = 7, QEC_OPT_MC_DECODE_TIME = 8,
        QEC_OPT_OSD = 9, QEC_OPT_OSD_ITERATIONS = 10, QEC_OPT_OSD_SECTORS = 11, QEC_OPT_OSD_SWEEP = 12,
-       QEC_OPT_OSD_ORDER = 13, QEC_OPT_OSD_CS_SECTORS = 14, QEC_OPT_NEAR_HARD_JUMP = 15, QEC_OPT_OSD_SCORE = 16 };
+       QEC_OPT_OSD_ORDER = 13, QEC_OPT_OSD_CS_SECTORS = 14, QEC_OPT_NEAR_HARD_JUMP = 15, QEC_OPT_OSD_SCORE = 16,
+       QEC_OPT_CORRELATED = 17 };
 enum {
     QEC_PATH_ORDERED = 1,          /* dispatch order pass (schedule.hip) */
     QEC_PATH_SECTOR_ORDER = 2,     /* ... in the per-sector form (each sector's waves by its own weight) */
@@ -325,7 +343,8 @@ enum {
     QEC_PATH_BIT_ROWS = 32,        /* bit-row syndromes in */
     QEC_PATH_SPARSE = 64,          /* sparse-graph engine */
     QEC_PATH_RECORDS = 128,        /* packed decision records out */
-    QEC_PATH_OSD = 256             /* the call ran the OSD stage (QEC_OPT_OSD) */
+    QEC_PATH_OSD = 256,            /* the call ran the OSD stage (QEC_OPT_OSD) */
+    QEC_PATH_CORRELATED = 512      /* one sector decoded under priors conditioned on the other's estimate */
 };
 /* The near-hard jump's threshold for p' = pPrime (the float (2/3) errorProbability the decoder forms), R
  * checks per variable and L variables per check: *eps0 = the largest power of two in [2^-20, 2^-8] with
@@ -379,6 +398,32 @@ int qec_decoder_get_priors(const qec_decoder* dec, float* priorX, float* priorZ)
  * the option's value): 1 and the arrays filled (n entries each, 0 .. 4095; a NULL array is skipped) if
  * priors are set, 0 if not. */
 int qec_decoder_get_osd_weights(const qec_decoder* dec, int32_t* wX, int32_t* wZ);
+/* The scalar tables of QEC_OPT_CORRELATED for depolarising noise of strength p: *c1 = P(other bit | this bit
+ * set) = 0.5f and *c0 = P(other bit | this bit clear) = (p / 3.0f) / (1.0f - 2.0f / 3.0f * p), every operation
+ * in fp32.  Both engines decode with exactly these values. */
+int qec_correlated_priors(float p, float* c0, float* c1);
+/* Per-qubit Pauli channel: qubit v suffers X, Y or Z with probabilities pX[v], pY[v], pZ[v] (HOST arrays of n
+ * floats); Y sets both bits.  Every entry in [0, 1] (NaN is not), (pX + pY) + pZ <= 1 evaluated in double:
+ * QEC_ERR_ARG otherwise, the text names array and index ("pY[17] = ...", "pX[17] + pY[17] + pZ[17] = ...").  Exactly one
+ * or two NULL pointers: QEC_ERR_ARG; all three NULL clears the channel and the priors.
+ *   - Marginals: priorX = pX + pY, priorZ = pZ + pY (double from the floats, rounded once to float), installed
+ *     exactly as qec_decoder_set_priors(priorX, priorZ) installs them (device buffer, OSD weight tables, its
+ *     refusals, every part of a group); qec_decoder_get_priors returns them.
+ *   - Conditionals (double, one rounding, min(1, .); a zero denominator gives 0.5f): cZ1 = pY / (pX + pY),
+ *     cZ0 = pZ / (1 - (pX + pY)), cX1 = pY / (pZ + pY), cX0 = pX / (1 - (pZ + pY)): the priors of the second
+ *     sector's bit given the first sector's estimate under QEC_OPT_CORRELATED.
+ *   - Any later qec_decoder_set_priors, (NULL, NULL) included, drops the channel.
+ *   - The device copies follow the priors' contract: allocated by the first set, rewritten in place afterwards,
+ *     synchronous; the _dev entry points allocate nothing and never synchronise, and a captured graph replayed
+ *     after a later set decodes (and samples) with the new tables.
+ *   - On a handle with a channel qec_sample_syndrome_dev and qec_monte_carlo draw qec_sample_pauli_dev's errors,
+ *     whatever QEC_OPT_CORRELATED says (the channel is the noise, the option how it is decoded), through the
+ *     unfused byte-syndrome pipeline that priors force.
+ *   - A wave-circulant handle refuses with QEC_ERR_UNSUPPORTED (create the decoder with QEC_ENGINE_SPARSE). */
+int qec_decoder_set_pauli_channel(qec_decoder* dec, const float* pX, const float* pY, const float* pZ);
+/* 1 and the arrays filled (n floats each; a NULL array is skipped) if a channel is set, 0 if not. */
+int qec_decoder_get_pauli_channel(const qec_decoder* dec, float* pX, float* pY, float* pZ);
+int qec_decoder_get_conditional_priors(const qec_decoder* dec, float* cZ0, float* cZ1, float* cX0, float* cX1);
 /* which kernel variant serves this code: writes a short name (e.g. "wave-circulant P=61 G=1") */
 int qec_decoder_describe(const qec_decoder* dec, char* buf, size_t len);
 
@@ -472,12 +517,22 @@ int qec_sample_depolarizing_dev(qec_decoder* dec, uint64_t seed, uint64_t start,
  * synchronisation, no allocation.  Single-device GPU handle. */
 int qec_sample_independent_dev(qec_decoder* dec, uint64_t seed, uint64_t start, size_t B, uint8_t* x, uint8_t* z,
                                void* stream);
+/* Errors of the handle's Pauli channel (qec_decoder_set_pauli_channel; QEC_ERR_ARG without one) for samples
+ * [start, start+B) of stream `seed` (device buffers x, z: B x n bytes).  Sample b makes Philox4x32-10 calls
+ * k = 0, 1, ... with counter (b lo, b hi, k, 0x3C6EF372) and key (seed lo, seed hi); output word j of call k is
+ * the word u of qubit 4k + j.  With the 64-bit thresholds tX = floor(pX 2^32), tXY = floor((pX + pY) 2^32) and
+ * tXYZ = floor(min(1, (pX + pY) + pZ) 2^32), evaluated in double from the floats: x = u < tXY and
+ * z = tX <= u < tXYZ.  Any shard of the index space can be drawn alone.  Enqueued on `stream`; no
+ * synchronisation, no allocation.  Single-device GPU handle. */
+int qec_sample_pauli_dev(qec_decoder* dec, uint64_t seed, uint64_t start, size_t B, uint8_t* x, uint8_t* z,
+                         void* stream);
 /* Fused front end: the depolarising errors of qec_sample_depolarizing_dev (same stream, same
  * bits) go straight to their syndromes (GetSyndromeX/Z, Quantum_LDPC_Code.h:94-124) without
  * leaving the chip: sX B x numEqsX, sZ B x numEqsZ, and optionally errp B x 2 ceil(n/8), the
  * errors bit-packed in the decision-record layout (x bits then z bits) for
  * qec_statistics_packed_dev.  One wave per sample.  On a handle with priors the errors are those of
- * qec_sample_independent_dev instead (same stream, same bits) and p is not used. */
+ * qec_sample_independent_dev instead (same stream, same bits) and p is not used; with a Pauli channel those of
+ * qec_sample_pauli_dev. */
 int qec_sample_syndrome_dev(qec_decoder* dec, uint64_t seed, uint64_t start, size_t B, float p, uint8_t* sX,
                             uint8_t* sZ, uint8_t* errp, void* stream);
 /* GetSyndromeX/Z (Quantum_LDPC_Code.h:94-124) of device error vectors: x, z B x n -> sX B x numEqsX, sZ B x numEqsZ */

@@ -28,11 +28,12 @@ STOP = {"ref": 0, "fixed": 1, "syndrome": 2}
 ENGINE = {"auto": 0, "circulant": 1, "sparse": 2, "cpu": 3}
 OPTION = {"hard_paths": 1, "cycle_jump": 2, "schedule": 3, "sector_split": 4, "phase_stats": 5, "triage": 6,
           "last_path": 7, "mc_decode_time": 8, "osd": 9, "osd_iterations": 10, "osd_sectors": 11,
-          "osd_sweep": 12, "osd_order": 13, "osd_cs_sectors": 14, "near_hard": 15, "osd_score": 16}
+          "osd_sweep": 12, "osd_order": 13, "osd_cs_sectors": 14, "near_hard": 15, "osd_score": 16,
+          "correlated": 17}
 OPTIONS = OPTION
 # QEC_PATH_* bits of QEC_OPT_LAST_PATH (include/qec_ldpc.h): the launch sequence of the last decode call
 PATH = {"ordered": 1, "sector_order": 2, "split_waves": 4, "sector_launches": 8, "triage": 16, "bit_rows": 32,
-        "sparse": 64, "records": 128, "osd": 256}
+        "sparse": 64, "records": 128, "osd": 256, "correlated": 512}
 
 # every symbol include/qec_ldpc.h declares
 EXPORTS = (
@@ -45,6 +46,8 @@ EXPORTS = (
     "qec_decoder_num_parts", "qec_decoder_part", "qec_decoder_device", "qec_decoder_describe",
     "qec_decoder_set_option", "qec_decoder_get_option", "qec_near_hard_threshold",
     "qec_decoder_set_priors", "qec_decoder_get_priors", "qec_decoder_get_osd_weights", "qec_sample_independent_dev",
+    "qec_correlated_priors", "qec_decoder_set_pauli_channel", "qec_decoder_get_pauli_channel",
+    "qec_decoder_get_conditional_priors", "qec_sample_pauli_dev",
     "qec_decode_batch", "qec_decode_batch_dev", "qec_decode_batch_packed", "qec_decode_batch_packed_dev",
     "qec_decode_bits_packed_dev",
     "qec_sample_fixed_weight", "qec_get_statistics",
@@ -146,6 +149,11 @@ def lib():
             "qec_decoder_get_priors": (i, [vp, vp, vp]),
             "qec_decoder_get_osd_weights": (i, [vp, vp, vp]),
             "qec_sample_independent_dev": (i, [vp, ctypes.c_uint64, ctypes.c_uint64, sz, vp, vp, vp]),
+            "qec_correlated_priors": (i, [f, vp, vp]),
+            "qec_decoder_set_pauli_channel": (i, [vp, vp, vp, vp]),
+            "qec_decoder_get_pauli_channel": (i, [vp, vp, vp, vp]),
+            "qec_decoder_get_conditional_priors": (i, [vp, vp, vp, vp, vp]),
+            "qec_sample_pauli_dev": (i, [vp, ctypes.c_uint64, ctypes.c_uint64, sz, vp, vp, vp]),
             "qec_decode_batch": (i, [vp, vp, vp, sz, f, i, i, vp, vp, vp, vp, vp]),
             "qec_decode_batch_dev": (i, [vp, vp, vp, sz, f, i, i, vp, vp, vp, vp, vp, vp]),
             "qec_decode_batch_packed": (i, [vp, vp, vp, sz, f, i, i, vp, vp]),
@@ -189,6 +197,15 @@ def near_hard_threshold(p_prime, R, L):
     _check(lib().qec_near_hard_threshold(float(np.float32(p_prime)), int(R), int(L), ctypes.byref(eps0), ctypes.byref(T)),
            "qec_near_hard_threshold")
     return float(eps0.value), int(T.value)
+
+
+def correlated_priors(p):
+    """qec_correlated_priors: (c0, c1) as float32 -- the priors of one sector's bit given that the other sector's
+    bit of the same qubit is clear / set, under depolarising noise of strength p (a float32): the scalar tables
+    of set_option("correlated", 1 | 2) on a decoder without priors."""
+    c0, c1 = ctypes.c_float(0.0), ctypes.c_float(0.0)
+    _check(lib().qec_correlated_priors(float(np.float32(p)), ctypes.byref(c0), ctypes.byref(c1)), "qec_correlated_priors")
+    return np.float32(c0.value), np.float32(c1.value)
 
 
 def _check(rc, what):
@@ -476,6 +493,47 @@ class DecoderGPU:
             raise QecError("qec_decoder_get_priors failed (%d): %s" % (rc, last_error()))
         return (pX, pZ) if rc == 1 else None
 
+    def set_pauli_channel(self, pX, pY, pZ):
+        """Per-qubit Pauli channel (qec_decoder_set_pauli_channel): qubit v suffers X, Y or Z with probabilities
+        pX[v], pY[v], pZ[v] (Y sets both bits) -- array-likes of length n or scalars for every qubit;
+        set_pauli_channel(None, None, None) clears the channel and the priors.  Installs the marginals pX + pY and
+        pZ + pY as set_priors does (get_priors returns them), the conditional tables that
+        set_option("correlated", 1 | 2) decodes the second sector with (get_conditional_priors), and the noise
+        that sample_pauli_dev, sample_syndrome_dev and monte_carlo draw.  A later set_priors drops the channel."""
+        given = [a is not None for a in (pX, pY, pZ)]
+        if not any(given):
+            _check(lib().qec_decoder_set_pauli_channel(self._h, None, None, None), "qec_decoder_set_pauli_channel")
+            return
+        if not all(given):
+            raise QecError("set_pauli_channel: pX, pY and pZ must all be given, or all be None (clear)")
+        arrs = []
+        for name, pr in (("pX", pX), ("pY", pY), ("pZ", pZ)):
+            a = np.asarray(pr, dtype=np.float32)
+            if a.ndim == 0:
+                a = np.full(self.code.n, a, dtype=np.float32)
+            if a.shape != (self.code.n,):
+                raise QecError("set_pauli_channel: %s must be a scalar or have length n = %d, has shape %s"
+                               % (name, self.code.n, a.shape))
+            arrs.append(np.ascontiguousarray(a))
+        _check(lib().qec_decoder_set_pauli_channel(self._h, *[_ptr(a) for a in arrs]), "qec_decoder_set_pauli_channel")
+
+    def _get_tables(self, fn, count):
+        out = [np.empty(self.code.n, dtype=np.float32) for _ in range(count)]
+        rc = getattr(lib(), fn)(self._h, *[_ptr(a) for a in out])
+        if rc < 0:
+            raise QecError("%s failed (%d): %s" % (fn, rc, last_error()))
+        return tuple(out) if rc == 1 else None
+
+    def get_pauli_channel(self):
+        """(pX, pY, pZ) as float32 arrays (qec_decoder_get_pauli_channel), or None when no channel is set."""
+        return self._get_tables("qec_decoder_get_pauli_channel", 3)
+
+    def get_conditional_priors(self):
+        """(cZ0, cZ1, cX0, cX1) as float32 arrays (qec_decoder_get_conditional_priors): the prior of a qubit's Z
+        bit given its X bit clear / set, and of its X bit given its Z bit clear / set, under the Pauli channel;
+        None when no channel is set."""
+        return self._get_tables("qec_decoder_get_conditional_priors", 4)
+
     def osd_weights(self):
         """(wX, wZ) as int32 arrays (qec_decoder_get_osd_weights): the integer weights, 0 .. 4095 in
         sixteenths of a bit of log-likelihood ratio, that OSD-CS sums over a candidate's flips under
@@ -690,6 +748,19 @@ class DecoderGPU:
                                                 self._t(z, "z", torch.uint8, (B, n)),
                                                 ctypes.c_void_p(self._stream(stream))),
                "qec_sample_independent_dev")
+
+    def sample_pauli_dev(self, seed, start, x, z, stream=None):
+        """Device errors of the decoder's Pauli channel (qec_sample_pauli_dev; needs set_pauli_channel) for
+        samples [start, start + x.shape[0]): word u of qubit v is output word v % 4 of sample b's Philox call
+        v // 4; x[b, v] = u < tXY[v], z[b, v] = tX[v] <= u < tXYZ[v]."""
+        import torch
+        self._single("sample_pauli_dev")
+        B, n = x.shape[0], self.code.n
+        _check(lib().qec_sample_pauli_dev(self._h, seed & (2 ** 64 - 1), start, B,
+                                          self._t(x, "x", torch.uint8, (B, n)),
+                                          self._t(z, "z", torch.uint8, (B, n)),
+                                          ctypes.c_void_p(self._stream(stream))),
+               "qec_sample_pauli_dev")
 
     def sample_syndrome_dev(self, seed, start, p, sX, sZ, errp=None, stream=None):
         """Fused front end: syndromes of the depolarising errors of samples [start, start + B)

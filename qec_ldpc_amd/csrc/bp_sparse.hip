@@ -55,6 +55,12 @@ struct SparseArgs {
     float errorProbability;
     int maxIter;
     const float* prior;      // PRIORS kernels: pi of sector X [n], then of sector Z [n] (qec_decoder_set_priors)
+    // CORR kernels (QEC_OPT_CORRELATED): the first sector (0 = X, 1 = Z) and the second sector's conditional
+    // priors -- with `prior` set the tables cond = c0_X [n], c1_X [n], c0_Z [n], c1_Z [n] (the first sector then
+    // decodes under `prior`), without it the two scalars of qec_correlated_priors (the first sector under p')
+    int first;
+    float c0, c1;
+    const float* cond;
 };
 
 constexpr int kSparseThreads = 256;
@@ -132,13 +138,21 @@ __device__ __forceinline__ bool sp_var(float* __restrict__ msg, const int32_t* _
 
 extern __shared__ __attribute__((aligned(16))) uint8_t sp_lds[];
 
+// the body of both kernels' CORR variant (defined below, behind the general code's updates)
+template <int STOP, int MAXDC, int MAXDV, bool GENERAL>
+__device__ __forceinline__ void sp_corr_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws);
+
 // PRIORS: the per-variable prior form of DESIGN.md section 2 -- the initial message of a slot is the prior of
 // its variable (through chkVar) and a variable's two running products start from 1 - pi_v and pi_v, read
 // from global memory once per pass (8n bytes that every workgroup shares, so they stay in cache);
 // errorProbability is unused.  Without it the kernel is the scalar one, instruction for instruction.
-template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false>
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false>
 __global__ __launch_bounds__(kSparseThreads) void bp_sparse_kernel(const SparseArgs a)
 {
+    if constexpr (CORR) {
+        sp_corr_decode<STOP, MAXDC, MAXDV, false>(a, nullptr, LDS ? sp_lds : a.scratch + (long long)blockIdx.x * a.ws_bytes);
+        return;
+    }
     const int tid = threadIdx.x, nt = blockDim.x;
     const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
     const int EX = mX * dc, E = m * dc;
@@ -361,9 +375,158 @@ struct GeneralArgs {
     const uint8_t* chkDeg;   // mX + mZ degree bytes
 };
 
-template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false>
+// ---- CORR: the correlated form (QEC_OPT_CORRELATED) -----
+// The two sectors of a syndrome pair are decoded one after the other inside the workgroup, the first sector F
+// (a.first) exactly as the kernels above decode it -- the scalar p' or, with a.prior, its marginal priors -- and
+// the second sector S by the prior form with pi_v = d[v] ? c1[v] : c0[v], d = F's final hard decisions, which
+// stay in the workspace's hd bytes.  Workspace layout, grid and workgroup are the scalar plan's.  During a
+// sector's passes the check pass runs threads [0, m_s) and the variable pass threads [0, n) of that sector
+// only; each sector has its own iteration counter, last iteration and stop tests.  S's slots are initialised
+// after F's post-processing, behind its barriers, through chkVar with the select on hd; a variable's thread
+// reads its hd byte and its two table entries once per pass.  The updates are sp_check / sp_var (regular) or
+// sp_check_general / sp_var_general (general: the exact no-op padding, unused slots +0.0f, a variable in no
+// check decides 0), so every fp32 rule of the file carries over; one owner per edge per pass, no atomics.
+template <int STOP, int MAXDC, int MAXDV, bool GENERAL>
+__device__ __forceinline__ void sp_corr_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws)
+{
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
+    const int E = m * dc;
+    float* msg = reinterpret_cast<float*>(ws);            // E floats
+    uint8_t* syn = ws + (size_t)E * sizeof(float);        // m bytes: sX then sZ
+    uint8_t* hd = syn + m;                                // 2n bytes: X then Z hard decisions
+
+    const float pp = 2.0f / 3.0f * a.errorProbability;
+    const int N = a.maxIter < 0 ? 0 : a.maxIter;
+    const bool tab = a.prior != nullptr;  // workgroup-uniform: tables (priors / a Pauli channel) or the scalar case
+
+    for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
+        for (int c = tid; c < m; c += nt) {
+            const uint32_t s = c < mX ? a.sX[b * mX + c] : a.sZ[b * mZ + (c - mX)];
+            if (GENERAL) syn[c] = (uint8_t)((s > 1u ? 2u : s) | ((uint32_t)chkDeg[c] << 2));
+            else syn[c] = (uint8_t)s;
+        }
+        uint32_t f = 0;
+        int itX = 0, itZ = 0;
+        for (int pass = 0; pass < 2; ++pass) {
+            const int sec = pass == 0 ? a.first : 1 - a.first;  // workgroup-uniform
+            const bool second = pass == 1;
+            const int c0 = sec ? mX : 0, ms = sec ? mZ : mX, dv = sec ? a.dvZ : a.dvX;
+            const int e0 = c0 * dc, Es = ms * dc;
+            const int32_t* veS = a.varEdge + (sec ? (size_t)n * a.dvX : 0);
+            const float* pri = tab ? a.prior + (size_t)sec * n : nullptr;
+            const float* t0 = tab ? a.cond + (size_t)sec * 2 * n : nullptr;
+            const float* t1 = tab ? t0 + n : nullptr;
+            uint8_t* hdS = hd + (size_t)sec * n;
+            const uint8_t* hdF = hd + (size_t)(1 - sec) * n;  // read in the second pass only
+
+            // the sector's slots: pi of the slot's variable (the second sector: selected by F's decision)
+            for (int e = tid; e < Es; e += nt) {
+                const int v = a.chkVar[e0 + e];
+                float x = 0.0f;  // an unused slot of a general code
+                if (!GENERAL || v >= 0) {
+                    if (second) {
+                        const bool d = hdF[v] != 0;
+                        x = tab ? (d ? t1[v] : t0[v]) : (d ? a.c1 : a.c0);
+                    } else {
+                        x = tab ? pri[v] : pp;
+                    }
+                }
+                msg[e0 + e] = x;
+            }
+            __syncthreads();
+
+            bool act = true;  // workgroup-uniform
+            int itn = 0;
+            for (int it = 0; it < N && act; ++it) {
+                const bool last = it == N - 1;
+                ++itn;
+                for (int c = tid; c < ms; c += nt) {
+                    const uint32_t sd = syn[c0 + c];
+                    if (GENERAL)
+                        sp_check_general<MAXDC>(msg + (size_t)(c0 + c) * dc, dc, (int)(sd >> 2), (sd & 3u) ? 0.5f : -0.5f);
+                    else
+                        sp_check<MAXDC>(msg + (size_t)(c0 + c) * dc, dc, sd ? 0.5f : -0.5f);
+                }
+                __syncthreads();
+                for (int v = tid; v < n; v += nt) {
+                    float pv;
+                    if (second) {
+                        const bool d = hdF[v] != 0;
+                        pv = tab ? (d ? t1[v] : t0[v]) : (d ? a.c1 : a.c0);
+                    } else {
+                        pv = tab ? pri[v] : pp;
+                    }
+                    const int32_t* ve = veS + (size_t)v * dv;
+                    const bool h = GENERAL ? sp_var_general<MAXDV>(msg, ve, dv, pv, 1.0f - pv, last)
+                                           : sp_var<MAXDV>(msg, ve, dv, pv, 1.0f - pv, last);
+                    if (STOP == QEC_STOP_SYNDROME) hdS[v] = h;
+                }
+                __syncthreads();
+                if (STOP == QEC_STOP_REF && it % 10 == 0) {
+                    bool in = false;
+                    for (int e = tid; e < Es; e += nt) in |= sp_inside(msg[e0 + e]);
+                    act = __syncthreads_or(in);
+                } else if (STOP == QEC_STOP_SYNDROME) {
+                    bool bad = false;
+                    for (int c = tid; c < ms; c += nt) {
+                        uint32_t x = 0;
+                        for (int k = 0; k < dc; ++k) {
+                            const int v = a.chkVar[(size_t)(c0 + c) * dc + k];
+                            x ^= (!GENERAL || v >= 0) ? (uint32_t)hdS[v < 0 ? 0 : v] : 0u;
+                        }
+                        bad |= x != (GENERAL ? (syn[c0 + c] & 3u) : (uint32_t)syn[c0 + c]);
+                    }
+                    act = __syncthreads_or(bad);
+                }
+            }
+
+            // ---- post-processing of Decode for this sector ----
+            bool in = false;
+            for (int e = tid; e < Es; e += nt) in |= sp_inside(msg[e0 + e]);
+            uint8_t* eOut = sec ? a.eZ : a.eX;
+            for (int v = tid; v < n; v += nt) {
+                const int32_t* ve = veS + (size_t)v * dv;
+                bool h = false;
+                for (int j = 0; j < dv; ++j) {
+                    const int ed = ve[j];
+                    h |= (!GENERAL || ed >= 0) && msg[ed < 0 ? 0 : ed] >= 0.5f;
+                }
+                hdS[v] = h;
+                eOut[b * n + v] = h;
+            }
+            const bool convFail = __syncthreads_or(in);
+            bool bad = false;
+            for (int c = tid; c < ms; c += nt) {
+                uint32_t x = 0;
+                for (int k = 0; k < dc; ++k) {
+                    const int v = a.chkVar[(size_t)(c0 + c) * dc + k];
+                    x ^= (!GENERAL || v >= 0) ? (uint32_t)hdS[v < 0 ? 0 : v] : 0u;
+                }
+                bad |= x != (GENERAL ? (syn[c0 + c] & 3u) : (uint32_t)syn[c0 + c]);
+            }
+            const bool synFail = __syncthreads_or(bad);
+            if (synFail) f |= sec ? QEC_SYNDROME_FAIL_Z : QEC_SYNDROME_FAIL_X;
+            if (convFail) f |= sec ? QEC_CONVERGENCE_FAIL_Z : QEC_CONVERGENCE_FAIL_X;
+            if (sec) itZ = itn; else itX = itn;
+        }
+        if (a.q != nullptr)
+            for (int e = tid; e < E; e += nt) a.q[b * E + e] = msg[e];
+        if (tid == 0) {
+            a.flags[b] = (uint8_t)f;
+            if (a.iters != nullptr) { a.iters[2 * b] = itX; a.iters[2 * b + 1] = itZ; }
+        }
+        __syncthreads();  // the workspace is reused by the next syndrome pair
+    }
+}
+
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false>
 __global__ __launch_bounds__(kSparseThreads) void bp_general_kernel(const GeneralArgs ga)
 {
+    if constexpr (CORR) {
+        sp_corr_decode<STOP, MAXDC, MAXDV, true>(ga.s, ga.chkDeg, LDS ? sp_lds : ga.s.scratch + (long long)blockIdx.x * ga.s.ws_bytes);
+        return;
+    }
     const SparseArgs& a = ga.s;
     const int tid = threadIdx.x, nt = blockDim.x;
     const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, D = a.dc;
@@ -495,10 +658,13 @@ __global__ __launch_bounds__(kSparseThreads) void bp_general_kernel(const Genera
 using SparseFn = void (*)(const SparseArgs);
 using GeneralFn = void (*)(const GeneralArgs);
 
-// f: the scalar kernels per stop rule; fp: the same shapes with PRIORS
+// f: the scalar kernels per stop rule; fp: the same shapes with PRIORS; fc: with CORR
 template <int MAXDC, int MAXDV, bool LDS>
-static void general_fns(GeneralFn (&f)[3], GeneralFn (&fp)[3])
+static void general_fns(GeneralFn (&f)[3], GeneralFn (&fp)[3], GeneralFn (&fc)[3])
 {
+    fc[QEC_STOP_REF] = bp_general_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS, false, true>;
+    fc[QEC_STOP_FIXED] = bp_general_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS, false, true>;
+    fc[QEC_STOP_SYNDROME] = bp_general_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, false, true>;
     f[QEC_STOP_REF] = bp_general_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS>;
     f[QEC_STOP_FIXED] = bp_general_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS>;
     f[QEC_STOP_SYNDROME] = bp_general_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS>;
@@ -508,8 +674,11 @@ static void general_fns(GeneralFn (&f)[3], GeneralFn (&fp)[3])
 }
 
 template <int MAXDC, int MAXDV, bool LDS>
-static void sparse_fns(SparseFn (&f)[3], SparseFn (&fp)[3])
+static void sparse_fns(SparseFn (&f)[3], SparseFn (&fp)[3], SparseFn (&fc)[3])
 {
+    fc[QEC_STOP_REF] = bp_sparse_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS, false, true>;
+    fc[QEC_STOP_FIXED] = bp_sparse_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS, false, true>;
+    fc[QEC_STOP_SYNDROME] = bp_sparse_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, false, true>;
     f[QEC_STOP_REF] = bp_sparse_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS>;
     f[QEC_STOP_FIXED] = bp_sparse_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS>;
     f[QEC_STOP_SYNDROME] = bp_sparse_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS>;
@@ -525,10 +694,12 @@ struct SparsePlan {
     int grid = 0;
     SparseFn fn[3] = {nullptr, nullptr, nullptr};
     SparseFn pfn[3] = {nullptr, nullptr, nullptr};    // the PRIORS kernels of the same shape
+    SparseFn cfn[3] = {nullptr, nullptr, nullptr};    // the CORR kernels of the same shape
     // a general code: bp_general_kernel, its degree bytes and its fitted workgroup size
     bool general = false;
     GeneralFn gfn[3] = {nullptr, nullptr, nullptr};
     GeneralFn gpfn[3] = {nullptr, nullptr, nullptr};
+    GeneralFn gcfn[3] = {nullptr, nullptr, nullptr};
     DeviceArray<uint8_t> chkDeg;
     int threads = kSparseThreads;
     DeviceArray<int32_t> chkVar, varEdge;
@@ -617,16 +788,16 @@ void* sparse_plan_create(const Code& c, int device)
     const int wdv = std::max(dvX, dvZ) <= 4 ? 4 : std::max(dvX, dvZ) <= 8 ? 8 : 16;
     // instantiated shapes: (8,4) (16,8) (32,16); pick the smallest that covers the code
     if (general) {
-        if (wdc <= 8 && wdv <= 4) { if (p->lds) general_fns<8, 4, true>(p->gfn, p->gpfn); else general_fns<8, 4, false>(p->gfn, p->gpfn); }
-        else if (wdc <= 16 && wdv <= 8) { if (p->lds) general_fns<16, 8, true>(p->gfn, p->gpfn); else general_fns<16, 8, false>(p->gfn, p->gpfn); }
-        else { if (p->lds) general_fns<32, 16, true>(p->gfn, p->gpfn); else general_fns<32, 16, false>(p->gfn, p->gpfn); }
+        if (wdc <= 8 && wdv <= 4) { if (p->lds) general_fns<8, 4, true>(p->gfn, p->gpfn, p->gcfn); else general_fns<8, 4, false>(p->gfn, p->gpfn, p->gcfn); }
+        else if (wdc <= 16 && wdv <= 8) { if (p->lds) general_fns<16, 8, true>(p->gfn, p->gpfn, p->gcfn); else general_fns<16, 8, false>(p->gfn, p->gpfn, p->gcfn); }
+        else { if (p->lds) general_fns<32, 16, true>(p->gfn, p->gpfn, p->gcfn); else general_fns<32, 16, false>(p->gfn, p->gpfn, p->gcfn); }
         // the smallest workgroup that gives the wider pass a thread per node
         const long long wide = std::max<long long>(m, 2LL * n);
         p->threads = wide <= 64 ? 64 : wide <= 128 ? 128 : kSparseThreads;
     }
-    else if (wdc <= 8 && wdv <= 4) { if (p->lds) sparse_fns<8, 4, true>(p->fn, p->pfn); else sparse_fns<8, 4, false>(p->fn, p->pfn); }
-    else if (wdc <= 16 && wdv <= 8) { if (p->lds) sparse_fns<16, 8, true>(p->fn, p->pfn); else sparse_fns<16, 8, false>(p->fn, p->pfn); }
-    else { if (p->lds) sparse_fns<32, 16, true>(p->fn, p->pfn); else sparse_fns<32, 16, false>(p->fn, p->pfn); }
+    else if (wdc <= 8 && wdv <= 4) { if (p->lds) sparse_fns<8, 4, true>(p->fn, p->pfn, p->cfn); else sparse_fns<8, 4, false>(p->fn, p->pfn, p->cfn); }
+    else if (wdc <= 16 && wdv <= 8) { if (p->lds) sparse_fns<16, 8, true>(p->fn, p->pfn, p->cfn); else sparse_fns<16, 8, false>(p->fn, p->pfn, p->cfn); }
+    else { if (p->lds) sparse_fns<32, 16, true>(p->fn, p->pfn, p->cfn); else sparse_fns<32, 16, false>(p->fn, p->pfn, p->cfn); }
     try {
         if (hipSetDevice(device) != hipSuccess) throw std::runtime_error("hipSetDevice");
         int cus = 0;
@@ -640,9 +811,10 @@ void* sparse_plan_create(const Code& c, int device)
                 if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)p->ws_bytes) != hipSuccess)
                     throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-            // the PRIORS kernels take the same dynamic LDS (the grid stays the scalar kernels')
-            for (int k = 0; k < 3; ++k) {
-                const void* f = general ? reinterpret_cast<const void*>(p->gpfn[k]) : reinterpret_cast<const void*>(p->pfn[k]);
+            // the PRIORS and CORR kernels take the same dynamic LDS (the grid stays the scalar kernels')
+            for (int k = 0; k < 6; ++k) {
+                const void* f = k < 3 ? (general ? reinterpret_cast<const void*>(p->gpfn[k]) : reinterpret_cast<const void*>(p->pfn[k]))
+                                      : (general ? reinterpret_cast<const void*>(p->gcfn[k - 3]) : reinterpret_cast<const void*>(p->cfn[k - 3]));
                 if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->ws_bytes) != hipSuccess)
                     throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
             }
@@ -692,9 +864,11 @@ const int32_t* sparse_plan_chkvar(const void* plan) { return static_cast<const S
 const int32_t* sparse_plan_varedge(const void* plan) { return static_cast<const SparsePlan*>(plan)->varEdge.data(); }
 
 // prior: nullptr (the scalar kernels, errorProbability), or the device array of 2n priors (the PRIORS kernels)
+// corr: QEC_OPT_CORRELATED -- 0, or 1 / 2 for the CORR kernels with first sector X / Z; then cond is the device
+// array of the 4n conditional priors when prior is set, and c0 / c1 the scalar pair when it is not
 int launch_decode_sparse(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float errorProbability,
                          int maxIter, int stop, uint8_t* eX, uint8_t* eZ, uint8_t* flags, int32_t* iters, float* q,
-                         hipStream_t stream, const float* prior)
+                         hipStream_t stream, const float* prior, int corr, const float* cond, float c0, float c1)
 {
     auto* p = static_cast<SparsePlan*>(plan);
     if (B <= 0) return QEC_OK;
@@ -709,12 +883,16 @@ int launch_decode_sparse(void* plan, const uint8_t* sX, const uint8_t* sZ, long 
     a.errorProbability = errorProbability;
     a.maxIter = maxIter;
     a.prior = prior;
+    a.first = corr == 2 ? 1 : 0;
+    a.c0 = c0; a.c1 = c1;
+    a.cond = cond;
+    if (corr && prior != nullptr && cond == nullptr) return fail(QEC_ERR_ARG, "bp_sparse launch: the correlated form needs its conditional tables");
     const unsigned grid = (unsigned)std::min<long long>(B, p->grid);
     if (p->general) {
         GeneralArgs ga{a, p->chkDeg.data()};
-        hipLaunchKernelGGL(prior ? p->gpfn[stop] : p->gfn[stop], dim3(grid), dim3(p->threads), p->lds ? (size_t)p->ws_bytes : 0, stream, ga);
+        hipLaunchKernelGGL(corr ? p->gcfn[stop] : prior ? p->gpfn[stop] : p->gfn[stop], dim3(grid), dim3(p->threads), p->lds ? (size_t)p->ws_bytes : 0, stream, ga);
     } else {
-        hipLaunchKernelGGL(prior ? p->pfn[stop] : p->fn[stop], dim3(grid), dim3(kSparseThreads), p->lds ? (size_t)p->ws_bytes : 0, stream, a);
+        hipLaunchKernelGGL(corr ? p->cfn[stop] : prior ? p->pfn[stop] : p->fn[stop], dim3(grid), dim3(kSparseThreads), p->lds ? (size_t)p->ws_bytes : 0, stream, a);
     }
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(QEC_ERR_HIP, std::string("bp_sparse launch: ") + hipGetErrorString(err));

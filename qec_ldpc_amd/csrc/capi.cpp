@@ -78,7 +78,9 @@ const int32_t* sparse_plan_chkvar(const void* plan);
 const int32_t* sparse_plan_varedge(const void* plan);
 int launch_decode_sparse(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float errorProbability,
                          int maxIter, int stop, uint8_t* eX, uint8_t* eZ, uint8_t* flags, int32_t* iters, float* q,
-                         hipStream_t stream, const float* prior);
+                         hipStream_t stream, const float* prior, int corr, const float* cond, float c0, float c1);
+int launch_sample_pauli(uint64_t seed, uint64_t start, long long B, int n, const uint64_t* thr, uint8_t* x, uint8_t* z,
+                        hipStream_t st);
 int launch_sample_independent(uint64_t seed, uint64_t start, long long B, int n, const float* prior, uint8_t* x,
                               uint8_t* z, hipStream_t st);
 void* cpu_plan_create(const Code& c);
@@ -86,7 +88,8 @@ void cpu_plan_free(void* plan);
 int cpu_threads();
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
-                     bool near_hard, const float* prior);
+                     bool near_hard, const float* prior, int corr, const float* cond);
+void correlated_priors(float p, float* c0, float* c1);
 int launch_pack_decisions(const uint8_t* eX, const uint8_t* eZ, const uint8_t* flags, long long B, int n, uint8_t* out,
                           hipStream_t st);
 int launch_statistics(const Code& c, const uint64_t* imp_cols, const uint8_t* x, const uint8_t* z, const uint8_t* eX,
@@ -163,6 +166,19 @@ struct qec_decoder {
     DeviceArray<float> dpri;
     const float* prior_host() const { return has_priors ? priors.data() : nullptr; }
     const float* prior_dev() const { return has_priors ? dpri.data() : nullptr; }
+    // QEC_OPT_CORRELATED ("The correlated form"): the option, and the second sector's
+    // conditional priors c0_X [n], c1_X [n], c0_Z [n], c1_Z [n], kept beside the priors by every set (plain
+    // priors: c0 = c1 = the marginal; a Pauli channel: its four tables); device copy as dpri
+    int correlated = 0;
+    std::vector<float> cond;
+    DeviceArray<float> dcond;
+    const float* cond_host() const { return has_priors ? cond.data() : nullptr; }
+    const float* cond_dev() const { return has_priors ? dcond.data() : nullptr; }
+    // Per-qubit Pauli channel (qec_decoder_set_pauli_channel): pX [n], pY [n], pZ [n] and the sampler's 64-bit
+    // thresholds tX [n], tXY [n], tXYZ [n] (device copy as dpri)
+    bool has_channel = false;
+    std::vector<float> pauli;
+    DeviceArray<uint64_t> dpth;
     // QEC_OPT_OSD_SCORE: the rule, and the sweep's weight tables (sector X [n], then Z [n]), rebuilt by
     // every qec_decoder_set_priors; the device copy is allocated and rewritten as dpri is.  The sweep takes
     // the tables only with the rule at 1 and priors set (else the pointers are null: Hamming weight)
@@ -689,6 +705,15 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
         }
         d->osd_score = value;
         return QEC_OK;
+    case QEC_OPT_CORRELATED:
+        if (value < 0 || value > 2)
+            return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_CORRELATED is 0 (off), 1 (X first) or 2 (Z first)");
+        if (value && d->parts.empty() && !d->cpu && d->engine != QEC_ENGINE_SPARSE)
+            return fail(QEC_ERR_UNSUPPORTED,
+                        "qec_decoder_set_option: QEC_OPT_CORRELATED needs per-sample priors, which the wave-circulant engine "
+                        "cannot hold; create the decoder with QEC_ENGINE_SPARSE (engine \"sparse\")");
+        d->correlated = value;
+        return QEC_OK;
     case QEC_OPT_OSD_CS_SECTORS:
         return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD_CS_SECTORS is read only");
     case QEC_OPT_LAST_PATH: return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_LAST_PATH is read only");
@@ -696,26 +721,23 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
     }
 }
 
-int qec_decoder_set_priors(qec_decoder* d, const float* priorX, const float* priorZ)
+// qec_decoder_set_priors and qec_decoder_set_pauli_channel: validates and installs the marginal priors (host copy,
+// device buffer, OSD weight tables, every part of a group) together with the correlated form's conditional tables --
+// cond4 = c0_X, c1_X, c0_Z, c1_Z [n each], or nullptr for plain priors (c0 = c1 = the marginal) -- and the channel
+// (pauli3 = pX, pY, pZ [n each], or nullptr: no channel from here on).  `who` names the public call in the texts.
+static int install_priors(qec_decoder* d, const char* who, const float* priorX, const float* priorZ, const float* cond4,
+                          const float* pauli3)
 {
-    if (!d) return fail(QEC_ERR_ARG, "qec_decoder_set_priors: null decoder");
-    if ((priorX == nullptr) != (priorZ == nullptr))
-        return fail(QEC_ERR_ARG, "qec_decoder_set_priors: priorX and priorZ must both be given, or both be NULL (clear)");
-    if (!priorX) {  // clear: the handle behaves as one that never had priors (the device buffer is kept)
-        for (qec_decoder* p : d->parts) p->has_priors = false;
-        d->has_priors = false;
-        return QEC_OK;
-    }
     if (!d->cpu && d->engine != QEC_ENGINE_SPARSE)
         return fail(QEC_ERR_UNSUPPORTED,
-                    "qec_decoder_set_priors: the wave-circulant engine decodes with one error probability (its hard-message "
+                    std::string(who) + ": the wave-circulant engine decodes with one error probability (its hard-message "
                     "shortcuts are proven for one p'); create the decoder with QEC_ENGINE_SPARSE (engine \"sparse\")");
     const int n = d->code->n;
     for (int sec = 0; sec < 2; ++sec) {
         const float* pr = sec ? priorZ : priorX;
         for (int v = 0; v < n; ++v)
             if (!(pr[v] >= 0.0f && pr[v] <= 1.0f))  // a NaN fails both comparisons
-                return fail(QEC_ERR_ARG, std::string("qec_decoder_set_priors: prior") + (sec ? "Z[" : "X[") + std::to_string(v) +
+                return fail(QEC_ERR_ARG, std::string(who) + ": prior" + (sec ? "Z[" : "X[") + std::to_string(v) +
                                              "] = " + std::to_string(pr[v]) + " is not in [0, 1]");
     }
     if (d->odev && d->osd_score == 1 && d->osd_order > 0) {  // the weighted sweep would run from here on
@@ -727,27 +749,138 @@ int qec_decoder_set_priors(qec_decoder* d, const float* priorX, const float* pri
     std::memcpy(host.data() + n, priorZ, n * sizeof(float));
     std::vector<int32_t> wts(host.size());  // the sweep's weight tables (QEC_OPT_OSD_SCORE = 1)
     for (size_t i = 0; i < host.size(); ++i) wts[i] = osd_weight(host[i]);
+    std::vector<float> cond(4 * (size_t)n), pauli;
+    if (cond4) {
+        std::memcpy(cond.data(), cond4, cond.size() * sizeof(float));
+    } else {  // independent marginals carry no correlation: both conditionals are the marginal
+        for (int sec = 0; sec < 2; ++sec)
+            for (int k = 0; k < 2; ++k) std::memcpy(cond.data() + (size_t)(2 * sec + k) * n, sec ? priorZ : priorX, n * sizeof(float));
+    }
+    std::vector<uint64_t> thr;
+    if (pauli3) {
+        pauli.assign(pauli3, pauli3 + 3 * (size_t)n);
+        thr.resize(3 * (size_t)n);
+        for (int v = 0; v < n; ++v) {
+            const double x = pauli3[v], y = pauli3[n + v], z = pauli3[2 * n + v];
+            thr[v] = (uint64_t)(x * 4294967296.0);
+            thr[n + v] = (uint64_t)((x + y) * 4294967296.0);
+            thr[2 * n + v] = (uint64_t)(std::min(1.0, (x + y) + z) * 4294967296.0);
+        }
+    }
     for (qec_decoder* p : d->parts) {
-        const int rc = qec_decoder_set_priors(p, priorX, priorZ);
+        const int rc = install_priors(p, who, priorX, priorZ, cond4, pauli3);
         if (rc) return rc;
     }
     if (d->parts.empty() && !d->cpu) {
         QEC_DEVICE_SCOPE(d->device);
-        // synchronous: the handle's last launch may still read the buffer this call rewrites
+        // synchronous: the handle's last launch may still read the buffers this call rewrites
         QEC_HIP_CHECK(hipStreamSynchronize(d->stream));
         if (d->ws_used) QEC_HIP_CHECK(hipEventSynchronize(d->ws_ev));
         try {
             d->dpri.reserve(host.size());
             d->dosw.reserve(wts.size());
+            d->dcond.reserve(cond.size());
+            if (pauli3) d->dpth.reserve(thr.size());
         } catch (const std::exception& ex) {
-            return fail(QEC_ERR_NOMEM, std::string("qec_decoder_set_priors: ") + ex.what());
+            return fail(QEC_ERR_NOMEM, std::string(who) + ": " + ex.what());
         }
         QEC_HIP_CHECK(hipMemcpy(d->dpri.data(), host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
         QEC_HIP_CHECK(hipMemcpy(d->dosw.data(), wts.data(), wts.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        QEC_HIP_CHECK(hipMemcpy(d->dcond.data(), cond.data(), cond.size() * sizeof(float), hipMemcpyHostToDevice));
+        if (pauli3) QEC_HIP_CHECK(hipMemcpy(d->dpth.data(), thr.data(), thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
     d->priors.swap(host);
     d->osw.swap(wts);
+    d->cond.swap(cond);
+    d->pauli.swap(pauli);
+    d->has_channel = pauli3 != nullptr;
     d->has_priors = true;
+    return QEC_OK;
+}
+
+static void clear_priors(qec_decoder* d)
+{
+    // the handle behaves as one that never had priors or a channel (the device buffers are kept)
+    for (qec_decoder* p : d->parts) p->has_priors = p->has_channel = false;
+    d->has_priors = d->has_channel = false;
+}
+
+int qec_decoder_set_priors(qec_decoder* d, const float* priorX, const float* priorZ)
+{
+    if (!d) return fail(QEC_ERR_ARG, "qec_decoder_set_priors: null decoder");
+    if ((priorX == nullptr) != (priorZ == nullptr))
+        return fail(QEC_ERR_ARG, "qec_decoder_set_priors: priorX and priorZ must both be given, or both be NULL (clear)");
+    if (!priorX) {
+        clear_priors(d);
+        return QEC_OK;
+    }
+    return install_priors(d, "qec_decoder_set_priors", priorX, priorZ, nullptr, nullptr);
+}
+
+int qec_decoder_set_pauli_channel(qec_decoder* d, const float* pX, const float* pY, const float* pZ)
+{
+    if (!d) return fail(QEC_ERR_ARG, "qec_decoder_set_pauli_channel: null decoder");
+    const int nulls = (pX == nullptr) + (pY == nullptr) + (pZ == nullptr);
+    if (nulls == 3) {
+        clear_priors(d);
+        return QEC_OK;
+    }
+    if (nulls) return fail(QEC_ERR_ARG, "qec_decoder_set_pauli_channel: pX, pY and pZ must all be given, or all be NULL (clear)");
+    if (!d->cpu && d->engine != QEC_ENGINE_SPARSE)
+        return fail(QEC_ERR_UNSUPPORTED,
+                    "qec_decoder_set_pauli_channel: the wave-circulant engine decodes with one error probability (its "
+                    "hard-message shortcuts are proven for one p'); create the decoder with QEC_ENGINE_SPARSE (engine \"sparse\")");
+    const int n = d->code->n;
+    const float* arr[3] = {pX, pY, pZ};
+    for (int a = 0; a < 3; ++a)
+        for (int v = 0; v < n; ++v)
+            if (!(arr[a][v] >= 0.0f && arr[a][v] <= 1.0f))  // a NaN fails both comparisons
+                return fail(QEC_ERR_ARG, std::string("qec_decoder_set_pauli_channel: p") + "XYZ"[a] + "[" + std::to_string(v) +
+                                             "] = " + std::to_string(arr[a][v]) + " is not in [0, 1]");
+    std::vector<float> mar(2 * (size_t)n), cond(4 * (size_t)n), pauli(3 * (size_t)n);
+    auto ratio = [](double num, double den) { return den == 0.0 ? 0.5f : (float)std::min(1.0, num / den); };
+    for (int v = 0; v < n; ++v) {
+        const double x = pX[v], y = pY[v], z = pZ[v];
+        if (!((x + y) + z <= 1.0))
+            return fail(QEC_ERR_ARG, "qec_decoder_set_pauli_channel: pX[" + std::to_string(v) + "] + pY[" + std::to_string(v) +
+                                         "] + pZ[" + std::to_string(v) + "] = " + std::to_string((x + y) + z) + " is above 1");
+        mar[v] = (float)(x + y);
+        mar[n + v] = (float)(z + y);
+        cond[v] = ratio(x, 1.0 - (z + y));          // cX0
+        cond[n + v] = ratio(y, z + y);              // cX1
+        cond[2 * n + v] = ratio(z, 1.0 - (x + y));  // cZ0
+        cond[3 * n + v] = ratio(y, x + y);          // cZ1
+        pauli[v] = pX[v]; pauli[n + v] = pY[v]; pauli[2 * n + v] = pZ[v];
+    }
+    return install_priors(d, "qec_decoder_set_pauli_channel", mar.data(), mar.data() + n, cond.data(), pauli.data());
+}
+
+int qec_decoder_get_pauli_channel(const qec_decoder* d, float* pX, float* pY, float* pZ)
+{
+    if (!d) return fail(QEC_ERR_ARG, "qec_decoder_get_pauli_channel: null decoder");
+    if (!d->has_channel) return 0;
+    const int n = d->code->n;
+    float* out[3] = {pX, pY, pZ};
+    for (int a = 0; a < 3; ++a)
+        if (out[a]) std::memcpy(out[a], d->pauli.data() + (size_t)a * n, n * sizeof(float));
+    return 1;
+}
+
+int qec_decoder_get_conditional_priors(const qec_decoder* d, float* cZ0, float* cZ1, float* cX0, float* cX1)
+{
+    if (!d) return fail(QEC_ERR_ARG, "qec_decoder_get_conditional_priors: null decoder");
+    if (!d->has_channel) return 0;
+    const int n = d->code->n;
+    float* out[4] = {cX0, cX1, cZ0, cZ1};  // the tables' order in the handle
+    for (int a = 0; a < 4; ++a)
+        if (out[a]) std::memcpy(out[a], d->cond.data() + (size_t)a * n, n * sizeof(float));
+    return 1;
+}
+
+int qec_correlated_priors(float p, float* c0, float* c1)
+{
+    if (!c0 || !c1) return fail(QEC_ERR_ARG, "qec_correlated_priors: bad argument");
+    correlated_priors(p, c0, c1);
     return QEC_OK;
 }
 
@@ -795,6 +928,7 @@ int qec_decoder_get_option(const qec_decoder* d, int option, int* value)
     }
     case QEC_OPT_OSD_ORDER: *value = d->osd_order; return QEC_OK;
     case QEC_OPT_OSD_SCORE: *value = d->osd_score; return QEC_OK;
+    case QEC_OPT_CORRELATED: *value = d->correlated; return QEC_OK;
     case QEC_OPT_OSD_CS_SECTORS: {
         unsigned long long t = d->osd_cs_sectors;
         for (const qec_decoder* p : d->parts) t += p->osd_cs_sectors;
@@ -867,7 +1001,15 @@ int dispatch_decode(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, long l
                 return rc;
             eX = d->eX.data(); eZ = d->eZ.data(); flags = d->flags.data();
         }
-        rc = launch_decode_sparse(d->sparse, sX, sZ, B, p, maxIter, stop, eX, eZ, flags, iters, q, st, d->prior_dev());
+        // QEC_OPT_CORRELATED, read at the call: the CORR kernels, with the handle's conditional tables or the scalar pair
+        const int corr = d->correlated;
+        float c0 = 0.0f, c1 = 0.0f;
+        if (corr) {
+            correlated_priors(p, &c0, &c1);
+            d->last_path |= QEC_PATH_CORRELATED;
+        }
+        rc = launch_decode_sparse(d->sparse, sX, sZ, B, p, maxIter, stop, eX, eZ, flags, iters, q, st, d->prior_dev(), corr,
+                                  d->cond_dev(), c0, c1);
         if (!rc && rec != nullptr) rc = launch_pack_decisions(eX, eZ, flags, B, c.n, rec, st);
         if (rc) return rc;
         return ws_release(d, st);
@@ -1042,7 +1184,7 @@ int osd_repair_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t
             cFs.resize(cnt);
             const int rc = cpu_decode_batch(d->cpu, cX.data(), cZ.data(), (long long)cnt, p, d->osd_iters, QEC_STOP_FIXED,
                                             cEX.data(), cEZ.data(), cFs.data(), nullptr, nullptr, cq.data(), 0,
-                                            false, d->prior_host());
+                                            false, d->prior_host(), d->correlated, d->cond_host());
             if (rc) return rc;
             long long swept = 0;
             osd_host_batch(*d->oplan, cX.data(), cZ.data(), (long long)cnt, cq.data(), cEX.data(), cEZ.data(), cF.data(), 0,
@@ -1160,8 +1302,8 @@ int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
     if (B == 0) return QEC_OK;
     if (d->cpu) {
         const int rc = cpu_decode_batch(d->cpu, sX, sZ, (long long)B, p, maxIter, stop, eX, eZ, flags, rec, iters, q, 0,
-                                        d->hard_paths && d->near_hard, d->prior_host());
-        d->last_path = 0;
+                                        d->hard_paths && d->near_hard, d->prior_host(), d->correlated, d->cond_host());
+        d->last_path = d->correlated ? QEC_PATH_CORRELATED : 0;
         return rc || !d->osd ? rc : osd_repair_host(d, sX, sZ, B, p, eX, eZ, flags, rec);
     }
     QEC_DEVICE_SCOPE(d->device);
@@ -1462,9 +1604,11 @@ int monte_carlo_part(qec_decoder* d, uint64_t seed, uint64_t start, uint64_t cou
         McArgsHost h;
         h.seed = seed; h.start = start + base; h.p = p;
         h.prior = d->prior_dev();
+        h.pauli_thr = d->has_channel ? d->dpth.data() : nullptr;
         h.B = (long long)std::min<uint64_t>(batch, count - base);
-        // priors set: the independent sampler over them; mc_batch then takes the unfused byte-syndrome pipeline
-        rc = mc_batch(d, h, d->has_priors ? MC_SRC_INDEPENDENT : MC_SRC_PHILOX, p, maxIter, stop, true, d->mc_time ? ev.ev[2 * slot] : nullptr,
+        // priors set: the independent sampler over them (a Pauli channel: its own sampler); mc_batch then takes
+        // the unfused byte-syndrome pipeline
+        rc = mc_batch(d, h, d->has_channel ? MC_SRC_PAULI : d->has_priors ? MC_SRC_INDEPENDENT : MC_SRC_PHILOX, p, maxIter, stop, true, d->mc_time ? ev.ev[2 * slot] : nullptr,
                       d->mc_time ? ev.ev[2 * slot + 1] : nullptr, k == 0);
         if (rc) return rc;
     }
@@ -1512,7 +1656,7 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
         fl.resize(cnt);
         const int rc = cpu_decode_batch(d->cpu, sx.data(), sz.data(), cnt, p, maxIter, QEC_STOP_REF, ex.data(), ez.data(),
                                         fl.data(), nullptr, nullptr, nullptr, 0, d->hard_paths && d->near_hard,
-                                        d->prior_host());
+                                        d->prior_host(), d->correlated, d->cond_host());
         if (rc) return rc;
         if (d->osd) {  // the counters describe the repaired estimates
             d->osd_sectors = 0;
@@ -1546,7 +1690,7 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
     }
     d->osd_sectors = repaired;
     d->osd_cs_sectors = swept;
-    d->last_path = d->osd ? QEC_PATH_OSD : 0;
+    d->last_path = (d->osd ? QEC_PATH_OSD : 0) | (d->correlated ? QEC_PATH_CORRELATED : 0);
     std::memset(out, 0, sizeof *out);
     out->randSeed = seed;
     out->numErrorsTested = (uint32_t)tested;
@@ -1735,6 +1879,17 @@ int qec_sample_independent_dev(qec_decoder* d, uint64_t seed, uint64_t start, si
                                      static_cast<hipStream_t>(stream));
 }
 
+int qec_sample_pauli_dev(qec_decoder* d, uint64_t seed, uint64_t start, size_t B, uint8_t* x, uint8_t* z, void* stream)
+{
+    if (!d || (B && (!x || !z))) return fail(QEC_ERR_ARG, "qec_sample_pauli_dev: bad argument");
+    int rc = single_device_only(d, "qec_sample_pauli_dev");
+    if (rc) return rc;
+    if (!d->has_channel || d->cpu)
+        return fail(QEC_ERR_ARG, "qec_sample_pauli_dev: the decoder has no Pauli channel (qec_decoder_set_pauli_channel)");
+    QEC_DEVICE_SCOPE(d->device);
+    return launch_sample_pauli(seed, start, (long long)B, d->code->n, d->dpth.data(), x, z, static_cast<hipStream_t>(stream));
+}
+
 int qec_sample_syndrome_dev(qec_decoder* d, uint64_t seed, uint64_t start, size_t B, float p, uint8_t* sX, uint8_t* sZ,
                             uint8_t* errp, void* stream)
 {
@@ -1750,7 +1905,9 @@ int qec_sample_syndrome_dev(qec_decoder* d, uint64_t seed, uint64_t start, size_
     h.varEdge = variable_table(d);
     h.B = (long long)B;
     h.prior = d->prior_dev();
-    return launch_mc_errors_syndrome(d->has_priors ? MC_SRC_INDEPENDENT : MC_SRC_PHILOX, h, static_cast<hipStream_t>(stream));
+    h.pauli_thr = d->has_channel ? d->dpth.data() : nullptr;
+    return launch_mc_errors_syndrome(d->has_channel ? MC_SRC_PAULI : d->has_priors ? MC_SRC_INDEPENDENT : MC_SRC_PHILOX, h,
+                                     static_cast<hipStream_t>(stream));
 }
 
 int qec_syndrome_dev(qec_decoder* d, const uint8_t* x, const uint8_t* z, size_t B, uint8_t* sX, uint8_t* sZ,

@@ -332,11 +332,26 @@ int cpu_threads()
     return h ? (int)h : 1;
 }
 
+// The scalar tables of the correlated form (qec_correlated_priors): P(other bit | this bit clear) and
+// P(other bit | this bit set) under depolarising noise of strength p, every operation in fp32 (this unit is
+// built with -ffp-contract=off).  Both engines decode with these values.
+void correlated_priors(float p, float* c0, float* c1)
+{
+    const float marginal = 2.0f / 3.0f * p;
+    const float clear = 1.0f - marginal;
+    *c0 = (p / 3.0f) / clear;
+    *c1 = 0.5f;
+}
+
 // Batched Decode on host buffers; outputs in byte form (eX, eZ, flags) and/or packed records.
 // prior: nullptr, or the handle's priors (n floats of sector X, then n of sector Z); p is then unused.
+// corr (QEC_OPT_CORRELATED): 0, or 1 / 2 = the correlated form with first sector X / Z -- the first sector as
+// under 0, the second by the prior form with pi_v = d[v] ? c1[v] : c0[v], d the first sector's estimate; cond
+// (with prior) = the tables c0_X [n], c1_X [n], c0_Z [n], c1_Z [n], without prior the pair correlated_priors(p).
+// The near-hard jump never fires for the second sector.
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
-                     bool near_hard, const float* prior)
+                     bool near_hard, const float* prior, int corr, const float* cond)
 {
     const CpuPlan& P = *static_cast<const CpuPlan*>(plan);
     const int n = P.n, nb = (n + 7) / 8;
@@ -346,24 +361,38 @@ int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long
     uint32_t nearT[2] = {0u, 0u};
     if (near_hard && !prior && !P.general && qf == nullptr && stop != QEC_STOP_SYNDROME)
         for (int sec = 0; sec < 2; ++sec) nearT[sec] = near_hard_threshold((2.0f / 3.0f) * p, P.sec[sec].dv, P.sec[sec].dc).T;
+    if (corr && prior && !cond) return fail(QEC_ERR_ARG, "CPU engine: the correlated form needs its conditional tables");
+    float sc0 = 0.0f, sc1 = 0.0f;
+    if (corr) correlated_priors(p, &sc0, &sc1);
     if (threads <= 0) threads = cpu_threads();
     threads = (int)std::max<long long>(1, std::min<long long>(threads, B));
     auto run = [&](long long lo, long long hi) {
         Work w;
+        std::vector<uint8_t> first(corr ? n : 0);  // the first sector's estimate
+        std::vector<float> pi(corr ? n : 0);       // the second sector's priors of this sample
         const size_t E = std::max((size_t)mX * P.sec[0].dc, (size_t)mZ * P.sec[1].dc);
         w.q.resize(E);
         w.r.resize(E);
         w.e.resize(n);
         for (long long b = lo; b < hi; ++b) {
             uint8_t f = 0;
-            for (int sec = 0; sec < 2; ++sec) {
+            for (int pass = 0; pass < 2; ++pass) {
+                const int sec = corr == 2 ? 1 - pass : pass;
                 const CpuSector& S = P.sec[sec];
                 bool conv = false, ok = false;
                 float* qo = qf ? qf + b * qper + (sec ? (size_t)mX * P.sec[0].dc : 0) : nullptr;
                 const uint8_t* syn = sec ? sZ + b * mZ : sX + b * mX;
                 const float* pri = prior ? prior + (size_t)sec * n : nullptr;
+                const bool second = corr && pass == 1;
+                if (second) {
+                    const float* t0 = cond ? cond + (size_t)sec * 2 * n : nullptr;
+                    for (int v = 0; v < n; ++v) pi[v] = first[v] ? (cond ? t0[n + v] : sc1) : (cond ? t0[v] : sc0);
+                    pri = pi.data();
+                }
                 const int it = P.general ? decode_sector_general(S, n, syn, p, pri, maxIter, stop, w, conv, ok, qo)
-                                         : decode_sector(S, n, syn, p, pri, maxIter, stop, w, conv, ok, qo, nearT[sec]);
+                                         : decode_sector(S, n, syn, p, pri, maxIter, stop, w, conv, ok, qo,
+                                                         second ? 0u : nearT[sec]);
+                if (corr && pass == 0) std::memcpy(first.data(), w.e.data(), n);
                 if (!ok) f |= sec ? QEC_SYNDROME_FAIL_Z : QEC_SYNDROME_FAIL_X;
                 if (!conv) f |= sec ? QEC_CONVERGENCE_FAIL_Z : QEC_CONVERGENCE_FAIL_X;
                 if (iters) iters[2 * b + sec] = it;

@@ -147,6 +147,7 @@ __global__ void pack_decisions_kernel(const uint8_t* __restrict__ eX, const uint
 //   source BYTES:  x, z rows [B][n] from HBM;
 //   source INDEPENDENT: the independent X / Z sampler over the handle's priors (qec_mc.h, indep_call):
 //                  lanes go over the sample's Philox calls, each call covers two qubits.
+//   source PAULI:  the Pauli-channel sampler (qec_mc.h, pauli_call): each call covers four qubits.
 // Then, from LDS: the syndromes sX, sZ (QC: s(r, i) = XOR_l e[l P + (E[r][l] + i) mod P]; any other
 // regular code: the check's variables from the sparse engine's table), and the bit-packed errors
 // errp [B][2 nb] in the decision-record layout (x bits, then z bits) for the statistics kernel.
@@ -161,6 +162,7 @@ struct McArgs {
     const uint8_t* x;                          // BYTES: [B][n]
     const uint8_t* z;
     const float* prior;                        // INDEPENDENT: priors of sector X [n], then Z [n]
+    const uint64_t* pauli_thr;                 // PAULI: thresholds tX [n], tXY [n], tXYZ [n]
     uint64_t seed, start;                      //              sample b0 + s is index start + b0 + s of stream seed
     // outputs
     uint8_t* sX;                               // [B][mX]
@@ -215,6 +217,16 @@ __global__ __launch_bounds__(64 * kMcWaves) void mc_errors_syndrome_kernel(const
             uint8_t* ex = stage + (size_t)sI * 2 * npad;
             *reinterpret_cast<uint16_t*>(ex + 2 * k) = (uint16_t)((r & 1u) | ((r >> 2) & 1u) << 8);
             *reinterpret_cast<uint16_t*>(ex + npad + 2 * k) = (uint16_t)(((r >> 1) & 1u) | ((r >> 3) & 1u) << 8);
+        }
+    } else if constexpr (SRC == MC_SRC_PAULI) {
+        const int nc = npad / 4;  // calls per staged row pair: the padding qubits (>= n) come out 0
+        for (int t = lane; t < ns * nc; t += 64) {
+            const int sI = qdiv(t, a.magicG), k = t - sI * nc;
+            const uint32_t r = pauli_call(a.seed, a.start + (uint64_t)(b0 + sI), k, n, a.pauli_thr);
+            uint8_t* ex = stage + (size_t)sI * 2 * npad;
+            *reinterpret_cast<uint32_t*>(ex + 4 * k) = (r & 1u) | ((r >> 1) & 1u) << 8 | ((r >> 2) & 1u) << 16 | ((r >> 3) & 1u) << 24;
+            *reinterpret_cast<uint32_t*>(ex + npad + 4 * k) =
+                ((r >> 4) & 1u) | ((r >> 5) & 1u) << 8 | ((r >> 6) & 1u) << 16 | ((r >> 7) & 1u) << 24;
         }
     } else {
         for (int t = lane; t < ns * npad; t += 64) {
@@ -727,6 +739,28 @@ __global__ __launch_bounds__(64 * kIndepWaves) void sample_independent_kernel(ui
     }
 }
 
+// byte form of the Pauli-channel sampler (qec_sample_pauli_dev): as sample_independent_kernel, call k writes
+// x[4k .. 4k + 3] and z[4k .. 4k + 3] of the sample's HBM rows
+__global__ __launch_bounds__(64 * kIndepWaves) void sample_pauli_kernel(uint64_t seed, uint64_t start, long long B, int n,
+                                                                       const uint64_t* __restrict__ thr,
+                                                                       uint8_t* __restrict__ x, uint8_t* __restrict__ z)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nc = (n + 3) / 4;
+    for (long long s = (long long)blockIdx.x * kIndepWaves + wv; s < B; s += (long long)gridDim.x * kIndepWaves) {
+        uint8_t* __restrict__ xr = x + s * n;
+        uint8_t* __restrict__ zr = z + s * n;
+        for (int k = lane; k < nc; k += 64) {
+            const uint32_t r = pauli_call(seed, start + (uint64_t)s, k, n, thr);
+            for (int j = 0; j < 4; ++j)
+                if (4 * k + j < n) {
+                    xr[4 * k + j] = (uint8_t)((r >> j) & 1u);
+                    zr[4 * k + j] = (uint8_t)((r >> (4 + j)) & 1u);
+                }
+        }
+    }
+}
+
 // ---- launchers --------------------------------------------------------------
 static int launch_check(const char* what)
 {
@@ -754,6 +788,15 @@ int launch_sample_independent(uint64_t seed, uint64_t start, long long B, int n,
     hipLaunchKernelGGL(sample_independent_kernel, dim3((unsigned)blocks), dim3(64 * kIndepWaves), 0, st, seed, start, B, n,
                        prior, x, z);
     return launch_check("sample_independent");
+}
+
+int launch_sample_pauli(uint64_t seed, uint64_t start, long long B, int n, const uint64_t* thr, uint8_t* x, uint8_t* z,
+                        hipStream_t st)
+{
+    if (B <= 0) return QEC_OK;
+    const long long blocks = std::min<long long>((B + kIndepWaves - 1) / kIndepWaves, 1 << 16);
+    hipLaunchKernelGGL(sample_pauli_kernel, dim3((unsigned)blocks), dim3(64 * kIndepWaves), 0, st, seed, start, B, n, thr, x, z);
+    return launch_check("sample_pauli");
 }
 
 static uint32_t magic_of(long long d) { return d > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d) : 0u; }
@@ -821,6 +864,8 @@ int launch_mc_errors_syndrome(int src, const McArgsHost& h, hipStream_t st)
     a.x = h.x; a.z = h.z;
     a.prior = h.prior; a.seed = h.seed; a.start = h.start;
     if (src == MC_SRC_INDEPENDENT && h.prior == nullptr) return fail(QEC_ERR_ARG, "mc front end: the independent sampler needs priors");
+    a.pauli_thr = h.pauli_thr;
+    if (src == MC_SRC_PAULI && h.pauli_thr == nullptr) return fail(QEC_ERR_ARG, "mc front end: the Pauli sampler needs a channel");
     a.sX = h.sX; a.sZ = h.sZ; a.errp = h.errp;
     a.chkVar = h.chkVar;
     a.B = h.B;
@@ -852,6 +897,8 @@ int launch_mc_errors_syndrome(int src, const McArgsHost& h, hipStream_t st)
         QEC_MC_LAUNCH(MC_SRC_DRAWS);
     else if (src == MC_SRC_INDEPENDENT)
         QEC_MC_LAUNCH(MC_SRC_INDEPENDENT);
+    else if (src == MC_SRC_PAULI)
+        QEC_MC_LAUNCH(MC_SRC_PAULI);
     else
         QEC_MC_LAUNCH(MC_SRC_BYTES);
 #undef QEC_MC_LAUNCH

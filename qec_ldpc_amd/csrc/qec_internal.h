@@ -82,7 +82,8 @@ struct Mt19937 {
 // Host description of a fused Monte-Carlo front-end launch (montecarlo.hip,
 // mc_errors_syndrome_kernel, or mc_gap_kernel for PHILOX): error source (MC_SRC_*), syndromes out,
 // packed errors out.
-enum { MC_SRC_PHILOX = 0, MC_SRC_DRAWS = 1, MC_SRC_BYTES = 2, MC_SRC_INDEPENDENT = 3 /* over the handle's priors */ };
+enum { MC_SRC_PHILOX = 0, MC_SRC_DRAWS = 1, MC_SRC_BYTES = 2, MC_SRC_INDEPENDENT = 3 /* over the handle's priors */,
+       MC_SRC_PAULI = 4 /* the handle's Pauli channel */ };
 // the fused low-p Monte-Carlo pipeline's stages (triage.hip, launch_mc_fused)
 enum { MC_FUSED_SAMPLE = 0, MC_FUSED_SURVIVORS = 1 };
 struct McArgsHost {
@@ -95,6 +96,7 @@ struct McArgsHost {
     const uint8_t* x = nullptr;     // BYTES
     const uint8_t* z = nullptr;
     const float* prior = nullptr;   // INDEPENDENT (with seed, start): device priors, sector X [n] then Z [n]
+    const uint64_t* pauli_thr = nullptr;  // PAULI (with seed, start): device thresholds tX [n], tXY [n], tXYZ [n]
     uint8_t* sX = nullptr;
     uint8_t* sZ = nullptr;
     uint32_t* sXp = nullptr;        // PHILOX only: syndromes as bit rows [B][ceil(mX/32)] words instead

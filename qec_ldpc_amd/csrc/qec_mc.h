@@ -143,6 +143,32 @@ __device__ __forceinline__ uint32_t indep_call(uint64_t seed, uint64_t b, int k,
     return r;
 }
 
+// Pauli-channel sampler (qec_sample_pauli_dev; a handle with qec_decoder_set_pauli_channel).  Sample b makes
+// Philox calls k = 0, 1, ... with counter (b_lo, b_hi, k, kPauliSalt), key (seed_lo, seed_hi); output word j of
+// call k is the word u of qubit 4k + j: x = u < tXY, z = tX <= u < tXYZ (X below tX, Y up to tXY, Z up to tXYZ).
+// thr: the 64-bit thresholds tX [n], tXY [n], tXYZ [n] the host forms in double from the floats.
+constexpr uint32_t kPauliSalt = 0x3C6EF372u;
+
+// Call k of sample b as bits 0..3 = x[4k .. 4k + 3], bits 4..7 = z[4k .. 4k + 3] (a qubit >= n gives 0).
+__device__ __forceinline__ uint32_t pauli_call(uint64_t seed, uint64_t b, int k, int n, const uint64_t* __restrict__ thr)
+{
+    const int v0 = 4 * k;
+    if (v0 >= n) return 0u;
+    const U4 o = philox4x32_10(U4{(uint32_t)b, (uint32_t)(b >> 32), (uint32_t)k, kPauliSalt}, (uint32_t)seed,
+                               (uint32_t)(seed >> 32));
+    const uint32_t u[4] = {o.x, o.y, o.z, o.w};
+    uint32_t r = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int v = v0 + j;
+        if (v < n) {
+            const uint64_t w = u[j];
+            r |= (uint32_t)(w < thr[n + v]) << j | (uint32_t)(w >= thr[v] && w < thr[2 * n + v]) << (4 + j);
+        }
+    }
+    return r;
+}
+
 // counters, in qec_mc_counters order
 enum { C_WITHX, C_WITHZ, C_SYNX, C_SYNZ, C_LOGICAL, C_CORRECTED, C_CONVX, C_CONVZ, C_N };
 

@@ -35,6 +35,12 @@
 //                      used; --rng philox draws its errors independently per qubit from them.  Sparse-graph and
 //                      CPU engines: on a code the default engine decodes with wave-circulant kernels the run
 //                      fails with the library's message (use --engine sparse)
+//   --correlated xz|zx the correlated form (QEC_OPT_CORRELATED): sector X first and sector Z under priors conditioned
+//                      on the X estimate (xz), or Z first (zx).  Sparse-graph and CPU engines
+//   --pauli FILE       per-qubit Pauli channel (qec_decoder_set_pauli_channel): FILE holds three lines of n decimal
+//                      floats, pX, pY and pZ.  BP decodes under its marginals (and --correlated under its conditional
+//                      tables), the init file's p is not used, and --rng philox draws its errors from the channel.
+//                      Not together with --priors
 // Unknown or inconsistent flags exit with status 2.
 #include <algorithm>
 #include <chrono>
@@ -82,7 +88,8 @@ int usage(const std::string& why)
     std::cerr << why << std::endl
               << "usage: qec_ldpc [--engine gpu|sparse|cpu] [--gpus N | --devices i,j,...] [--rng msvc|philox]"
                  " [--stop ref|fixed|syndrome] [--batch B] [--seed S] [--logical file|reference|degenerate]"
-                 " [--osd 0 [--osd-order L] [--osd-iterations K] [--osd-score hamming|priors]] [--priors FILE] initFile"
+                 " [--osd 0 [--osd-order L] [--osd-iterations K] [--osd-score hamming|priors]] [--priors FILE]"
+                 " [--correlated xz|zx] [--pauli FILE] initFile"
               << std::endl;
     return 2;
 }
@@ -103,6 +110,22 @@ void read_priors(const std::string& path, int n, std::vector<float>& pX, std::ve
     }
 }
 
+// --pauli FILE: three lines of n decimal floats (pX, pY, pZ)
+void read_pauli(const std::string& path, int n, std::vector<float> (&out)[3])
+{
+    std::ifstream in(path);
+    if (!in.is_open()) throw std::string("--pauli: unable to open " + path);
+    std::string line;
+    for (std::vector<float>& o : out) {
+        if (!std::getline(in, line)) throw std::string("--pauli: " + path + " needs three lines of n floats (pX, pY, pZ)");
+        std::stringstream ss(line);
+        float v;
+        while (ss >> v) o.push_back(v);
+        if (!ss.eof() || (int)o.size() != n)
+            throw std::string("--pauli: each line of " + path + " needs n = " + std::to_string(n) + " decimal floats");
+    }
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -115,7 +138,8 @@ int main(int argc, char** argv)
     std::time_t ts = std::chrono::system_clock::to_time_t(std::chrono::system_clock::now());
     log << std::endl << std::ctime(&ts);
     std::vector<int> devices{0};
-    std::string engine = "gpu", rng = "msvc", stopName = "ref", logical = "file", priorsFile;
+    std::string engine = "gpu", rng = "msvc", stopName = "ref", logical = "file", priorsFile, pauliFile;
+    int correlated = 0;
     bool deviceFlag = false, stopFlag = false, batchFlag = false, seedFlag = false, osd = false, osdIterFlag = false;
     bool osdOrderFlag = false, osdScoreFlag = false;
     int osdScore = 0;
@@ -174,6 +198,11 @@ int main(int argc, char** argv)
                 osdScoreFlag = true;
             } else if (flag == "--priors") {
                 priorsFile = val;
+            } else if (flag == "--pauli") {
+                pauliFile = val;
+            } else if (flag == "--correlated") {
+                if (val != "xz" && val != "zx") return usage("--correlated: xz or zx");
+                correlated = val == "xz" ? 1 : 2;
             } else if (flag == "--seed") {
                 seed = std::stoull(val, nullptr, 0);
                 seedFlag = true;
@@ -191,6 +220,7 @@ int main(int argc, char** argv)
     if (osdIterFlag && !osd) return usage("--osd-iterations needs --osd 0");
     if (osdOrderFlag && !osd) return usage("--osd-order needs --osd 0");
     if (osdScoreFlag && !osd) return usage("--osd-score needs --osd 0");
+    if (!pauliFile.empty() && !priorsFile.empty()) return usage("--pauli and --priors exclude each other");
     if (osdScore == 1 && priorsFile.empty()) return usage("--osd-score priors needs --priors FILE");
     if (argc - a != 1 || devices.empty()) {
         log << "Must provide initialization file." << std::endl;
@@ -224,6 +254,8 @@ int main(int argc, char** argv)
         }
         std::vector<float> priorX, priorZ;
         if (!priorsFile.empty()) read_priors(priorsFile, code.n, priorX, priorZ);
+        std::vector<float> pauli[3];
+        if (!pauliFile.empty()) read_pauli(pauliFile, code.n, pauli);
         if (rng == "philox") {
             std::unique_ptr<DecoderGPU> dp(engine == "sparse" ? new DecoderGPU(code, 0, QEC_ENGINE_SPARSE)
                                                                : new DecoderGPU(code, devices));
@@ -231,6 +263,8 @@ int main(int argc, char** argv)
             if (osd) decoder.SetOsd(osdOrder, osdIterations);
             if (osd) decoder.SetOsdScore(osdScore);
             if (!priorsFile.empty()) decoder.SetPriors(priorX, priorZ);
+            if (!pauliFile.empty()) decoder.SetPauliChannel(pauli[0], pauli[1], pauli[2]);
+            if (correlated) decoder.SetCorrelated(correlated);
             std::cout << "Engine: " << decoder.Describe() << std::endl;
             const int stop = stopName == "ref" ? QEC_STOP_REF : stopName == "fixed" ? QEC_STOP_FIXED : QEC_STOP_SYNDROME;
             std::stringstream fileName;
@@ -255,6 +289,8 @@ int main(int argc, char** argv)
             if (osd) c->SetOsd(osdOrder, osdIterations);
             if (osd) c->SetOsdScore(osdScore);
             if (!priorsFile.empty()) c->SetPriors(priorX, priorZ);
+            if (!pauliFile.empty()) c->SetPauliChannel(pauli[0], pauli[1], pauli[2]);
+            if (correlated) c->SetCorrelated(correlated);
             std::cout << "Engine: CPU (" << std::thread::hardware_concurrency() << " threads)" << std::endl;
         } else {
             DecoderGPU* g = engine == "sparse" ? new DecoderGPU(code, 0, QEC_ENGINE_SPARSE) : new DecoderGPU(code, devices);
@@ -262,6 +298,8 @@ int main(int argc, char** argv)
             if (osd) g->SetOsd(osdOrder, osdIterations);
             if (osd) g->SetOsdScore(osdScore);
             if (!priorsFile.empty()) g->SetPriors(priorX, priorZ);
+            if (!pauliFile.empty()) g->SetPauliChannel(pauli[0], pauli[1], pauli[2]);
+            if (correlated) g->SetCorrelated(correlated);
             std::cout << "Engine: " << g->Describe() << std::endl;
         }
         for (; w <= W; ++w) {
