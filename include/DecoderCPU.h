@@ -85,6 +85,9 @@ public:
     // The correlated form (QEC_OPT_CORRELATED): 0 = both sectors independently (the default), 1 = sector X first and
     // sector Z under priors conditioned on the X estimate, 2 = Z first.  Any other value throws the library's message.
     void SetCorrelated(int order) override { check(qec_decoder_set_option(dec_, QEC_OPT_CORRELATED, order)); }
+    // The BP schedule (QEC_OPT_BP_SCHEDULE): 0 = flooding (the default), 1 = the serial (layered) schedule.  Any other
+    // value, and 1 together with SetCorrelated(1 | 2), throws the library's message.
+    void SetBpSchedule(int schedule) override { check(qec_decoder_set_option(dec_, QEC_OPT_BP_SCHEDULE, schedule)); }
     // Per-qubit Pauli channel (qec_decoder_set_pauli_channel): qubit v suffers X, Y or Z with probabilities pX[v],
     // pY[v], pZ[v] (n entries each; Y sets both bits).  Installs the marginal priors, the conditional tables of
     // SetCorrelated and the noise of the device Monte-Carlo run; a later SetPriors or ClearPriors drops it.

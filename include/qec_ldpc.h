@@ -116,6 +116,11 @@ qec_code* qec_code_from_matrices(int n, int mX, const uint8_t* HX, int mZ, const
 /* out[5] = largest row weight of HX, of HZ, largest column weight of HX, of HZ, and the slot stride
  * D = the larger row weight.  Any code; a regular one gives L, L, J, K, L. */
 int qec_code_degrees(const qec_code* code, int* out5);
+/* The layers of the serial BP schedule (QEC_OPT_BP_SCHEDULE) for one sector: walking the sector's checks in
+ * ascending index, check c gets the smallest colour l >= 0 such that no check already coloured l shares a
+ * variable with c.  colour: numEqs entries, nullable.  Returns the number of layers (< 0 on error).  Checks of
+ * one colour share no variable; a circulant-permutation QC code gives colour c / P. */
+int qec_code_layers(const qec_code* code, int sector, int32_t* colour);
 /* Replaces the QC_LDPC_CSS(J,K,L,P,sigma,tau) generator (QEC_LDPC/QEC_LDPC_CSS.cu:5-131).
  * Generated codes carry no I-P matrix (the reference never generates one); qec_code_with_logical
  * derives the check from the two matrices. */
@@ -328,12 +333,35 @@ int qec_decoder_device(const qec_decoder* dec);         /* HIP device ordinal (o
  *     QEC_ERR_UNSUPPORTED and the text says to create the decoder with QEC_ENGINE_SPARSE.  Every decode entry
  *     point honours it, the _dev ones read it at the call (a captured graph keeps the kernels it captured), the
  *     OSD stage's soft decode goes through the same path; QEC_OPT_OSD_SCORE = 1 keeps scoring with the marginal
- *     tables and S is not decoded again after OSD repairs F.  A group applies the value to every part. */
+ *     tables and S is not decoded again after OSD repairs F.  A group applies the value to every part.
+ *   QEC_OPT_BP_SCHEDULE (default 0; 0 or 1, other values QEC_ERR_ARG): the order of BP's updates (not the dispatch
+ *     order of QEC_OPT_SCHEDULE).  0 = flooding, all checks and then all variables, as ever (the same kernels).
+ *     1 = the serial (layered, check-sequential) schedule of DESIGN.md section 2: the state is one check->variable
+ *     message R per real edge, 0.5f at the start (an unused slot of a general code +0.0f throughout).  An
+ *     iteration takes the sector's checks in the order of qec_code_layers, sorted by (colour, index); check c
+ *     forms, for each of its slots in ascending order, the message of the slot's variable v from pi_v and the R of
+ *     v's OTHER checks as they stand (two running products from 1.0f - pi_v and pi_v in ascending check order,
+ *     then P1 / (P0 + P1); pi_v = the prior of v, or p' = 2.0f / 3.0f * p), and then its own R by the check update
+ *     of the flooding schedule.  The posterior of v is the same form over ALL its checks; its decision is
+ *     posterior >= 0.5f; a variable in no check decides 0 and enters no test.  Stop rules over the posteriors:
+ *     FIXED N iterations; SYNDROME after the first iteration whose decisions satisfy the syndrome; REF after an
+ *     iteration with index % 10 == 0 that leaves no posterior inside (0.01, 0.99).  There is no special last
+ *     iteration.  CONVERGENCE_FAIL: a posterior of the final state inside (0.01, 0.99); SYNDROME_FAIL from the
+ *     final decisions; q_final: every real slot of v holds v's final posterior; N = 0 gives the posterior of the
+ *     initial state.  Sparse-graph engine (the SERIAL kernels of bp_sparse.hip; plan, workspace, grid and describe
+ *     string unchanged; the layer tables are uploaded when the plan is created, so setting the option allocates
+ *     nothing) and CPU engine; a wave-circulant handle refuses 1 with QEC_ERR_UNSUPPORTED and the text says to
+ *     create the decoder with QEC_ENGINE_SPARSE.  1 together with QEC_OPT_CORRELATED != 0 is refused with
+ *     QEC_ERR_UNSUPPORTED by whichever qec_decoder_set_option comes second (the handle stays as it was).  Every
+ *     decode entry point honours it, the _dev ones read it at the call (a captured graph keeps the kernels it
+ *     captured); the OSD stage's soft decode runs the same schedule, so the stage's result then also depends on
+ *     the schedule (its column key reads q_final, here the posterior).  The near-hard jump never fires under 1.
+ *     A group applies the value to every part. */
 enum { QEC_OPT_HARD_PATHS = 1, QEC_OPT_CYCLE_JUMP = 2, QEC_OPT_SCHEDULE = 3, QEC_OPT_SECTOR_SPLIT = 4,
        QEC_OPT_PHASE_STATS = 5, QEC_OPT_TRIAGE = 6, QEC_OPT_LAST_PATH = 7, QEC_OPT_MC_DECODE_TIME = 8,
        QEC_OPT_OSD = 9, QEC_OPT_OSD_ITERATIONS = 10, QEC_OPT_OSD_SECTORS = 11, QEC_OPT_OSD_SWEEP = 12,
        QEC_OPT_OSD_ORDER = 13, QEC_OPT_OSD_CS_SECTORS = 14, QEC_OPT_NEAR_HARD_JUMP = 15, QEC_OPT_OSD_SCORE = 16,
-       QEC_OPT_CORRELATED = 17 };
+       QEC_OPT_CORRELATED = 17, QEC_OPT_BP_SCHEDULE = 18 };
 enum {
     QEC_PATH_ORDERED = 1,          /* dispatch order pass (schedule.hip) */
     QEC_PATH_SECTOR_ORDER = 2,     /* ... in the per-sector form (each sector's waves by its own weight) */
@@ -344,7 +372,8 @@ enum {
     QEC_PATH_SPARSE = 64,          /* sparse-graph engine */
     QEC_PATH_RECORDS = 128,        /* packed decision records out */
     QEC_PATH_OSD = 256,            /* the call ran the OSD stage (QEC_OPT_OSD) */
-    QEC_PATH_CORRELATED = 512      /* one sector decoded under priors conditioned on the other's estimate */
+    QEC_PATH_CORRELATED = 512,     /* one sector decoded under priors conditioned on the other's estimate */
+    QEC_PATH_SERIAL = 1024         /* BP under the serial schedule (QEC_OPT_BP_SCHEDULE = 1) */
 };
 /* The near-hard jump's threshold for p' = pPrime (the float (2/3) errorProbability the decoder forms), R
  * checks per variable and L variables per check: *eps0 = the largest power of two in [2^-20, 2^-8] with

@@ -29,16 +29,19 @@ ENGINE = {"auto": 0, "circulant": 1, "sparse": 2, "cpu": 3}
 OPTION = {"hard_paths": 1, "cycle_jump": 2, "schedule": 3, "sector_split": 4, "phase_stats": 5, "triage": 6,
           "last_path": 7, "mc_decode_time": 8, "osd": 9, "osd_iterations": 10, "osd_sectors": 11,
           "osd_sweep": 12, "osd_order": 13, "osd_cs_sectors": 14, "near_hard": 15, "osd_score": 16,
-          "correlated": 17}
+          "correlated": 17, "bp_schedule": 18}
 OPTIONS = OPTION
+# values of the "bp_schedule" option (QEC_OPT_BP_SCHEDULE)
+BP_SCHEDULE = {"flooding": 0, "serial": 1}
 # QEC_PATH_* bits of QEC_OPT_LAST_PATH (include/qec_ldpc.h): the launch sequence of the last decode call
 PATH = {"ordered": 1, "sector_order": 2, "split_waves": 4, "sector_launches": 8, "triage": 16, "bit_rows": 32,
-        "sparse": 64, "records": 128, "osd": 256, "correlated": 512}
+        "sparse": 64, "records": 128, "osd": 256, "correlated": 512, "serial": 1024}
 
 # every symbol include/qec_ldpc.h declares
 EXPORTS = (
     "qec_last_error", "qec_abi_version", "qec_build_id",
-    "qec_code_load", "qec_code_generate", "qec_code_from_matrices", "qec_code_degrees", "qec_code_free",
+    "qec_code_load", "qec_code_generate", "qec_code_from_matrices", "qec_code_degrees", "qec_code_layers",
+    "qec_code_free",
     "qec_code_params", "qec_code_exponents",
     "qec_code_pcm", "qec_code_describe", "qec_code_syndrome", "qec_code_check_logical",
     "qec_code_with_logical", "qec_code_logical_mode", "qec_code_logical_rows", "qec_code_imp",
@@ -123,6 +126,7 @@ def lib():
             "qec_code_generate": (vp, [i, i, i, i, i, i]),
             "qec_code_from_matrices": (vp, [i, i, vp, i, vp]),
             "qec_code_degrees": (i, [vp, vp]),
+            "qec_code_layers": (i, [vp, i, vp]),
             "qec_code_free": (i, [vp]),
             "qec_code_params": (i, [vp, vp]),
             "qec_code_exponents": (i, [vp, i, vp]),
@@ -283,6 +287,15 @@ class Quantum_LDPC_Code:
         v = np.zeros(5, dtype=np.int32)
         _check(lib().qec_code_degrees(self._h, _ptr(v)), "qec_code_degrees")
         return tuple(int(x) for x in v)
+
+    def layers(self, sector):
+        """The colour of every check of the sector under the serial BP schedule (qec_code_layers): int32
+        [numEqs]; checks of one colour share no variable, and the processing order is (colour, index)."""
+        sector = int(sector)
+        colour = np.zeros(self.numEqsZ if sector else self.numEqsX, dtype=np.int32)
+        if lib().qec_code_layers(self._h, sector, _ptr(colour)) < 0:
+            raise QecError("qec_code_layers failed: %s" % last_error())
+        return colour
 
     def __del__(self):
         h = getattr(self, "_h", None)

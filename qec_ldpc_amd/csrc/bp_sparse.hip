@@ -61,6 +61,12 @@ struct SparseArgs {
     int first;
     float c0, c1;
     const float* cond;
+    // SERIAL kernels (QEC_OPT_BP_SCHEDULE = 1): the processing order -- layOrder [mX + mZ], sector X's checks sorted
+    // by (colour, index), then sector Z's (ids counted from mX) -- and the first position of each layer in it,
+    // layOff = offX [LX + 1] (0 .. mX), then offZ [LZ + 1] (mX .. mX + mZ)
+    const int32_t* layOrder;
+    const int32_t* layOff;
+    int LX, LZ;
 };
 
 constexpr int kSparseThreads = 256;
@@ -142,13 +148,21 @@ extern __shared__ __attribute__((aligned(16))) uint8_t sp_lds[];
 template <int STOP, int MAXDC, int MAXDV, bool GENERAL>
 __device__ __forceinline__ void sp_corr_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws);
 
+// the body of both kernels' SERIAL variant (defined below, behind the CORR body)
+template <int STOP, int MAXDC, int MAXDV, bool GENERAL>
+__device__ __forceinline__ void sp_serial_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws);
+
 // PRIORS: the per-variable prior form of DESIGN.md section 2 -- the initial message of a slot is the prior of
 // its variable (through chkVar) and a variable's two running products start from 1 - pi_v and pi_v, read
 // from global memory once per pass (8n bytes that every workgroup shares, so they stay in cache);
 // errorProbability is unused.  Without it the kernel is the scalar one, instruction for instruction.
-template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false>
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false, bool SERIAL = false>
 __global__ __launch_bounds__(kSparseThreads) void bp_sparse_kernel(const SparseArgs a)
 {
+    if constexpr (SERIAL) {
+        sp_serial_decode<STOP, MAXDC, MAXDV, false>(a, nullptr, LDS ? sp_lds : a.scratch + (long long)blockIdx.x * a.ws_bytes);
+        return;
+    }
     if constexpr (CORR) {
         sp_corr_decode<STOP, MAXDC, MAXDV, false>(a, nullptr, LDS ? sp_lds : a.scratch + (long long)blockIdx.x * a.ws_bytes);
         return;
@@ -520,9 +534,189 @@ __device__ __forceinline__ void sp_corr_decode(const SparseArgs& a, const uint8_
     }
 }
 
-template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false>
+// ---- SERIAL: the serial schedule (QEC_OPT_BP_SCHEDULE = 1) -----
+// The message array holds R, the check->variable message of every edge: 0.5f at the start, an unused slot of a
+// general code +0.0f throughout.  An iteration walks the layers; a layer interval takes the X checks of colour l and,
+// behind them, the Z checks of colour l, in two steps with a barrier behind each (striding over the workgroup when a
+// layer is larger):
+//   * a thread per slot of those checks forms the message of the slot's variable from the R of the variable's other
+//     checks -- a plain ascending loop over its varEdge row with two scalar accumulators, its own edge told by the
+//     edge id -- and parks it in its own slot, which nobody else reads in this interval: the checks of one colour
+//     share no variable, so an edge of these checks is read only for checks of other colours, in other intervals;
+//   * a thread per check turns its row into the check's R in place by sp_check / sp_check_general, as in the
+//     flooding kernels.
+// Each R[e] is thus written by one thread per step and read by threads of other intervals: no atomics.  A sector
+// with fewer layers idles in the remaining intervals, a stopped sector in all of them.  (The one-step form, a thread
+// per check forming its own slots one after the other, keeps 6 of hgp_ham's 128 threads busy and measured 1.4 to 2.9
+// times slower per iteration: profiles/serial_edge_ab.json.)
+// The posterior pass (thread per variable, the same loop over all of the variable's checks) writes the decision bytes
+// and folds the inside test into its ballot; it runs where a stop rule looks (syndrome stop: every iteration,
+// reference stop: iterations with index % 10 == 0) and once on the final state.  The q_final export recomputes the
+// posterior per edge, only when q is requested.  Workspace, grid and workgroup are the scalar plan's.
+template <bool GENERAL>
+__device__ __forceinline__ float sp_serial_fold(const float* __restrict__ msg, const int32_t* __restrict__ ve, int dv,
+                                                int self, float pv)
+{
+    float P0 = 1.0f - pv, P1 = pv;
+    for (int j = 0; j < dv; ++j) {
+        const int ed = ve[j];
+        if (GENERAL && ed < 0) break;  // the real entries come first
+        if (ed == self) continue;
+        const float r = msg[ed];
+        P0 = P0 * (1.0f - r);
+        P1 = P1 * r;
+    }
+    return P1 / (P0 + P1);
+}
+
+template <int STOP, int MAXDC, int MAXDV, bool GENERAL>
+__device__ __forceinline__ void sp_serial_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws)
+{
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
+    const int EX = mX * dc, E = m * dc;
+    float* msg = reinterpret_cast<float*>(ws);            // E floats
+    uint8_t* syn = ws + (size_t)E * sizeof(float);        // m bytes: sX then sZ
+    uint8_t* hd = syn + m;                                // 2n bytes: X then Z hard decisions
+
+    const float pp = 2.0f / 3.0f * a.errorProbability;
+    const int N = a.maxIter < 0 ? 0 : a.maxIter;
+    const bool tab = a.prior != nullptr;  // workgroup-uniform: per-variable priors or the scalar p'
+    const int LX = a.LX, LZ = a.LZ;
+    const int32_t* offX = a.layOff;
+    const int32_t* offZ = a.layOff + LX + 1;
+
+    // one variable's row of the varEdge table; v runs over [X | Z], as the prior array does
+    auto var_row = [&](int v, int& dv) {
+        const bool z = v >= n;
+        dv = z ? a.dvZ : a.dvX;
+        return a.varEdge + (z ? (size_t)n * a.dvX + (size_t)(v - n) * dv : (size_t)v * dv);
+    };
+    // the posterior pass over the sectors doX / doZ: decision bytes, and whether a posterior is inside (0.01, 0.99)
+    auto posterior = [&](bool doX, bool doZ, bool& bx, bool& bz) {
+        for (int v = tid; v < 2 * n; v += nt) {
+            const bool z = v >= n;
+            if (z ? !doZ : !doX) continue;
+            int dv;
+            const int32_t* ve = var_row(v, dv);
+            if (GENERAL && ve[0] < 0) { hd[v] = 0; continue; }  // a variable in no check decides 0, enters no test
+            const float post = sp_serial_fold<GENERAL>(msg, ve, dv, -1, tab ? a.prior[v] : pp);
+            hd[v] = post >= 0.5f;
+            if (sp_inside(post)) { if (z) bz = true; else bx = true; }
+        }
+    };
+    auto syndrome_bad = [&](bool& bx, bool& bz) {
+        for (int c = tid; c < m; c += nt) {
+            const bool z = c >= mX;
+            const uint8_t* h = hd + (z ? n : 0);
+            uint32_t x = 0;
+            for (int k = 0; k < dc; ++k) {
+                const int v = a.chkVar[(size_t)c * dc + k];
+                x ^= (!GENERAL || v >= 0) ? (uint32_t)h[v < 0 ? 0 : v] : 0u;
+            }
+            if (x != (GENERAL ? (syn[c] & 3u) : (uint32_t)syn[c])) { if (z) bz = true; else bx = true; }
+        }
+    };
+
+    for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
+        for (int c = tid; c < m; c += nt) {
+            const uint32_t s = c < mX ? a.sX[b * mX + c] : a.sZ[b * mZ + (c - mX)];
+            if (GENERAL) syn[c] = (uint8_t)((s > 1u ? 2u : s) | ((uint32_t)chkDeg[c] << 2));
+            else syn[c] = (uint8_t)s;
+        }
+        for (int e = tid; e < E; e += nt) msg[e] = (!GENERAL || a.chkVar[e] >= 0) ? 0.5f : 0.0f;
+        __syncthreads();
+
+        bool actX = true, actZ = true;  // workgroup-uniform
+        int itX = 0, itZ = 0;
+        for (int it = 0; it < N && (actX || actZ); ++it) {
+            itX += actX;
+            itZ += actZ;
+            const int layers = max(actX ? LX : 0, actZ ? LZ : 0);
+            for (int l = 0; l < layers; ++l) {
+                const int x0 = actX && l < LX ? offX[l] : 0, nx = actX && l < LX ? offX[l + 1] - x0 : 0;
+                const int z0 = actZ && l < LZ ? offZ[l] : 0, nz = actZ && l < LZ ? offZ[l + 1] - z0 : 0;
+                // the slots of the layer's checks, a thread per slot: the message of the slot's variable
+                for (int i = tid; i < (nx + nz) * dc; i += nt) {
+                    const int j = i / dc, k = i - j * dc;
+                    const int c = a.layOrder[j < nx ? x0 + j : z0 + (j - nx)];
+                    const int e = c * dc + k, v = a.chkVar[e];
+                    if (GENERAL && v < 0) continue;  // an unused slot keeps +0.0f
+                    const bool z = c >= mX;
+                    const int dv = z ? a.dvZ : a.dvX;
+                    const int32_t* ve = a.varEdge + (z ? (size_t)n * a.dvX : 0) + (size_t)v * dv;
+                    msg[e] = sp_serial_fold<GENERAL>(msg, ve, dv, e, tab ? a.prior[(z ? n : 0) + v] : pp);
+                }
+                __syncthreads();
+                // the layer's checks, a thread per check: the row becomes the check's R
+                for (int i = tid; i < nx + nz; i += nt) {
+                    const int c = a.layOrder[i < nx ? x0 + i : z0 + (i - nx)];
+                    const uint32_t sd = syn[c];
+                    if (GENERAL) sp_check_general<MAXDC>(msg + (size_t)c * dc, dc, (int)(sd >> 2), (sd & 3u) ? 0.5f : -0.5f);
+                    else sp_check<MAXDC>(msg + (size_t)c * dc, dc, sd ? 0.5f : -0.5f);
+                }
+                __syncthreads();
+            }
+            if (STOP == QEC_STOP_REF && it % 10 == 0) {
+                bool bx = false, bz = false;
+                posterior(actX, actZ, bx, bz);
+                const bool anyx = __syncthreads_or(bx), anyz = __syncthreads_or(bz);
+                if (actX && !anyx) actX = false;
+                if (actZ && !anyz) actZ = false;
+            } else if (STOP == QEC_STOP_SYNDROME) {
+                bool bx = false, bz = false;
+                posterior(actX, actZ, bx, bz);
+                __syncthreads();
+                bx = bz = false;
+                syndrome_bad(bx, bz);
+                const bool badx = __syncthreads_or(bx), badz = __syncthreads_or(bz);
+                if (actX && !badx) actX = false;
+                if (actZ && !badz) actZ = false;
+            }
+        }
+
+        // ---- the final state: decisions, flags, q_final ----
+        bool bx = false, bz = false;
+        posterior(true, true, bx, bz);
+        const bool convFailX = __syncthreads_or(bx), convFailZ = __syncthreads_or(bz);
+        for (int v = tid; v < 2 * n; v += nt) {
+            if (v >= n) a.eZ[b * n + (v - n)] = hd[v]; else a.eX[b * n + v] = hd[v];
+        }
+        bool sx = false, sz = false;
+        syndrome_bad(sx, sz);
+        const bool synFailX = __syncthreads_or(sx), synFailZ = __syncthreads_or(sz);
+        if (a.q != nullptr)
+            for (int e = tid; e < E; e += nt) {
+                const int v = a.chkVar[e];
+                float post = 0.0f;  // an unused slot of a general code
+                if (!GENERAL || v >= 0) {
+                    const int gv = (e < EX ? 0 : n) + v;
+                    int dv;
+                    const int32_t* ve = var_row(gv, dv);
+                    post = sp_serial_fold<GENERAL>(msg, ve, dv, -1, tab ? a.prior[gv] : pp);
+                }
+                a.q[b * E + e] = post;
+            }
+        if (tid == 0) {
+            uint32_t f = 0;
+            if (synFailX) f |= QEC_SYNDROME_FAIL_X;
+            if (synFailZ) f |= QEC_SYNDROME_FAIL_Z;
+            if (convFailX) f |= QEC_CONVERGENCE_FAIL_X;
+            if (convFailZ) f |= QEC_CONVERGENCE_FAIL_Z;
+            a.flags[b] = (uint8_t)f;
+            if (a.iters != nullptr) { a.iters[2 * b] = itX; a.iters[2 * b + 1] = itZ; }
+        }
+        __syncthreads();  // the workspace is reused by the next syndrome pair
+    }
+}
+
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false, bool SERIAL = false>
 __global__ __launch_bounds__(kSparseThreads) void bp_general_kernel(const GeneralArgs ga)
 {
+    if constexpr (SERIAL) {
+        sp_serial_decode<STOP, MAXDC, MAXDV, true>(ga.s, ga.chkDeg, LDS ? sp_lds : ga.s.scratch + (long long)blockIdx.x * ga.s.ws_bytes);
+        return;
+    }
     if constexpr (CORR) {
         sp_corr_decode<STOP, MAXDC, MAXDV, true>(ga.s, ga.chkDeg, LDS ? sp_lds : ga.s.scratch + (long long)blockIdx.x * ga.s.ws_bytes);
         return;
@@ -673,6 +867,18 @@ static void general_fns(GeneralFn (&f)[3], GeneralFn (&fp)[3], GeneralFn (&fc)[3
     fp[QEC_STOP_SYNDROME] = bp_general_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, true>;
 }
 
+// fs: the SERIAL kernels per stop rule (priors are their runtime branch: one set per shape)
+template <int MAXDC, int MAXDV, bool LDS>
+static void serial_fns(SparseFn (&fs)[3], GeneralFn (&gfs)[3])
+{
+    fs[QEC_STOP_REF] = bp_sparse_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS, false, false, true>;
+    fs[QEC_STOP_FIXED] = bp_sparse_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS, false, false, true>;
+    fs[QEC_STOP_SYNDROME] = bp_sparse_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, false, false, true>;
+    gfs[QEC_STOP_REF] = bp_general_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS, false, false, true>;
+    gfs[QEC_STOP_FIXED] = bp_general_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS, false, false, true>;
+    gfs[QEC_STOP_SYNDROME] = bp_general_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, false, false, true>;
+}
+
 template <int MAXDC, int MAXDV, bool LDS>
 static void sparse_fns(SparseFn (&f)[3], SparseFn (&fp)[3], SparseFn (&fc)[3])
 {
@@ -700,6 +906,12 @@ struct SparsePlan {
     GeneralFn gfn[3] = {nullptr, nullptr, nullptr};
     GeneralFn gpfn[3] = {nullptr, nullptr, nullptr};
     GeneralFn gcfn[3] = {nullptr, nullptr, nullptr};
+    // the SERIAL kernels of the same shape (the route's own set is launched) and their layer tables:
+    // layers = layOrder [mX + mZ], offX [LX + 1], offZ [LZ + 1] (SparseArgs)
+    SparseFn sfn[3] = {nullptr, nullptr, nullptr};
+    GeneralFn gsfn[3] = {nullptr, nullptr, nullptr};
+    DeviceArray<int32_t> layers;
+    int LX = 0, LZ = 0;
     DeviceArray<uint8_t> chkDeg;
     int threads = kSparseThreads;
     DeviceArray<int32_t> chkVar, varEdge;
@@ -798,6 +1010,19 @@ void* sparse_plan_create(const Code& c, int device)
     else if (wdc <= 8 && wdv <= 4) { if (p->lds) sparse_fns<8, 4, true>(p->fn, p->pfn, p->cfn); else sparse_fns<8, 4, false>(p->fn, p->pfn, p->cfn); }
     else if (wdc <= 16 && wdv <= 8) { if (p->lds) sparse_fns<16, 8, true>(p->fn, p->pfn, p->cfn); else sparse_fns<16, 8, false>(p->fn, p->pfn, p->cfn); }
     else { if (p->lds) sparse_fns<32, 16, true>(p->fn, p->pfn, p->cfn); else sparse_fns<32, 16, false>(p->fn, p->pfn, p->cfn); }
+    if (wdc <= 8 && wdv <= 4) { if (p->lds) serial_fns<8, 4, true>(p->sfn, p->gsfn); else serial_fns<8, 4, false>(p->sfn, p->gsfn); }
+    else if (wdc <= 16 && wdv <= 8) { if (p->lds) serial_fns<16, 8, true>(p->sfn, p->gsfn); else serial_fns<16, 8, false>(p->sfn, p->gsfn); }
+    else { if (p->lds) serial_fns<32, 16, true>(p->sfn, p->gsfn); else serial_fns<32, 16, false>(p->sfn, p->gsfn); }
+    // the serial schedule's processing order and layer offsets, as positions in one array over both sectors
+    std::vector<int32_t> lay, ordX, offX, ordZ, offZ;
+    code_layer_order(c, 0, ordX, offX);
+    code_layer_order(c, 1, ordZ, offZ);
+    p->LX = (int)offX.size() - 1;
+    p->LZ = (int)offZ.size() - 1;
+    lay.insert(lay.end(), ordX.begin(), ordX.end());
+    for (int32_t r : ordZ) lay.push_back(mX + r);
+    lay.insert(lay.end(), offX.begin(), offX.end());
+    for (int32_t o : offZ) lay.push_back(mX + o);
     try {
         if (hipSetDevice(device) != hipSuccess) throw std::runtime_error("hipSetDevice");
         int cus = 0;
@@ -815,6 +1040,12 @@ void* sparse_plan_create(const Code& c, int device)
             for (int k = 0; k < 6; ++k) {
                 const void* f = k < 3 ? (general ? reinterpret_cast<const void*>(p->gpfn[k]) : reinterpret_cast<const void*>(p->pfn[k]))
                                       : (general ? reinterpret_cast<const void*>(p->gcfn[k - 3]) : reinterpret_cast<const void*>(p->cfn[k - 3]));
+                if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->ws_bytes) != hipSuccess)
+                    throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+            }
+            // and the SERIAL kernels
+            for (int k = 0; k < 3; ++k) {
+                const void* f = general ? reinterpret_cast<const void*>(p->gsfn[k]) : reinterpret_cast<const void*>(p->sfn[k]);
                 if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->ws_bytes) != hipSuccess)
                     throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
             }
@@ -843,6 +1074,8 @@ void* sparse_plan_create(const Code& c, int device)
             p->chkDeg.reserve(cdeg.size());
             hip_throw(hipMemcpy(p->chkDeg.data(), cdeg.data(), cdeg.size(), hipMemcpyHostToDevice), "chkDeg upload");
         }
+        p->layers.reserve(lay.size());
+        hip_throw(hipMemcpy(p->layers.data(), lay.data(), lay.size() * 4, hipMemcpyHostToDevice), "layer table upload");
         if (!p->lds) p->scratch.reserve((size_t)p->grid * p->ws_bytes);
     } catch (const std::exception& ex) {
         delete p;
@@ -866,9 +1099,11 @@ const int32_t* sparse_plan_varedge(const void* plan) { return static_cast<const 
 // prior: nullptr (the scalar kernels, errorProbability), or the device array of 2n priors (the PRIORS kernels)
 // corr: QEC_OPT_CORRELATED -- 0, or 1 / 2 for the CORR kernels with first sector X / Z; then cond is the device
 // array of the 4n conditional priors when prior is set, and c0 / c1 the scalar pair when it is not
+// serial: QEC_OPT_BP_SCHEDULE -- 1 for the SERIAL kernels (scalar p' or prior; never with corr)
 int launch_decode_sparse(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float errorProbability,
                          int maxIter, int stop, uint8_t* eX, uint8_t* eZ, uint8_t* flags, int32_t* iters, float* q,
-                         hipStream_t stream, const float* prior, int corr, const float* cond, float c0, float c1)
+                         hipStream_t stream, const float* prior, int corr, const float* cond, float c0, float c1,
+                         int serial)
 {
     auto* p = static_cast<SparsePlan*>(plan);
     if (B <= 0) return QEC_OK;
@@ -887,12 +1122,16 @@ int launch_decode_sparse(void* plan, const uint8_t* sX, const uint8_t* sZ, long 
     a.c0 = c0; a.c1 = c1;
     a.cond = cond;
     if (corr && prior != nullptr && cond == nullptr) return fail(QEC_ERR_ARG, "bp_sparse launch: the correlated form needs its conditional tables");
+    if (serial && corr) return fail(QEC_ERR_UNSUPPORTED, "bp_sparse launch: the serial schedule has no correlated form");
+    a.layOrder = p->layers.data();
+    a.layOff = p->layers.data() + p->mX + p->mZ;
+    a.LX = p->LX; a.LZ = p->LZ;
     const unsigned grid = (unsigned)std::min<long long>(B, p->grid);
     if (p->general) {
         GeneralArgs ga{a, p->chkDeg.data()};
-        hipLaunchKernelGGL(corr ? p->gcfn[stop] : prior ? p->gpfn[stop] : p->gfn[stop], dim3(grid), dim3(p->threads), p->lds ? (size_t)p->ws_bytes : 0, stream, ga);
+        hipLaunchKernelGGL(serial ? p->gsfn[stop] : corr ? p->gcfn[stop] : prior ? p->gpfn[stop] : p->gfn[stop], dim3(grid), dim3(p->threads), p->lds ? (size_t)p->ws_bytes : 0, stream, ga);
     } else {
-        hipLaunchKernelGGL(corr ? p->cfn[stop] : prior ? p->pfn[stop] : p->fn[stop], dim3(grid), dim3(kSparseThreads), p->lds ? (size_t)p->ws_bytes : 0, stream, a);
+        hipLaunchKernelGGL(serial ? p->sfn[stop] : corr ? p->cfn[stop] : prior ? p->pfn[stop] : p->fn[stop], dim3(grid), dim3(kSparseThreads), p->lds ? (size_t)p->ws_bytes : 0, stream, a);
     }
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(QEC_ERR_HIP, std::string("bp_sparse launch: ") + hipGetErrorString(err));

@@ -78,7 +78,8 @@ const int32_t* sparse_plan_chkvar(const void* plan);
 const int32_t* sparse_plan_varedge(const void* plan);
 int launch_decode_sparse(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float errorProbability,
                          int maxIter, int stop, uint8_t* eX, uint8_t* eZ, uint8_t* flags, int32_t* iters, float* q,
-                         hipStream_t stream, const float* prior, int corr, const float* cond, float c0, float c1);
+                         hipStream_t stream, const float* prior, int corr, const float* cond, float c0, float c1,
+                         int serial);
 int launch_sample_pauli(uint64_t seed, uint64_t start, long long B, int n, const uint64_t* thr, uint8_t* x, uint8_t* z,
                         hipStream_t st);
 int launch_sample_independent(uint64_t seed, uint64_t start, long long B, int n, const float* prior, uint8_t* x,
@@ -88,7 +89,7 @@ void cpu_plan_free(void* plan);
 int cpu_threads();
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
-                     bool near_hard, const float* prior, int corr, const float* cond);
+                     bool near_hard, const float* prior, int corr, const float* cond, int serial);
 void correlated_priors(float p, float* c0, float* c1);
 int launch_pack_decisions(const uint8_t* eX, const uint8_t* eZ, const uint8_t* flags, long long B, int n, uint8_t* out,
                           hipStream_t st);
@@ -170,6 +171,7 @@ struct qec_decoder {
     // conditional priors c0_X [n], c1_X [n], c0_Z [n], c1_Z [n], kept beside the priors by every set (plain
     // priors: c0 = c1 = the marginal; a Pauli channel: its four tables); device copy as dpri
     int correlated = 0;
+    int bp_schedule = 0;            // QEC_OPT_BP_SCHEDULE: 0 flooding, 1 the serial schedule
     std::vector<float> cond;
     DeviceArray<float> dcond;
     const float* cond_host() const { return has_priors ? cond.data() : nullptr; }
@@ -367,6 +369,12 @@ int qec_code_degrees(const qec_code* h, int* out)
     if (!h || !out) return fail(QEC_ERR_ARG, "qec_code_degrees: null argument");
     code_degrees(h->c, out);
     return QEC_OK;
+}
+
+int qec_code_layers(const qec_code* h, int sector, int32_t* colour)
+{
+    if (!h || (sector != 0 && sector != 1)) return fail(QEC_ERR_ARG, "qec_code_layers: bad argument");
+    return code_layers(h->c, sector, colour);
 }
 
 int qec_code_free(qec_code* code)
@@ -712,7 +720,25 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
             return fail(QEC_ERR_UNSUPPORTED,
                         "qec_decoder_set_option: QEC_OPT_CORRELATED needs per-sample priors, which the wave-circulant engine "
                         "cannot hold; create the decoder with QEC_ENGINE_SPARSE (engine \"sparse\")");
+        if (value && d->bp_schedule)
+            return fail(QEC_ERR_UNSUPPORTED,
+                        "qec_decoder_set_option: QEC_OPT_CORRELATED has no form under the serial schedule; set "
+                        "QEC_OPT_BP_SCHEDULE to 0 (flooding) first");
         d->correlated = value;
+        return QEC_OK;
+    case QEC_OPT_BP_SCHEDULE:
+        if (value != 0 && value != 1)
+            return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_BP_SCHEDULE is 0 (flooding) or 1 (serial)");
+        if (value && d->parts.empty() && !d->cpu && d->engine != QEC_ENGINE_SPARSE)
+            return fail(QEC_ERR_UNSUPPORTED,
+                        "qec_decoder_set_option: QEC_OPT_BP_SCHEDULE = 1 (serial) is not built for the wave-circulant engine, "
+                        "whose hard-message shortcuts are proven for flooding; create the decoder with QEC_ENGINE_SPARSE "
+                        "(engine \"sparse\")");
+        if (value && d->correlated)
+            return fail(QEC_ERR_UNSUPPORTED,
+                        "qec_decoder_set_option: the serial schedule has no correlated form; set QEC_OPT_CORRELATED to 0 "
+                        "first");
+        d->bp_schedule = value;
         return QEC_OK;
     case QEC_OPT_OSD_CS_SECTORS:
         return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD_CS_SECTORS is read only");
@@ -929,6 +955,7 @@ int qec_decoder_get_option(const qec_decoder* d, int option, int* value)
     case QEC_OPT_OSD_ORDER: *value = d->osd_order; return QEC_OK;
     case QEC_OPT_OSD_SCORE: *value = d->osd_score; return QEC_OK;
     case QEC_OPT_CORRELATED: *value = d->correlated; return QEC_OK;
+    case QEC_OPT_BP_SCHEDULE: *value = d->bp_schedule; return QEC_OK;
     case QEC_OPT_OSD_CS_SECTORS: {
         unsigned long long t = d->osd_cs_sectors;
         for (const qec_decoder* p : d->parts) t += p->osd_cs_sectors;
@@ -1008,8 +1035,11 @@ int dispatch_decode(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, long l
             correlated_priors(p, &c0, &c1);
             d->last_path |= QEC_PATH_CORRELATED;
         }
+        // QEC_OPT_BP_SCHEDULE, read at the call too: the SERIAL kernels (never together with corr: set_option refuses)
+        const int serial = d->bp_schedule;
+        if (serial) d->last_path |= QEC_PATH_SERIAL;
         rc = launch_decode_sparse(d->sparse, sX, sZ, B, p, maxIter, stop, eX, eZ, flags, iters, q, st, d->prior_dev(), corr,
-                                  d->cond_dev(), c0, c1);
+                                  d->cond_dev(), c0, c1, serial);
         if (!rc && rec != nullptr) rc = launch_pack_decisions(eX, eZ, flags, B, c.n, rec, st);
         if (rc) return rc;
         return ws_release(d, st);
@@ -1184,7 +1214,7 @@ int osd_repair_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t
             cFs.resize(cnt);
             const int rc = cpu_decode_batch(d->cpu, cX.data(), cZ.data(), (long long)cnt, p, d->osd_iters, QEC_STOP_FIXED,
                                             cEX.data(), cEZ.data(), cFs.data(), nullptr, nullptr, cq.data(), 0,
-                                            false, d->prior_host(), d->correlated, d->cond_host());
+                                            false, d->prior_host(), d->correlated, d->cond_host(), d->bp_schedule);
             if (rc) return rc;
             long long swept = 0;
             osd_host_batch(*d->oplan, cX.data(), cZ.data(), (long long)cnt, cq.data(), cEX.data(), cEZ.data(), cF.data(), 0,
@@ -1302,8 +1332,9 @@ int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
     if (B == 0) return QEC_OK;
     if (d->cpu) {
         const int rc = cpu_decode_batch(d->cpu, sX, sZ, (long long)B, p, maxIter, stop, eX, eZ, flags, rec, iters, q, 0,
-                                        d->hard_paths && d->near_hard, d->prior_host(), d->correlated, d->cond_host());
-        d->last_path = d->correlated ? QEC_PATH_CORRELATED : 0;
+                                        d->hard_paths && d->near_hard, d->prior_host(), d->correlated, d->cond_host(),
+                                        d->bp_schedule);
+        d->last_path = (d->correlated ? QEC_PATH_CORRELATED : 0) | (d->bp_schedule ? QEC_PATH_SERIAL : 0);
         return rc || !d->osd ? rc : osd_repair_host(d, sX, sZ, B, p, eX, eZ, flags, rec);
     }
     QEC_DEVICE_SCOPE(d->device);
@@ -1656,7 +1687,7 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
         fl.resize(cnt);
         const int rc = cpu_decode_batch(d->cpu, sx.data(), sz.data(), cnt, p, maxIter, QEC_STOP_REF, ex.data(), ez.data(),
                                         fl.data(), nullptr, nullptr, nullptr, 0, d->hard_paths && d->near_hard,
-                                        d->prior_host(), d->correlated, d->cond_host());
+                                        d->prior_host(), d->correlated, d->cond_host(), d->bp_schedule);
         if (rc) return rc;
         if (d->osd) {  // the counters describe the repaired estimates
             d->osd_sectors = 0;
@@ -1690,7 +1721,8 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
     }
     d->osd_sectors = repaired;
     d->osd_cs_sectors = swept;
-    d->last_path = (d->osd ? QEC_PATH_OSD : 0) | (d->correlated ? QEC_PATH_CORRELATED : 0);
+    d->last_path = (d->osd ? QEC_PATH_OSD : 0) | (d->correlated ? QEC_PATH_CORRELATED : 0) |
+                   (d->bp_schedule ? QEC_PATH_SERIAL : 0);
     std::memset(out, 0, sizeof *out);
     out->randSeed = seed;
     out->numErrorsTested = (uint32_t)tested;

@@ -290,6 +290,44 @@ void code_degrees(const Code& c, int out[5])
     out[4] = std::max(out[0], out[1]);
 }
 
+// The layers of the serial schedule: the checks in ascending index, each with the smallest
+// colour none of whose checks shares a variable with it.  used[l][v]: a check of colour l contains v.
+int code_layers(const Code& c, int sector, int32_t* colour)
+{
+    const std::vector<uint8_t>& H = sector ? c.pcmZ : c.pcmX;
+    const int m = sector ? c.mZ : c.mX, n = c.n;
+    std::vector<std::vector<uint8_t>> used;
+    std::vector<int> vars;
+    for (int r = 0; r < m; ++r) {
+        vars.clear();
+        for (int v = 0; v < n; ++v)
+            if (H[(size_t)r * n + v]) vars.push_back(v);
+        size_t l = 0;
+        for (; l < used.size(); ++l) {
+            bool shared = false;
+            for (int v : vars) shared |= used[l][v] != 0;
+            if (!shared) break;
+        }
+        if (l == used.size()) used.emplace_back(n, 0);
+        for (int v : vars) used[l][v] = 1;
+        if (colour) colour[r] = (int32_t)l;
+    }
+    return (int)used.size();
+}
+
+void code_layer_order(const Code& c, int sector, std::vector<int32_t>& order, std::vector<int32_t>& offset)
+{
+    const int m = sector ? c.mZ : c.mX;
+    std::vector<int32_t> colour(m);
+    const int layers = code_layers(c, sector, colour.data());
+    offset.assign(layers + 1, 0);
+    for (int r = 0; r < m; ++r) ++offset[colour[r] + 1];
+    for (int l = 0; l < layers; ++l) offset[l + 1] += offset[l];
+    order.resize(m);
+    std::vector<int32_t> next(offset.begin(), offset.end() - 1);
+    for (int r = 0; r < m; ++r) order[next[colour[r]]++] = r;  // ascending index inside a colour
+}
+
 int general_code(int n, int mX, const uint8_t* HX, int mZ, const uint8_t* HZ, const uint8_t* imp, Code& c)
 {
     if (n <= 0 || mX <= 0 || mZ <= 0)

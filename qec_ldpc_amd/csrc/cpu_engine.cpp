@@ -32,6 +32,7 @@ struct CpuSector {
     // a general code: dc = the slot stride D and dv = the sector's largest column
     // weight, both tables padded with -1, and each node's own degree
     std::vector<uint8_t> chk_deg, var_deg;
+    std::vector<int32_t> order;     // the serial schedule's processing order: the checks by (colour, index)
 };
 
 struct CpuPlan {
@@ -90,7 +91,7 @@ void build_sector_general(const std::vector<uint8_t>& pcm, int m, int n, int D, 
 inline bool outside(float x) { return !(x > 0.01f && x < 0.99f); }  // CheckConvergence, DecoderCPU.h:231-246
 
 struct Work {
-    std::vector<float> q, r;
+    std::vector<float> q, r, post;
     std::vector<uint8_t> e;
 };
 
@@ -298,6 +299,98 @@ int decode_sector_general(const CpuSector& S, int n, const uint8_t* syn, float e
     return it;
 }
 
+// One sector under the serial schedule (QEC_OPT_BP_SCHEDULE = 1; DESIGN.md section 2, "The serial schedule"),
+// regular and general codes.  r[e] is the check->variable message R of edge e, 0.5f at the start (an unused slot
+// +0.0f throughout).  An iteration takes the checks in S.order; check c first forms the variable->check message of
+// each of its slots from the other checks' R as they stand, then its own R by EqNodeUpdate.  The posterior of a
+// variable is the same product over all its checks; decisions, both stop tests, the flags and q_out are stated
+// over the posteriors, and a variable in no check decides 0 and enters no test.
+int decode_sector_serial(const CpuSector& S, int n, bool general, const uint8_t* syn, float errorProbability,
+                         const float* pri, int N, int stop, Work& w, bool& conv_out, bool& syn_ok, float* q_out)
+{
+    const int m = S.m, D = S.dc, dvs = S.dv;
+    float* q = w.q.data();     // the current check's inputs
+    float* r = w.r.data();
+    uint8_t* e = w.e.data();
+    const float pp = (2.0f / 3.0f) * errorProbability;
+    const float one_minus_pp = 1.0f - pp;
+    auto cdeg = [&](int c) { return general ? (int)S.chk_deg[c] : D; };
+    auto vdeg = [&](int v) { return general ? (int)S.var_deg[v] : dvs; };
+    for (int c = 0; c < m; ++c)
+        for (int k = 0; k < D; ++k) r[(size_t)c * D + k] = k < cdeg(c) ? 0.5f : 0.0f;
+    std::vector<float>& post = w.post;
+    post.resize(n);
+    bool inside = false;
+    auto posterior = [&]() {
+        inside = false;
+        for (int v = 0; v < n; ++v) {
+            const int dv = vdeg(v);
+            if (dv == 0) { e[v] = 0; post[v] = 0.0f; continue; }
+            const int32_t* ve = S.var_edge.data() + (size_t)v * dvs;
+            float P0 = pri ? 1.0f - pri[v] : one_minus_pp, P1 = pri ? pri[v] : pp;
+            for (int j = 0; j < dv; ++j) {
+                const float rk = r[ve[j]];
+                P0 = P0 * (1.0f - rk);
+                P1 = P1 * rk;
+            }
+            post[v] = P1 / (P0 + P1);
+            e[v] = post[v] >= 0.5f;
+            inside |= !outside(post[v]);
+        }
+    };
+    auto syndrome_ok = [&]() {
+        for (int c = 0; c < m; ++c) {
+            uint32_t x = 0;
+            for (int k = 0; k < cdeg(c); ++k) x ^= e[S.chk_var[(size_t)c * D + k]];
+            if ((x & 1u) != syn[c]) return false;
+        }
+        return true;
+    };
+    int it = 0;
+    for (int iter = 0; iter < N; ++iter) {
+        ++it;
+        for (int o = 0; o < m; ++o) {
+            const int c = S.order[o], dc = cdeg(c);
+            float* rc = r + (size_t)c * D;
+            for (int k = 0; k < dc; ++k) {
+                const int v = S.chk_var[(size_t)c * D + k], self = c * D + k;
+                const int32_t* ve = S.var_edge.data() + (size_t)v * dvs;
+                float P0 = pri ? 1.0f - pri[v] : one_minus_pp, P1 = pri ? pri[v] : pp;
+                for (int j = 0; j < vdeg(v); ++j) {
+                    if (ve[j] == self) continue;
+                    const float rk = r[ve[j]];
+                    P0 = P0 * (1.0f - rk);
+                    P1 = P1 * rk;
+                }
+                q[k] = P1 / (P0 + P1);
+            }
+            const bool s = syn[c] != 0;
+            for (int i = 0; i < dc; ++i) {
+                float t = 1.0f;
+                for (int k = 0; k < dc; ++k)
+                    if (k != i) t = t * (1.0f - 2.0f * q[k]);
+                rc[i] = s ? 0.5f * (1.0f + t) : 0.5f * (1.0f - t);
+            }
+        }
+        if (stop == QEC_STOP_REF && iter % 10 == 0) {
+            posterior();
+            if (!inside) break;
+        }
+        if (stop == QEC_STOP_SYNDROME) {
+            posterior();
+            if (syndrome_ok()) break;
+        }
+    }
+    posterior();
+    conv_out = !inside;
+    syn_ok = syndrome_ok();
+    if (q_out)
+        for (int c = 0; c < m; ++c)
+            for (int k = 0; k < D; ++k)
+                q_out[(size_t)c * D + k] = k < cdeg(c) ? post[S.chk_var[(size_t)c * D + k]] : 0.0f;
+    return it;
+}
+
 }  // namespace
 
 void* cpu_plan_create(const Code& c)
@@ -313,6 +406,8 @@ void* cpu_plan_create(const Code& c)
         p->general = true;
         build_sector_general(c.pcmX, c.mX, c.n, c.D, c.dvX, p->sec[0]);
         build_sector_general(c.pcmZ, c.mZ, c.n, c.D, c.dvZ, p->sec[1]);
+        std::vector<int32_t> off;
+        for (int sec = 0; sec < 2; ++sec) code_layer_order(c, sec, p->sec[sec].order, off);
         return p;
     }
     std::string why;
@@ -321,6 +416,8 @@ void* cpu_plan_create(const Code& c)
         fail(QEC_ERR_UNSUPPORTED, "CPU engine: " + why + " (DecoderCPU assumes regular degrees)");
         return nullptr;
     }
+    std::vector<int32_t> off;
+    for (int sec = 0; sec < 2; ++sec) code_layer_order(c, sec, p->sec[sec].order, off);
     return p;
 }
 
@@ -349,9 +446,10 @@ void correlated_priors(float p, float* c0, float* c1)
 // under 0, the second by the prior form with pi_v = d[v] ? c1[v] : c0[v], d the first sector's estimate; cond
 // (with prior) = the tables c0_X [n], c1_X [n], c0_Z [n], c1_Z [n], without prior the pair correlated_priors(p).
 // The near-hard jump never fires for the second sector.
+// serial (QEC_OPT_BP_SCHEDULE): 1 = the serial schedule (decode_sector_serial; no near-hard jump, never with corr).
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
-                     bool near_hard, const float* prior, int corr, const float* cond)
+                     bool near_hard, const float* prior, int corr, const float* cond, int serial)
 {
     const CpuPlan& P = *static_cast<const CpuPlan*>(plan);
     const int n = P.n, nb = (n + 7) / 8;
@@ -362,6 +460,7 @@ int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long
     if (near_hard && !prior && !P.general && qf == nullptr && stop != QEC_STOP_SYNDROME)
         for (int sec = 0; sec < 2; ++sec) nearT[sec] = near_hard_threshold((2.0f / 3.0f) * p, P.sec[sec].dv, P.sec[sec].dc).T;
     if (corr && prior && !cond) return fail(QEC_ERR_ARG, "CPU engine: the correlated form needs its conditional tables");
+    if (serial && corr) return fail(QEC_ERR_UNSUPPORTED, "CPU engine: the serial schedule has no correlated form");
     float sc0 = 0.0f, sc1 = 0.0f;
     if (corr) correlated_priors(p, &sc0, &sc1);
     if (threads <= 0) threads = cpu_threads();
@@ -389,9 +488,10 @@ int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long
                     for (int v = 0; v < n; ++v) pi[v] = first[v] ? (cond ? t0[n + v] : sc1) : (cond ? t0[v] : sc0);
                     pri = pi.data();
                 }
-                const int it = P.general ? decode_sector_general(S, n, syn, p, pri, maxIter, stop, w, conv, ok, qo)
-                                         : decode_sector(S, n, syn, p, pri, maxIter, stop, w, conv, ok, qo,
-                                                         second ? 0u : nearT[sec]);
+                const int it = serial ? decode_sector_serial(S, n, P.general, syn, p, pri, maxIter, stop, w, conv, ok, qo)
+                               : P.general ? decode_sector_general(S, n, syn, p, pri, maxIter, stop, w, conv, ok, qo)
+                                           : decode_sector(S, n, syn, p, pri, maxIter, stop, w, conv, ok, qo,
+                                                           second ? 0u : nearT[sec]);
                 if (corr && pass == 0) std::memcpy(first.data(), w.e.data(), n);
                 if (!ok) f |= sec ? QEC_SYNDROME_FAIL_Z : QEC_SYNDROME_FAIL_X;
                 if (!conv) f |= sec ? QEC_CONVERGENCE_FAIL_Z : QEC_CONVERGENCE_FAIL_X;

@@ -55,6 +55,11 @@ int generate_code(int J, int K, int L, int P, int sigma, int tau, Code& out);
 int general_code(int n, int mX, const uint8_t* HX, int mZ, const uint8_t* HZ, const uint8_t* imp, Code& out);
 // max row weight X, Z, max column weight X, Z, slot stride (qec_code_degrees); any code
 void code_degrees(const Code& c, int out[5]);
+// The serial schedule's layers of one sector (qec_code_layers): colour[m] (nullable); returns their number
+int code_layers(const Code& c, int sector, int32_t* colour);
+// The sector's processing order under the serial schedule: its checks sorted by (colour, index), and the first
+// position of each layer in that order (layers + 1 entries, the last = m)
+void code_layer_order(const Code& c, int sector, std::vector<int32_t>& order, std::vector<int32_t>& offset);
 // Generator exponent tables (QEC_LDPC/QEC_LDPC_CSS.cu:37-90); returns false if sigma has no inverse.
 bool generator_exponents(int J, int K, int L, int P, int sigma, int tau, std::vector<int>& EX, std::vector<int>& EZ);
 void finalize_code(Code& c);  // derive circulant tables + packed I-P from the dense matrices

@@ -37,6 +37,8 @@
 //                      fails with the library's message (use --engine sparse)
 //   --correlated xz|zx the correlated form (QEC_OPT_CORRELATED): sector X first and sector Z under priors conditioned
 //                      on the X estimate (xz), or Z first (zx).  Sparse-graph and CPU engines
+//   --bp-schedule flooding|serial   the order of BP's updates (QEC_OPT_BP_SCHEDULE): flooding (default), or the serial
+//                      (layered, check-sequential) schedule.  Sparse-graph and CPU engines; not with --correlated
 //   --pauli FILE       per-qubit Pauli channel (qec_decoder_set_pauli_channel): FILE holds three lines of n decimal
 //                      floats, pX, pY and pZ.  BP decodes under its marginals (and --correlated under its conditional
 //                      tables), the init file's p is not used, and --rng philox draws its errors from the channel.
@@ -89,7 +91,7 @@ int usage(const std::string& why)
               << "usage: qec_ldpc [--engine gpu|sparse|cpu] [--gpus N | --devices i,j,...] [--rng msvc|philox]"
                  " [--stop ref|fixed|syndrome] [--batch B] [--seed S] [--logical file|reference|degenerate]"
                  " [--osd 0 [--osd-order L] [--osd-iterations K] [--osd-score hamming|priors]] [--priors FILE]"
-                 " [--correlated xz|zx] [--pauli FILE] initFile"
+                 " [--correlated xz|zx] [--bp-schedule flooding|serial] [--pauli FILE] initFile"
               << std::endl;
     return 2;
 }
@@ -139,7 +141,7 @@ int main(int argc, char** argv)
     log << std::endl << std::ctime(&ts);
     std::vector<int> devices{0};
     std::string engine = "gpu", rng = "msvc", stopName = "ref", logical = "file", priorsFile, pauliFile;
-    int correlated = 0;
+    int correlated = 0, bpSchedule = 0;
     bool deviceFlag = false, stopFlag = false, batchFlag = false, seedFlag = false, osd = false, osdIterFlag = false;
     bool osdOrderFlag = false, osdScoreFlag = false;
     int osdScore = 0;
@@ -203,6 +205,9 @@ int main(int argc, char** argv)
             } else if (flag == "--correlated") {
                 if (val != "xz" && val != "zx") return usage("--correlated: xz or zx");
                 correlated = val == "xz" ? 1 : 2;
+            } else if (flag == "--bp-schedule") {
+                if (val != "flooding" && val != "serial") return usage("--bp-schedule: flooding or serial");
+                bpSchedule = val == "serial" ? 1 : 0;
             } else if (flag == "--seed") {
                 seed = std::stoull(val, nullptr, 0);
                 seedFlag = true;
@@ -220,6 +225,7 @@ int main(int argc, char** argv)
     if (osdIterFlag && !osd) return usage("--osd-iterations needs --osd 0");
     if (osdOrderFlag && !osd) return usage("--osd-order needs --osd 0");
     if (osdScoreFlag && !osd) return usage("--osd-score needs --osd 0");
+    if (bpSchedule && correlated) return usage("--bp-schedule serial and --correlated exclude each other");
     if (!pauliFile.empty() && !priorsFile.empty()) return usage("--pauli and --priors exclude each other");
     if (osdScore == 1 && priorsFile.empty()) return usage("--osd-score priors needs --priors FILE");
     if (argc - a != 1 || devices.empty()) {
@@ -265,6 +271,7 @@ int main(int argc, char** argv)
             if (!priorsFile.empty()) decoder.SetPriors(priorX, priorZ);
             if (!pauliFile.empty()) decoder.SetPauliChannel(pauli[0], pauli[1], pauli[2]);
             if (correlated) decoder.SetCorrelated(correlated);
+            if (bpSchedule) decoder.SetBpSchedule(bpSchedule);
             std::cout << "Engine: " << decoder.Describe() << std::endl;
             const int stop = stopName == "ref" ? QEC_STOP_REF : stopName == "fixed" ? QEC_STOP_FIXED : QEC_STOP_SYNDROME;
             std::stringstream fileName;
@@ -291,6 +298,7 @@ int main(int argc, char** argv)
             if (!priorsFile.empty()) c->SetPriors(priorX, priorZ);
             if (!pauliFile.empty()) c->SetPauliChannel(pauli[0], pauli[1], pauli[2]);
             if (correlated) c->SetCorrelated(correlated);
+            if (bpSchedule) c->SetBpSchedule(bpSchedule);
             std::cout << "Engine: CPU (" << std::thread::hardware_concurrency() << " threads)" << std::endl;
         } else {
             DecoderGPU* g = engine == "sparse" ? new DecoderGPU(code, 0, QEC_ENGINE_SPARSE) : new DecoderGPU(code, devices);
@@ -300,6 +308,7 @@ int main(int argc, char** argv)
             if (!priorsFile.empty()) g->SetPriors(priorX, priorZ);
             if (!pauliFile.empty()) g->SetPauliChannel(pauli[0], pauli[1], pauli[2]);
             if (correlated) g->SetCorrelated(correlated);
+            if (bpSchedule) g->SetBpSchedule(bpSchedule);
             std::cout << "Engine: " << g->Describe() << std::endl;
         }
         for (; w <= W; ++w) {
