@@ -20,6 +20,12 @@
 // Each edge is owned by exactly one thread in each pass, so in-place updates are
 // race-free; passes are separated by workgroup barriers.
 //
+// Two kernel entries, bp_sparse_kernel (regular codes) and bp_general_kernel (codes given by two matrices, any
+// degrees), run the same three decode bodies -- sp_flood_decode (the flooding schedule, scalar p' or PRIORS),
+// sp_corr_decode (CORR) and sp_serial_decode (SERIAL) -- each templated on GENERAL, which selects the table
+// sentinels, the packed syndrome byte and the update functions; everything around the updates (loops, stop tests,
+// post-processing, flags) is one text for both routes.  The plan keeps one table of kernels, by variant and stop rule.
+//
 // Arithmetic is the same as the wave-circulant engine's (and so the reference's):
 // left folds in ascending neighbour order (prefix reuse only), IEEE fp32 with
 // denormals, -ffp-contract=off, correctly rounded division, and the two exact FMAs
@@ -142,141 +148,8 @@ __device__ __forceinline__ bool sp_var(float* __restrict__ msg, const int32_t* _
     return hd;
 }
 
-extern __shared__ __attribute__((aligned(16))) uint8_t sp_lds[];
-
-// the body of both kernels' CORR variant (defined below, behind the general code's updates)
-template <int STOP, int MAXDC, int MAXDV, bool GENERAL>
-__device__ __forceinline__ void sp_corr_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws);
-
-// the body of both kernels' SERIAL variant (defined below, behind the CORR body)
-template <int STOP, int MAXDC, int MAXDV, bool GENERAL>
-__device__ __forceinline__ void sp_serial_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws);
-
-// PRIORS: the per-variable prior form of DESIGN.md section 2 -- the initial message of a slot is the prior of
-// its variable (through chkVar) and a variable's two running products start from 1 - pi_v and pi_v, read
-// from global memory once per pass (8n bytes that every workgroup shares, so they stay in cache);
-// errorProbability is unused.  Without it the kernel is the scalar one, instruction for instruction.
-template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false, bool SERIAL = false>
-__global__ __launch_bounds__(kSparseThreads) void bp_sparse_kernel(const SparseArgs a)
-{
-    if constexpr (SERIAL) {
-        sp_serial_decode<STOP, MAXDC, MAXDV, false>(a, nullptr, LDS ? sp_lds : a.scratch + (long long)blockIdx.x * a.ws_bytes);
-        return;
-    }
-    if constexpr (CORR) {
-        sp_corr_decode<STOP, MAXDC, MAXDV, false>(a, nullptr, LDS ? sp_lds : a.scratch + (long long)blockIdx.x * a.ws_bytes);
-        return;
-    }
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
-    const int EX = mX * dc, E = m * dc;
-    uint8_t* ws = LDS ? sp_lds : a.scratch + (long long)blockIdx.x * a.ws_bytes;
-    float* msg = reinterpret_cast<float*>(ws);            // E floats
-    uint8_t* syn = ws + (size_t)E * sizeof(float);        // m bytes: sX then sZ
-    uint8_t* hd = syn + m;                                // 2n bytes: X then Z hard decisions
-
-    const float pp = 2.0f / 3.0f * a.errorProbability;   // DecoderCPU.h:259
-    const float omp = 1.0f - pp;
-    const int N = a.maxIter < 0 ? 0 : a.maxIter;
-
-    for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
-        // syndromes in, InitVarNodes: every edge starts at p' (DecoderCPU.h:135-148, 265-267)
-        // the entry as given: the check update takes its truthiness, the syndrome tests compare it
-        // exactly (DecoderCPU.h:178, :381), so an entry other than 0/1 never matches a parity
-        for (int c = tid; c < m; c += nt) syn[c] = c < mX ? a.sX[b * mX + c] : a.sZ[b * mZ + (c - mX)];
-        if (PRIORS)
-            for (int e = tid; e < E; e += nt) msg[e] = a.prior[(e < EX ? 0 : n) + a.chkVar[e]];
-        else
-            for (int e = tid; e < E; e += nt) msg[e] = pp;
-        __syncthreads();
-
-        bool actX = true, actZ = true;  // workgroup-uniform
-        int itX = 0, itZ = 0;
-        for (int it = 0; it < N && (actX || actZ); ++it) {  // BeliefPropogation, DecoderCPU.h:280-291
-            const bool last = it == N - 1;
-            itX += actX;
-            itZ += actZ;
-            for (int c = tid; c < m; c += nt) {
-                if (c < mX ? !actX : !actZ) continue;
-                sp_check<MAXDC>(msg + (size_t)c * dc, dc, syn[c] ? 0.5f : -0.5f);
-            }
-            __syncthreads();
-            for (int v = tid; v < 2 * n; v += nt) {
-                const bool z = v >= n;
-                if (z ? !actZ : !actX) continue;
-                const int dv = z ? a.dvZ : a.dvX;
-                const int32_t* ve = a.varEdge + (z ? (size_t)n * a.dvX + (size_t)(v - n) * dv : (size_t)v * dv);
-                const float pv = PRIORS ? a.prior[v] : pp;  // v runs over [X | Z], as the prior array does
-                const bool h = sp_var<MAXDV>(msg, ve, dv, pv, PRIORS ? 1.0f - pv : omp, last);
-                if (STOP == QEC_STOP_SYNDROME) hd[v] = h;
-            }
-            __syncthreads();
-            if (STOP == QEC_STOP_REF && it % 10 == 0) {  // CheckConvergence, DecoderCPU.h:287-290
-                bool bx = false, bz = false;
-                for (int e = tid; e < E; e += nt) {
-                    const bool in = sp_inside(msg[e]);
-                    if (e < EX) bx |= in; else bz |= in;
-                }
-                const bool anyx = __syncthreads_or(bx), anyz = __syncthreads_or(bz);
-                if (actX && !anyx) actX = false;
-                if (actZ && !anyz) actZ = false;
-            } else if (STOP == QEC_STOP_SYNDROME) {  // hard decision satisfies the syndrome
-                bool bx = false, bz = false;
-                for (int c = tid; c < m; c += nt) {
-                    const bool z = c >= mX;
-                    const uint8_t* h = hd + (z ? n : 0);
-                    uint32_t x = 0;
-                    for (int k = 0; k < dc; ++k) x ^= h[a.chkVar[(size_t)c * dc + k]];
-                    if (x != syn[c]) { if (z) bz = true; else bx = true; }
-                }
-                const bool badx = __syncthreads_or(bx), badz = __syncthreads_or(bz);
-                if (actX && !badx) actX = false;
-                if (actZ && !badz) actZ = false;
-            }
-        }
-
-        // ---- post-processing of Decode (DecoderCPU.h:354-384) ----
-        bool bx = false, bz = false;
-        for (int e = tid; e < E; e += nt) {
-            const bool in = sp_inside(msg[e]);
-            if (e < EX) bx |= in; else bz |= in;
-        }
-        for (int v = tid; v < 2 * n; v += nt) {
-            const bool z = v >= n;
-            const int dv = z ? a.dvZ : a.dvX;
-            const int32_t* ve = a.varEdge + (z ? (size_t)n * a.dvX + (size_t)(v - n) * dv : (size_t)v * dv);
-            bool h = false;
-            for (int j = 0; j < dv; ++j) h |= msg[ve[j]] >= 0.5f;
-            hd[v] = h;
-            if (z) a.eZ[b * n + (v - n)] = h; else a.eX[b * n + v] = h;
-        }
-        const bool convFailX = __syncthreads_or(bx), convFailZ = __syncthreads_or(bz);
-        bool sx = false, sz = false;
-        for (int c = tid; c < m; c += nt) {
-            const bool z = c >= mX;
-            const uint8_t* h = hd + (z ? n : 0);
-            uint32_t x = 0;
-            for (int k = 0; k < dc; ++k) x ^= h[a.chkVar[(size_t)c * dc + k]];
-            if (x != syn[c]) { if (z) sz = true; else sx = true; }
-        }
-        const bool synFailX = __syncthreads_or(sx), synFailZ = __syncthreads_or(sz);
-        if (a.q != nullptr)
-            for (int e = tid; e < E; e += nt) a.q[b * E + e] = msg[e];
-        if (tid == 0) {
-            uint32_t f = 0;
-            if (synFailX) f |= QEC_SYNDROME_FAIL_X;
-            if (synFailZ) f |= QEC_SYNDROME_FAIL_Z;
-            if (convFailX) f |= QEC_CONVERGENCE_FAIL_X;
-            if (convFailZ) f |= QEC_CONVERGENCE_FAIL_Z;
-            a.flags[b] = (uint8_t)f;
-            if (a.iters != nullptr) { a.iters[2 * b] = itX; a.iters[2 * b + 1] = itZ; }
-        }
-        __syncthreads();  // the workspace is reused by the next syndrome pair
-    }
-}
-
 // ---- general codes (qec_code_from_matrices) -------------
-// The same kernel plan for a graph whose nodes have their own degrees.  Layout: msg[c * D + k] with
+// The same decode bodies (GENERAL) for a graph whose nodes have their own degrees.  Layout: msg[c * D + k] with
 // one slot stride D (the largest row weight of both sectors); check c uses its first deg(c) slots and
 // the others hold +0.0f from the initialisation to the q_final export.  Tables:
 // chkVar [mX + mZ][D] and varEdge [n][dvX] / [n][dvZ] (the sectors' largest column weights), padded
@@ -389,9 +262,217 @@ struct GeneralArgs {
     const uint8_t* chkDeg;   // mX + mZ degree bytes
 };
 
+extern __shared__ __attribute__((aligned(16))) uint8_t sp_lds[];
+
+// ---- pieces of the decode bodies ------------------------------------------------
+// Every body (flooding, CORR, SERIAL) is templated on GENERAL: false for bp_sparse_kernel's regular tables,
+// true for bp_general_kernel's padded ones.  sp_var_edges and sp_store_status serve all three bodies; the
+// others serve the flooding body alone: calling them from the CORR and SERIAL bodies, which spell the same
+// steps out, changed those kernels' code and measured up to 2.6 % slower (profiles/flood_merge_ab.json).
+
+// Syndromes in.  Regular: the entry as given -- the check update takes its truthiness, the syndrome tests compare
+// it exactly (DecoderCPU.h:178, :381), so an entry other than 0/1 never matches a parity.  General: the entry as
+// 0, 1 or 2 = any other value (truthy in the check update, never equal to a parity in the syndrome tests) with the
+// check's degree above it.
+template <bool GENERAL>
+__device__ __forceinline__ void sp_load_syndromes(const SparseArgs& a, const uint8_t* chkDeg, long long b,
+                                                  uint8_t* syn)
+{
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int mX = a.mX, mZ = a.mZ, m = mX + mZ;
+    for (int c = tid; c < m; c += nt) {
+        const uint32_t s = c < mX ? a.sX[b * mX + c] : a.sZ[b * mZ + (c - mX)];
+        if (GENERAL) syn[c] = (uint8_t)((s > 1u ? 2u : s) | ((uint32_t)chkDeg[c] << 2));
+        else syn[c] = (uint8_t)s;
+    }
+}
+
+// One check's update in place, from its row of slots and its syndrome byte
+template <int MAXDC, bool GENERAL>
+__device__ __forceinline__ void sp_check_row(float* row, int dc, uint32_t sd)
+{
+    if (GENERAL) sp_check_general<MAXDC>(row, dc, (int)(sd >> 2), (sd & 3u) ? 0.5f : -0.5f);
+    else sp_check<MAXDC>(row, dc, sd ? 0.5f : -0.5f);
+}
+
+// One variable's update; returns its hard decision
+template <int MAXDV, bool GENERAL>
+__device__ __forceinline__ bool sp_var_row(float* msg, const int32_t* ve, int dv, float pp,
+                                           float omp, bool last)
+{
+    return GENERAL ? sp_var_general<MAXDV>(msg, ve, dv, pp, omp, last) : sp_var<MAXDV>(msg, ve, dv, pp, omp, last);
+}
+
+// One variable's row of the varEdge table and its stride; v runs over [X | Z], as the prior array does
+__device__ __forceinline__ const int32_t* sp_var_edges(const SparseArgs& a, int v, int& dv)
+{
+    const bool z = v >= a.n;
+    dv = z ? a.dvZ : a.dvX;
+    return a.varEdge + (z ? (size_t)a.n * a.dvX + (size_t)(v - a.n) * dv : (size_t)v * dv);
+}
+
+// Whether the parity of one check (its chkVar row) over its sector's decision bytes h misses its syndrome byte.
+// A general code walks the whole stride and selects on the sentinel: no early exit, the dc loads stay independent.
+template <bool GENERAL>
+__device__ __forceinline__ bool sp_parity_fails(const int32_t* row, int dc, const uint8_t* h, uint32_t sd)
+{
+    uint32_t x = 0;
+    for (int k = 0; k < dc; ++k) {
+        const int v = row[k];
+        x ^= (!GENERAL || v >= 0) ? (uint32_t)h[v < 0 ? 0 : v] : 0u;
+    }
+    return x != (GENERAL ? (sd & 3u) : sd);
+}
+
+// The syndrome test over all checks of both sectors: bx / bz are set where a check fails
+template <bool GENERAL>
+__device__ __forceinline__ void sp_syndrome_fails(const SparseArgs& a, const uint8_t* syn, const uint8_t* hd, bool& bx,
+                                                  bool& bz)
+{
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int mX = a.mX, m = mX + a.mZ, dc = a.dc;
+    for (int c = tid; c < m; c += nt) {
+        const bool z = c >= mX;
+        if (sp_parity_fails<GENERAL>(a.chkVar + (size_t)c * dc, dc, hd + (z ? a.n : 0), syn[c])) {
+            if (z) bz = true; else bx = true;
+        }
+    }
+}
+
+// The final hard decision of one variable: any message on its edges >= 0.5f (DecoderCPU.h:354-373)
+template <bool GENERAL>
+__device__ __forceinline__ bool sp_decide(const float* msg, const int32_t* ve, int dv)
+{
+    bool h = false;
+    for (int j = 0; j < dv; ++j) {
+        const int ed = ve[j];
+        h |= (!GENERAL || ed >= 0) && msg[ed < 0 ? 0 : ed] >= 0.5f;
+    }
+    return h;
+}
+
+__device__ __forceinline__ uint32_t sp_fail_flags(bool synFailX, bool synFailZ, bool convFailX, bool convFailZ)
+{
+    uint32_t f = 0;
+    if (synFailX) f |= QEC_SYNDROME_FAIL_X;
+    if (synFailZ) f |= QEC_SYNDROME_FAIL_Z;
+    if (convFailX) f |= QEC_CONVERGENCE_FAIL_X;
+    if (convFailZ) f |= QEC_CONVERGENCE_FAIL_Z;
+    return f;
+}
+
+// The flag word and the iteration counts of syndrome pair b, by thread 0
+__device__ __forceinline__ void sp_store_status(const SparseArgs& a, long long b, uint32_t f, int itX, int itZ)
+{
+    if (threadIdx.x == 0) {
+        a.flags[b] = (uint8_t)f;
+        if (a.iters != nullptr) { a.iters[2 * b] = itX; a.iters[2 * b + 1] = itZ; }
+    }
+}
+
+// ---- the flooding schedule: the scalar and the PRIORS kernels -------------------
+// PRIORS: the per-variable prior form of DESIGN.md section 2 -- the initial message of a slot is the prior of
+// its variable (through chkVar) and a variable's two running products start from 1 - pi_v and pi_v, read
+// from global memory once per pass (8n bytes that every workgroup shares, so they stay in cache);
+// errorProbability is unused.  Without it the body is the scalar one: PRIORS only selects operands.
+
+// CheckConvergence (DecoderCPU.h:287-290) over every slot: whether a message of sector X / Z is inside (0.01, 0.99)
+__device__ __forceinline__ void sp_any_inside(const float* msg, int E, int EX, bool& bx, bool& bz)
+{
+    const int tid = threadIdx.x, nt = blockDim.x;
+    for (int e = tid; e < E; e += nt) {
+        const bool in = sp_inside(msg[e]);
+        if (e < EX) bx |= in; else bz |= in;
+    }
+}
+
+template <int STOP, int MAXDC, int MAXDV, bool GENERAL, bool PRIORS>
+__device__ __forceinline__ void sp_flood_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws)
+{
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
+    const int EX = mX * dc, E = m * dc;
+    float* msg = reinterpret_cast<float*>(ws);            // E floats
+    uint8_t* syn = ws + (size_t)E * sizeof(float);        // m bytes: sX then sZ
+    uint8_t* hd = syn + m;                                // 2n bytes: X then Z hard decisions
+
+    const float pp = 2.0f / 3.0f * a.errorProbability;   // DecoderCPU.h:259
+    const float omp = 1.0f - pp;
+    const int N = a.maxIter < 0 ? 0 : a.maxIter;
+
+    for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
+        sp_load_syndromes<GENERAL>(a, chkDeg, b, syn);
+        // InitVarNodes: every edge starts at p' (DecoderCPU.h:135-148, 265-267) or at its variable's prior, one
+        // edge per thread.  The check table is read only where it is needed: for the prior's index and for a
+        // general code's sentinel, which tells a real slot from an unused one (coalesced words that every
+        // workgroup reads, so they stay in cache).
+        for (int e = tid; e < E; e += nt) {
+            const int v = (GENERAL || PRIORS) ? a.chkVar[e] : 0;
+            float x = 0.0f;  // an unused slot of a general code
+            if (!GENERAL || v >= 0) x = PRIORS ? a.prior[(e < EX ? 0 : n) + v] : pp;
+            msg[e] = x;
+        }
+        __syncthreads();
+
+        bool actX = true, actZ = true;  // workgroup-uniform
+        int itX = 0, itZ = 0;
+        for (int it = 0; it < N && (actX || actZ); ++it) {  // BeliefPropogation, DecoderCPU.h:280-291
+            const bool last = it == N - 1;
+            itX += actX;
+            itZ += actZ;
+            for (int c = tid; c < m; c += nt) {
+                if (c < mX ? !actX : !actZ) continue;
+                sp_check_row<MAXDC, GENERAL>(msg + (size_t)c * dc, dc, syn[c]);
+            }
+            __syncthreads();
+            for (int v = tid; v < 2 * n; v += nt) {
+                if (v >= n ? !actZ : !actX) continue;
+                int dv;
+                const int32_t* ve = sp_var_edges(a, v, dv);
+                const float pv = PRIORS ? a.prior[v] : pp;
+                const bool h = sp_var_row<MAXDV, GENERAL>(msg, ve, dv, pv, PRIORS ? 1.0f - pv : omp, last);
+                if (STOP == QEC_STOP_SYNDROME) hd[v] = h;
+            }
+            __syncthreads();
+            if (STOP == QEC_STOP_REF && it % 10 == 0) {  // CheckConvergence, DecoderCPU.h:287-290
+                bool bx = false, bz = false;
+                sp_any_inside(msg, E, EX, bx, bz);
+                const bool anyx = __syncthreads_or(bx), anyz = __syncthreads_or(bz);
+                if (actX && !anyx) actX = false;
+                if (actZ && !anyz) actZ = false;
+            } else if (STOP == QEC_STOP_SYNDROME) {  // hard decision satisfies the syndrome
+                bool bx = false, bz = false;
+                sp_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
+                const bool badx = __syncthreads_or(bx), badz = __syncthreads_or(bz);
+                if (actX && !badx) actX = false;
+                if (actZ && !badz) actZ = false;
+            }
+        }
+
+        // ---- post-processing of Decode (DecoderCPU.h:354-384) ----
+        bool bx = false, bz = false;
+        sp_any_inside(msg, E, EX, bx, bz);
+        for (int v = tid; v < 2 * n; v += nt) {
+            int dv;
+            const int32_t* ve = sp_var_edges(a, v, dv);
+            const bool h = sp_decide<GENERAL>(msg, ve, dv);
+            hd[v] = h;
+            if (v >= n) a.eZ[b * n + (v - n)] = h; else a.eX[b * n + v] = h;
+        }
+        const bool convFailX = __syncthreads_or(bx), convFailZ = __syncthreads_or(bz);
+        bool sx = false, sz = false;
+        sp_syndrome_fails<GENERAL>(a, syn, hd, sx, sz);
+        const bool synFailX = __syncthreads_or(sx), synFailZ = __syncthreads_or(sz);
+        if (a.q != nullptr)
+            for (int e = tid; e < E; e += nt) a.q[b * E + e] = msg[e];
+        sp_store_status(a, b, sp_fail_flags(synFailX, synFailZ, convFailX, convFailZ), itX, itZ);
+        __syncthreads();  // the workspace is reused by the next syndrome pair
+    }
+}
+
 // ---- CORR: the correlated form (QEC_OPT_CORRELATED) -----
 // The two sectors of a syndrome pair are decoded one after the other inside the workgroup, the first sector F
-// (a.first) exactly as the kernels above decode it -- the scalar p' or, with a.prior, its marginal priors -- and
+// (a.first) exactly as the flooding body decodes it -- the scalar p' or, with a.prior, its marginal priors -- and
 // the second sector S by the prior form with pi_v = d[v] ? c1[v] : c0[v], d = F's final hard decisions, which
 // stay in the workspace's hd bytes.  Workspace layout, grid and workgroup are the scalar plan's.  During a
 // sector's passes the check pass runs threads [0, m_s) and the variable pass threads [0, n) of that sector
@@ -526,10 +607,7 @@ __device__ __forceinline__ void sp_corr_decode(const SparseArgs& a, const uint8_
         }
         if (a.q != nullptr)
             for (int e = tid; e < E; e += nt) a.q[b * E + e] = msg[e];
-        if (tid == 0) {
-            a.flags[b] = (uint8_t)f;
-            if (a.iters != nullptr) { a.iters[2 * b] = itX; a.iters[2 * b + 1] = itZ; }
-        }
+        sp_store_status(a, b, f, itX, itZ);
         __syncthreads();  // the workspace is reused by the next syndrome pair
     }
 }
@@ -586,19 +664,13 @@ __device__ __forceinline__ void sp_serial_decode(const SparseArgs& a, const uint
     const int32_t* offX = a.layOff;
     const int32_t* offZ = a.layOff + LX + 1;
 
-    // one variable's row of the varEdge table; v runs over [X | Z], as the prior array does
-    auto var_row = [&](int v, int& dv) {
-        const bool z = v >= n;
-        dv = z ? a.dvZ : a.dvX;
-        return a.varEdge + (z ? (size_t)n * a.dvX + (size_t)(v - n) * dv : (size_t)v * dv);
-    };
     // the posterior pass over the sectors doX / doZ: decision bytes, and whether a posterior is inside (0.01, 0.99)
     auto posterior = [&](bool doX, bool doZ, bool& bx, bool& bz) {
         for (int v = tid; v < 2 * n; v += nt) {
             const bool z = v >= n;
             if (z ? !doZ : !doX) continue;
             int dv;
-            const int32_t* ve = var_row(v, dv);
+            const int32_t* ve = sp_var_edges(a, v, dv);
             if (GENERAL && ve[0] < 0) { hd[v] = 0; continue; }  // a variable in no check decides 0, enters no test
             const float post = sp_serial_fold<GENERAL>(msg, ve, dv, -1, tab ? a.prior[v] : pp);
             hd[v] = post >= 0.5f;
@@ -692,205 +764,70 @@ __device__ __forceinline__ void sp_serial_decode(const SparseArgs& a, const uint
                 if (!GENERAL || v >= 0) {
                     const int gv = (e < EX ? 0 : n) + v;
                     int dv;
-                    const int32_t* ve = var_row(gv, dv);
+                    const int32_t* ve = sp_var_edges(a, gv, dv);
                     post = sp_serial_fold<GENERAL>(msg, ve, dv, -1, tab ? a.prior[gv] : pp);
                 }
                 a.q[b * E + e] = post;
             }
-        if (tid == 0) {
-            uint32_t f = 0;
-            if (synFailX) f |= QEC_SYNDROME_FAIL_X;
-            if (synFailZ) f |= QEC_SYNDROME_FAIL_Z;
-            if (convFailX) f |= QEC_CONVERGENCE_FAIL_X;
-            if (convFailZ) f |= QEC_CONVERGENCE_FAIL_Z;
-            a.flags[b] = (uint8_t)f;
-            if (a.iters != nullptr) { a.iters[2 * b] = itX; a.iters[2 * b + 1] = itZ; }
-        }
+        sp_store_status(a, b, sp_fail_flags(synFailX, synFailZ, convFailX, convFailZ), itX, itZ);
         __syncthreads();  // the workspace is reused by the next syndrome pair
     }
+}
+
+// ---- the kernels ---------------------------------------------------------------
+// Both entries run the same bodies; they differ in GENERAL and in the degree bytes that a general code brings.
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false, bool SERIAL = false>
+__global__ __launch_bounds__(kSparseThreads) void bp_sparse_kernel(const SparseArgs a)
+{
+    uint8_t* ws = LDS ? sp_lds : a.scratch + (long long)blockIdx.x * a.ws_bytes;
+    if constexpr (SERIAL) sp_serial_decode<STOP, MAXDC, MAXDV, false>(a, nullptr, ws);
+    else if constexpr (CORR) sp_corr_decode<STOP, MAXDC, MAXDV, false>(a, nullptr, ws);
+    else sp_flood_decode<STOP, MAXDC, MAXDV, false, PRIORS>(a, nullptr, ws);
 }
 
 template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false, bool SERIAL = false>
 __global__ __launch_bounds__(kSparseThreads) void bp_general_kernel(const GeneralArgs ga)
 {
-    if constexpr (SERIAL) {
-        sp_serial_decode<STOP, MAXDC, MAXDV, true>(ga.s, ga.chkDeg, LDS ? sp_lds : ga.s.scratch + (long long)blockIdx.x * ga.s.ws_bytes);
-        return;
-    }
-    if constexpr (CORR) {
-        sp_corr_decode<STOP, MAXDC, MAXDV, true>(ga.s, ga.chkDeg, LDS ? sp_lds : ga.s.scratch + (long long)blockIdx.x * ga.s.ws_bytes);
-        return;
-    }
-    const SparseArgs& a = ga.s;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, D = a.dc;
-    const int EX = mX * D, E = m * D;
-    uint8_t* ws = LDS ? sp_lds : a.scratch + (long long)blockIdx.x * a.ws_bytes;
-    float* msg = reinterpret_cast<float*>(ws);            // E floats
-    uint8_t* syn = ws + (size_t)E * sizeof(float);        // m bytes: sX then sZ
-    uint8_t* hd = syn + m;                                // 2n bytes: X then Z hard decisions
-
-    const float pp = 2.0f / 3.0f * a.errorProbability;
-    const float omp = 1.0f - pp;
-    const int N = a.maxIter < 0 ? 0 : a.maxIter;
-
-    for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
-        // the syndrome entry as 0, 1 or 2 = any other value (truthy in the check update, never equal to a
-        // parity in the syndrome tests) with the check's degree above it
-        for (int c = tid; c < m; c += nt) {
-            const uint32_t s = c < mX ? a.sX[b * mX + c] : a.sZ[b * mZ + (c - mX)];
-            const int deg = ga.chkDeg[c];
-            syn[c] = (uint8_t)((s > 1u ? 2u : s) | ((uint32_t)deg << 2));
-        }
-        // one edge per thread, as the regular kernel's initialisation: the sentinel of the check table tells a
-        // real slot from an unused one (coalesced words that every workgroup reads, so they stay in cache)
-        if (PRIORS)
-            for (int e = tid; e < E; e += nt) {
-                const int v = a.chkVar[e];
-                msg[e] = v >= 0 ? a.prior[(e < EX ? 0 : n) + v] : 0.0f;
-            }
-        else
-            for (int e = tid; e < E; e += nt) msg[e] = a.chkVar[e] >= 0 ? pp : 0.0f;
-        __syncthreads();
-
-        bool actX = true, actZ = true;  // workgroup-uniform
-        int itX = 0, itZ = 0;
-        for (int it = 0; it < N && (actX || actZ); ++it) {
-            const bool last = it == N - 1;
-            itX += actX;
-            itZ += actZ;
-            for (int c = tid; c < m; c += nt) {
-                if (c < mX ? !actX : !actZ) continue;
-                const uint32_t sd = syn[c];
-                sp_check_general<MAXDC>(msg + (size_t)c * D, D, (int)(sd >> 2), (sd & 3u) ? 0.5f : -0.5f);
-            }
-            __syncthreads();
-            for (int v = tid; v < 2 * n; v += nt) {
-                const bool z = v >= n;
-                if (z ? !actZ : !actX) continue;
-                const int dv = z ? a.dvZ : a.dvX;
-                const int32_t* ve = a.varEdge + (z ? (size_t)n * a.dvX + (size_t)(v - n) * dv : (size_t)v * dv);
-                const float pv = PRIORS ? a.prior[v] : pp;
-                const bool h = sp_var_general<MAXDV>(msg, ve, dv, pv, PRIORS ? 1.0f - pv : omp, last);
-                if (STOP == QEC_STOP_SYNDROME) hd[v] = h;
-            }
-            __syncthreads();
-            if (STOP == QEC_STOP_REF && it % 10 == 0) {
-                bool bx = false, bz = false;
-                for (int e = tid; e < E; e += nt) {
-                    const bool in = sp_inside(msg[e]);
-                    if (e < EX) bx |= in; else bz |= in;
-                }
-                const bool anyx = __syncthreads_or(bx), anyz = __syncthreads_or(bz);
-                if (actX && !anyx) actX = false;
-                if (actZ && !anyz) actZ = false;
-            } else if (STOP == QEC_STOP_SYNDROME) {
-                bool bx = false, bz = false;
-                for (int c = tid; c < m; c += nt) {
-                    const bool z = c >= mX;
-                    const uint8_t* h = hd + (z ? n : 0);
-                    uint32_t x = 0;
-                    for (int k = 0; k < D; ++k) {  // no early exit: the D loads stay independent
-                        const int v = a.chkVar[(size_t)c * D + k];
-                        x ^= v >= 0 ? (uint32_t)h[v < 0 ? 0 : v] : 0u;
-                    }
-                    if (x != (syn[c] & 3u)) { if (z) bz = true; else bx = true; }
-                }
-                const bool badx = __syncthreads_or(bx), badz = __syncthreads_or(bz);
-                if (actX && !badx) actX = false;
-                if (actZ && !badz) actZ = false;
-            }
-        }
-
-        // ---- post-processing of Decode ----
-        bool bx = false, bz = false;
-        for (int e = tid; e < E; e += nt) {
-            const bool in = sp_inside(msg[e]);
-            if (e < EX) bx |= in; else bz |= in;
-        }
-        for (int v = tid; v < 2 * n; v += nt) {
-            const bool z = v >= n;
-            const int dv = z ? a.dvZ : a.dvX;
-            const int32_t* ve = a.varEdge + (z ? (size_t)n * a.dvX + (size_t)(v - n) * dv : (size_t)v * dv);
-            bool h = false;
-            for (int j = 0; j < dv; ++j) {
-                const int ed = ve[j];
-                h |= ed >= 0 && msg[ed < 0 ? 0 : ed] >= 0.5f;
-            }
-            hd[v] = h;
-            if (z) a.eZ[b * n + (v - n)] = h; else a.eX[b * n + v] = h;
-        }
-        const bool convFailX = __syncthreads_or(bx), convFailZ = __syncthreads_or(bz);
-        bool sx = false, sz = false;
-        for (int c = tid; c < m; c += nt) {
-            const bool z = c >= mX;
-            const uint8_t* h = hd + (z ? n : 0);
-            uint32_t x = 0;
-            for (int k = 0; k < D; ++k) {
-                const int v = a.chkVar[(size_t)c * D + k];
-                x ^= v >= 0 ? (uint32_t)h[v < 0 ? 0 : v] : 0u;
-            }
-            if (x != (syn[c] & 3u)) { if (z) sz = true; else sx = true; }
-        }
-        const bool synFailX = __syncthreads_or(sx), synFailZ = __syncthreads_or(sz);
-        if (a.q != nullptr)
-            for (int e = tid; e < E; e += nt) a.q[b * E + e] = msg[e];
-        if (tid == 0) {
-            uint32_t f = 0;
-            if (synFailX) f |= QEC_SYNDROME_FAIL_X;
-            if (synFailZ) f |= QEC_SYNDROME_FAIL_Z;
-            if (convFailX) f |= QEC_CONVERGENCE_FAIL_X;
-            if (convFailZ) f |= QEC_CONVERGENCE_FAIL_Z;
-            a.flags[b] = (uint8_t)f;
-            if (a.iters != nullptr) { a.iters[2 * b] = itX; a.iters[2 * b + 1] = itZ; }
-        }
-        __syncthreads();  // the workspace is reused by the next syndrome pair
-    }
+    uint8_t* ws = LDS ? sp_lds : ga.s.scratch + (long long)blockIdx.x * ga.s.ws_bytes;
+    if constexpr (SERIAL) sp_serial_decode<STOP, MAXDC, MAXDV, true>(ga.s, ga.chkDeg, ws);
+    else if constexpr (CORR) sp_corr_decode<STOP, MAXDC, MAXDV, true>(ga.s, ga.chkDeg, ws);
+    else sp_flood_decode<STOP, MAXDC, MAXDV, true, PRIORS>(ga.s, ga.chkDeg, ws);
 }
 
 // ---- plan ------------------------------------------------------------------
-using SparseFn = void (*)(const SparseArgs);
-using GeneralFn = void (*)(const GeneralArgs);
+// The kernels of one shape, by variant and stop rule.  SERIAL takes priors as a runtime branch, CORR too.
+enum { kScalar = 0, kPriors = 1, kCorr = 2, kSerial = 3, kVariants = 4 };
+using SparseKernels = const void* [kVariants][3];
 
-// f: the scalar kernels per stop rule; fp: the same shapes with PRIORS; fc: with CORR
-template <int MAXDC, int MAXDV, bool LDS>
-static void general_fns(GeneralFn (&f)[3], GeneralFn (&fp)[3], GeneralFn (&fc)[3])
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL, bool PRIORS, bool CORR, bool SERIAL>
+static const void* sparse_kernel()
 {
-    fc[QEC_STOP_REF] = bp_general_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS, false, true>;
-    fc[QEC_STOP_FIXED] = bp_general_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS, false, true>;
-    fc[QEC_STOP_SYNDROME] = bp_general_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, false, true>;
-    f[QEC_STOP_REF] = bp_general_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS>;
-    f[QEC_STOP_FIXED] = bp_general_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS>;
-    f[QEC_STOP_SYNDROME] = bp_general_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS>;
-    fp[QEC_STOP_REF] = bp_general_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS, true>;
-    fp[QEC_STOP_FIXED] = bp_general_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS, true>;
-    fp[QEC_STOP_SYNDROME] = bp_general_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, true>;
+    if constexpr (GENERAL) return reinterpret_cast<const void*>(&bp_general_kernel<STOP, MAXDC, MAXDV, LDS, PRIORS, CORR, SERIAL>);
+    else return reinterpret_cast<const void*>(&bp_sparse_kernel<STOP, MAXDC, MAXDV, LDS, PRIORS, CORR, SERIAL>);
 }
 
-// fs: the SERIAL kernels per stop rule (priors are their runtime branch: one set per shape)
-template <int MAXDC, int MAXDV, bool LDS>
-static void serial_fns(SparseFn (&fs)[3], GeneralFn (&gfs)[3])
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL>
+static void sparse_kernels_of_stop(SparseKernels& fn)
 {
-    fs[QEC_STOP_REF] = bp_sparse_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS, false, false, true>;
-    fs[QEC_STOP_FIXED] = bp_sparse_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS, false, false, true>;
-    fs[QEC_STOP_SYNDROME] = bp_sparse_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, false, false, true>;
-    gfs[QEC_STOP_REF] = bp_general_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS, false, false, true>;
-    gfs[QEC_STOP_FIXED] = bp_general_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS, false, false, true>;
-    gfs[QEC_STOP_SYNDROME] = bp_general_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, false, false, true>;
+    fn[kScalar][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, false, false>();
+    fn[kPriors][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, true, false, false>();
+    fn[kCorr][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, true, false>();
+    fn[kSerial][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, false, true>();
 }
 
-template <int MAXDC, int MAXDV, bool LDS>
-static void sparse_fns(SparseFn (&f)[3], SparseFn (&fp)[3], SparseFn (&fc)[3])
+template <int MAXDC, int MAXDV, bool LDS, bool GENERAL>
+static void sparse_kernels(SparseKernels& fn)
 {
-    fc[QEC_STOP_REF] = bp_sparse_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS, false, true>;
-    fc[QEC_STOP_FIXED] = bp_sparse_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS, false, true>;
-    fc[QEC_STOP_SYNDROME] = bp_sparse_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, false, true>;
-    f[QEC_STOP_REF] = bp_sparse_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS>;
-    f[QEC_STOP_FIXED] = bp_sparse_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS>;
-    f[QEC_STOP_SYNDROME] = bp_sparse_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS>;
-    fp[QEC_STOP_REF] = bp_sparse_kernel<QEC_STOP_REF, MAXDC, MAXDV, LDS, true>;
-    fp[QEC_STOP_FIXED] = bp_sparse_kernel<QEC_STOP_FIXED, MAXDC, MAXDV, LDS, true>;
-    fp[QEC_STOP_SYNDROME] = bp_sparse_kernel<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, true>;
+    sparse_kernels_of_stop<QEC_STOP_REF, MAXDC, MAXDV, LDS, GENERAL>(fn);
+    sparse_kernels_of_stop<QEC_STOP_FIXED, MAXDC, MAXDV, LDS, GENERAL>(fn);
+    sparse_kernels_of_stop<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, GENERAL>(fn);
+}
+
+template <int MAXDC, int MAXDV>
+static void sparse_kernels_of_shape(bool lds, bool general, SparseKernels& fn)
+{
+    if (lds) { if (general) sparse_kernels<MAXDC, MAXDV, true, true>(fn); else sparse_kernels<MAXDC, MAXDV, true, false>(fn); }
+    else { if (general) sparse_kernels<MAXDC, MAXDV, false, true>(fn); else sparse_kernels<MAXDC, MAXDV, false, false>(fn); }
 }
 
 struct SparsePlan {
@@ -898,22 +835,14 @@ struct SparsePlan {
     bool lds = true;
     long long ws_bytes = 0;
     int grid = 0;
-    SparseFn fn[3] = {nullptr, nullptr, nullptr};
-    SparseFn pfn[3] = {nullptr, nullptr, nullptr};    // the PRIORS kernels of the same shape
-    SparseFn cfn[3] = {nullptr, nullptr, nullptr};    // the CORR kernels of the same shape
+    SparseKernels fn = {};
     // a general code: bp_general_kernel, its degree bytes and its fitted workgroup size
     bool general = false;
-    GeneralFn gfn[3] = {nullptr, nullptr, nullptr};
-    GeneralFn gpfn[3] = {nullptr, nullptr, nullptr};
-    GeneralFn gcfn[3] = {nullptr, nullptr, nullptr};
-    // the SERIAL kernels of the same shape (the route's own set is launched) and their layer tables:
-    // layers = layOrder [mX + mZ], offX [LX + 1], offZ [LZ + 1] (SparseArgs)
-    SparseFn sfn[3] = {nullptr, nullptr, nullptr};
-    GeneralFn gsfn[3] = {nullptr, nullptr, nullptr};
-    DeviceArray<int32_t> layers;
-    int LX = 0, LZ = 0;
     DeviceArray<uint8_t> chkDeg;
     int threads = kSparseThreads;
+    // the SERIAL kernels' layer tables: layers = layOrder [mX + mZ], offX [LX + 1], offZ [LZ + 1] (SparseArgs)
+    DeviceArray<int32_t> layers;
+    int LX = 0, LZ = 0;
     DeviceArray<int32_t> chkVar, varEdge;
     DeviceArray<uint8_t> scratch;
     std::string name;
@@ -999,20 +928,14 @@ void* sparse_plan_create(const Code& c, int device)
     const int wdc = dc <= 8 ? 8 : dc <= 16 ? 16 : 32;
     const int wdv = std::max(dvX, dvZ) <= 4 ? 4 : std::max(dvX, dvZ) <= 8 ? 8 : 16;
     // instantiated shapes: (8,4) (16,8) (32,16); pick the smallest that covers the code
+    if (wdc <= 8 && wdv <= 4) sparse_kernels_of_shape<8, 4>(p->lds, general, p->fn);
+    else if (wdc <= 16 && wdv <= 8) sparse_kernels_of_shape<16, 8>(p->lds, general, p->fn);
+    else sparse_kernels_of_shape<32, 16>(p->lds, general, p->fn);
     if (general) {
-        if (wdc <= 8 && wdv <= 4) { if (p->lds) general_fns<8, 4, true>(p->gfn, p->gpfn, p->gcfn); else general_fns<8, 4, false>(p->gfn, p->gpfn, p->gcfn); }
-        else if (wdc <= 16 && wdv <= 8) { if (p->lds) general_fns<16, 8, true>(p->gfn, p->gpfn, p->gcfn); else general_fns<16, 8, false>(p->gfn, p->gpfn, p->gcfn); }
-        else { if (p->lds) general_fns<32, 16, true>(p->gfn, p->gpfn, p->gcfn); else general_fns<32, 16, false>(p->gfn, p->gpfn, p->gcfn); }
         // the smallest workgroup that gives the wider pass a thread per node
         const long long wide = std::max<long long>(m, 2LL * n);
         p->threads = wide <= 64 ? 64 : wide <= 128 ? 128 : kSparseThreads;
     }
-    else if (wdc <= 8 && wdv <= 4) { if (p->lds) sparse_fns<8, 4, true>(p->fn, p->pfn, p->cfn); else sparse_fns<8, 4, false>(p->fn, p->pfn, p->cfn); }
-    else if (wdc <= 16 && wdv <= 8) { if (p->lds) sparse_fns<16, 8, true>(p->fn, p->pfn, p->cfn); else sparse_fns<16, 8, false>(p->fn, p->pfn, p->cfn); }
-    else { if (p->lds) sparse_fns<32, 16, true>(p->fn, p->pfn, p->cfn); else sparse_fns<32, 16, false>(p->fn, p->pfn, p->cfn); }
-    if (wdc <= 8 && wdv <= 4) { if (p->lds) serial_fns<8, 4, true>(p->sfn, p->gsfn); else serial_fns<8, 4, false>(p->sfn, p->gsfn); }
-    else if (wdc <= 16 && wdv <= 8) { if (p->lds) serial_fns<16, 8, true>(p->sfn, p->gsfn); else serial_fns<16, 8, false>(p->sfn, p->gsfn); }
-    else { if (p->lds) serial_fns<32, 16, true>(p->sfn, p->gsfn); else serial_fns<32, 16, false>(p->sfn, p->gsfn); }
     // the serial schedule's processing order and layer offsets, as positions in one array over both sectors
     std::vector<int32_t> lay, ordX, offX, ordZ, offZ;
     code_layer_order(c, 0, ordX, offX);
@@ -1029,33 +952,18 @@ void* sparse_plan_create(const Code& c, int device)
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
         int per_cu = 1;
         if (p->lds) {
-            const void* fns[3];
-            for (int k = 0; k < 3; ++k)
-                fns[k] = general ? reinterpret_cast<const void*>(p->gfn[k]) : reinterpret_cast<const void*>(p->fn[k]);
-            for (const void* f : fns)
-                if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)p->ws_bytes) != hipSuccess)
-                    throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-            // the PRIORS and CORR kernels take the same dynamic LDS (the grid stays the scalar kernels')
-            for (int k = 0; k < 6; ++k) {
-                const void* f = k < 3 ? (general ? reinterpret_cast<const void*>(p->gpfn[k]) : reinterpret_cast<const void*>(p->pfn[k]))
-                                      : (general ? reinterpret_cast<const void*>(p->gcfn[k - 3]) : reinterpret_cast<const void*>(p->cfn[k - 3]));
-                if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->ws_bytes) != hipSuccess)
-                    throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-            }
-            // and the SERIAL kernels
-            for (int k = 0; k < 3; ++k) {
-                const void* f = general ? reinterpret_cast<const void*>(p->gsfn[k]) : reinterpret_cast<const void*>(p->sfn[k]);
-                if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->ws_bytes) != hipSuccess)
-                    throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-            }
+            // every variant takes the same dynamic LDS (the grid stays the scalar kernels')
+            for (const auto& variant : p->fn)
+                for (const void* f : variant)
+                    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->ws_bytes) != hipSuccess)
+                        throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
             per_cu = std::max(1, std::min(8, (int)((160 * 1024) / p->ws_bytes)));
             // a general code: the same 32 waves per CU at most, in its fitted workgroups
             if (general) {
                 per_cu = std::max(1, std::min(8 * (kSparseThreads / p->threads), (int)((160 * 1024) / p->ws_bytes)));
                 // and no more workgroups than the runtime says are resident at once: one beyond that runs its
                 // share of the batch alone behind the others
-                for (const void* f : fns) {
+                for (const void* f : p->fn[kScalar]) {
                     int resident = 0;
                     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, f, p->threads, (size_t)p->ws_bytes) ==
                             hipSuccess && resident > 0)
@@ -1096,43 +1004,34 @@ void* sparse_plan_create(const Code& c, int device)
 const int32_t* sparse_plan_chkvar(const void* plan) { return static_cast<const SparsePlan*>(plan)->chkVar.data(); }
 const int32_t* sparse_plan_varedge(const void* plan) { return static_cast<const SparsePlan*>(plan)->varEdge.data(); }
 
-// prior: nullptr (the scalar kernels, errorProbability), or the device array of 2n priors (the PRIORS kernels)
-// corr: QEC_OPT_CORRELATED -- 0, or 1 / 2 for the CORR kernels with first sector X / Z; then cond is the device
-// array of the 4n conditional priors when prior is set, and c0 / c1 the scalar pair when it is not
-// serial: QEC_OPT_BP_SCHEDULE -- 1 for the SERIAL kernels (scalar p' or prior; never with corr)
-int launch_decode_sparse(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float errorProbability,
-                         int maxIter, int stop, uint8_t* eX, uint8_t* eZ, uint8_t* flags, int32_t* iters, float* q,
-                         hipStream_t stream, const float* prior, int corr, const float* cond, float c0, float c1,
-                         int serial)
+int launch_decode_sparse(void* plan, const SparseDecode& d, hipStream_t stream)
 {
     auto* p = static_cast<SparsePlan*>(plan);
-    if (B <= 0) return QEC_OK;
+    if (d.B <= 0) return QEC_OK;
+    if (d.corr && d.prior != nullptr && d.cond == nullptr) return fail(QEC_ERR_ARG, "bp_sparse launch: the correlated form needs its conditional tables");
+    if (d.serial && d.corr) return fail(QEC_ERR_UNSUPPORTED, "bp_sparse launch: the serial schedule has no correlated form");
     SparseArgs a{};
-    a.sX = sX; a.sZ = sZ; a.eX = eX; a.eZ = eZ; a.flags = flags; a.iters = iters; a.q = q;
+    a.sX = d.sX; a.sZ = d.sZ; a.eX = d.eX; a.eZ = d.eZ; a.flags = d.flags; a.iters = d.iters; a.q = d.q;
     a.chkVar = p->chkVar.data();
     a.varEdge = p->varEdge.data();
     a.scratch = p->lds ? nullptr : p->scratch.data();
-    a.B = B;
+    a.B = d.B;
     a.ws_bytes = p->ws_bytes;
     a.n = p->n; a.mX = p->mX; a.mZ = p->mZ; a.dc = p->dc; a.dvX = p->dvX; a.dvZ = p->dvZ;
-    a.errorProbability = errorProbability;
-    a.maxIter = maxIter;
-    a.prior = prior;
-    a.first = corr == 2 ? 1 : 0;
-    a.c0 = c0; a.c1 = c1;
-    a.cond = cond;
-    if (corr && prior != nullptr && cond == nullptr) return fail(QEC_ERR_ARG, "bp_sparse launch: the correlated form needs its conditional tables");
-    if (serial && corr) return fail(QEC_ERR_UNSUPPORTED, "bp_sparse launch: the serial schedule has no correlated form");
+    a.errorProbability = d.errorProbability;
+    a.maxIter = d.maxIter;
+    a.prior = d.prior;
+    a.first = d.corr == 2 ? 1 : 0;
+    a.c0 = d.c0; a.c1 = d.c1;
+    a.cond = d.cond;
     a.layOrder = p->layers.data();
     a.layOff = p->layers.data() + p->mX + p->mZ;
     a.LX = p->LX; a.LZ = p->LZ;
-    const unsigned grid = (unsigned)std::min<long long>(B, p->grid);
-    if (p->general) {
-        GeneralArgs ga{a, p->chkDeg.data()};
-        hipLaunchKernelGGL(serial ? p->gsfn[stop] : corr ? p->gcfn[stop] : prior ? p->gpfn[stop] : p->gfn[stop], dim3(grid), dim3(p->threads), p->lds ? (size_t)p->ws_bytes : 0, stream, ga);
-    } else {
-        hipLaunchKernelGGL(serial ? p->sfn[stop] : corr ? p->cfn[stop] : prior ? p->pfn[stop] : p->fn[stop], dim3(grid), dim3(kSparseThreads), p->lds ? (size_t)p->ws_bytes : 0, stream, a);
-    }
+    GeneralArgs ga{a, p->chkDeg.data()};
+    void* args[] = {p->general ? static_cast<void*>(&ga) : static_cast<void*>(&a)};  // the entry's one argument
+    const int variant = d.serial ? kSerial : d.corr ? kCorr : d.prior ? kPriors : kScalar;
+    const unsigned grid = (unsigned)std::min<long long>(d.B, p->grid);
+    (void)hipLaunchKernel(p->fn[variant][d.stop], dim3(grid), dim3(p->threads), args, p->lds ? (size_t)p->ws_bytes : 0, stream);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(QEC_ERR_HIP, std::string("bp_sparse launch: ") + hipGetErrorString(err));
     return QEC_OK;

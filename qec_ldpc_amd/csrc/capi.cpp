@@ -76,10 +76,7 @@ void sparse_plan_free(void* plan);
 const char* sparse_plan_name(const void* plan);
 const int32_t* sparse_plan_chkvar(const void* plan);
 const int32_t* sparse_plan_varedge(const void* plan);
-int launch_decode_sparse(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float errorProbability,
-                         int maxIter, int stop, uint8_t* eX, uint8_t* eZ, uint8_t* flags, int32_t* iters, float* q,
-                         hipStream_t stream, const float* prior, int corr, const float* cond, float c0, float c1,
-                         int serial);
+int launch_decode_sparse(void* plan, const SparseDecode& d, hipStream_t stream);
 int launch_sample_pauli(uint64_t seed, uint64_t start, long long B, int n, const uint64_t* thr, uint8_t* x, uint8_t* z,
                         hipStream_t st);
 int launch_sample_independent(uint64_t seed, uint64_t start, long long B, int n, const float* prior, uint8_t* x,
@@ -1028,18 +1025,21 @@ int dispatch_decode(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, long l
                 return rc;
             eX = d->eX.data(); eZ = d->eZ.data(); flags = d->flags.data();
         }
+        SparseDecode sd;
+        sd.sX = sX; sd.sZ = sZ; sd.B = B; sd.errorProbability = p; sd.maxIter = maxIter; sd.stop = stop;
+        sd.eX = eX; sd.eZ = eZ; sd.flags = flags; sd.iters = iters; sd.q = q;
+        sd.prior = d->prior_dev();
         // QEC_OPT_CORRELATED, read at the call: the CORR kernels, with the handle's conditional tables or the scalar pair
-        const int corr = d->correlated;
-        float c0 = 0.0f, c1 = 0.0f;
-        if (corr) {
-            correlated_priors(p, &c0, &c1);
+        sd.corr = d->correlated;
+        sd.cond = d->cond_dev();
+        if (sd.corr) {
+            correlated_priors(p, &sd.c0, &sd.c1);
             d->last_path |= QEC_PATH_CORRELATED;
         }
         // QEC_OPT_BP_SCHEDULE, read at the call too: the SERIAL kernels (never together with corr: set_option refuses)
-        const int serial = d->bp_schedule;
-        if (serial) d->last_path |= QEC_PATH_SERIAL;
-        rc = launch_decode_sparse(d->sparse, sX, sZ, B, p, maxIter, stop, eX, eZ, flags, iters, q, st, d->prior_dev(), corr,
-                                  d->cond_dev(), c0, c1, serial);
+        sd.serial = d->bp_schedule;
+        if (sd.serial) d->last_path |= QEC_PATH_SERIAL;
+        rc = launch_decode_sparse(d->sparse, sd, st);
         if (!rc && rec != nullptr) rc = launch_pack_decisions(eX, eZ, flags, B, c.n, rec, st);
         if (rc) return rc;
         return ws_release(d, st);

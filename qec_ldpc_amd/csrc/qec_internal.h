@@ -113,4 +113,26 @@ struct McArgsHost {
     long long B = 0;
 };
 
+// One decode launch of the sparse-graph engine (bp_sparse.hip, launch_decode_sparse); every pointer is a device pointer.
+struct SparseDecode {
+    // the decode buffers and the arguments of Decode
+    const uint8_t* sX = nullptr;
+    const uint8_t* sZ = nullptr;
+    long long B = 0;
+    float errorProbability = 0.0f;
+    int maxIter = 0;
+    int stop = QEC_STOP_REF;
+    uint8_t* eX = nullptr;
+    uint8_t* eZ = nullptr;
+    uint8_t* flags = nullptr;
+    int32_t* iters = nullptr;       // nullable
+    float* q = nullptr;             // nullable
+    // the kernel variant and its tables
+    const float* prior = nullptr;   // nullptr: the scalar kernels (errorProbability); else the 2n priors (PRIORS kernels)
+    int corr = 0;                   // QEC_OPT_CORRELATED: 0, or 1 / 2 for the CORR kernels with first sector X / Z
+    const float* cond = nullptr;    // CORR with prior set: the 4n conditional priors
+    float c0 = 0.0f, c1 = 0.0f;     // CORR without prior: the scalar pair (correlated_priors)
+    int serial = 0;                 // QEC_OPT_BP_SCHEDULE: 1 for the SERIAL kernels (scalar p' or prior; never with corr)
+};
+
 }  // namespace qec

@@ -317,7 +317,7 @@ def test_near_hard_option_changes_nothing_under_serial():
 
 
 # ---- the SERIAL kernels of bp_sparse.hip, restated -------------------------------------------------------------------
-# serial_fns / sparse_plan_create: the shape and the workspace are the scalar plan's (plan_of), priors are a runtime
+# sparse_kernels / sparse_plan_create: the shape and the workspace are the scalar plan's (plan_of), priors are a runtime
 # branch of the one kernel, and the route chooses between the two kernels: 2 kernels x 3 shapes x LDS / HBM x 3 stops
 SERIAL_INSTANCES = {(k, s, mem, stop) for k in KERNELS for s in SHAPES for mem in ("lds", "hbm") for stop in STOPS}
 GPU_CASES = CASES  # the case table of tests/test_gpu_serial.py: every row, scalar p and priors, every stop rule
