@@ -212,8 +212,9 @@ struct BpArgs {
     uint32_t nearT[2];
     // lane-relabelled circulant tables (see relabel() below)
     // iteration-0 tables of both sectors computed on the host (launch_decode: the same operations,
-    // so the same bits, as table0_entry on the device; each workgroup copies them to LDS)
-    float tab0[kMaxTab0];
+    // so the same bits, as table0_entry on the device; each workgroup copies them to LDS, four entries
+    // per load)
+    alignas(16) float tab0[kMaxTab0];
     // zero-syndrome outcome of each sector under the fixed / reference stop (zero_outcome; 0: none):
     // kZsValid | decision bit | conv-fail << 1 | syndrome-fail << 2 | iterations << 8
     uint32_t zs[2];
@@ -1260,21 +1261,31 @@ __device__ __forceinline__ uint32_t load_sbits(const BpArgs& a, const Lane& ln, 
     if (in_range) {
         if (a.sbits) {  // bit rows (the Monte-Carlo pipeline's layout)
             const uint32_t* __restrict__ w = reinterpret_cast<const uint32_t*>(s) + (size_t)b * (SEC ? a.wZ : a.wX);
+            // All R words are requested before the first is used (the scheduling barrier): the
+            // minimum-register scheduler otherwise waits for each load before it issues the next, R
+            // memory latencies in a row at the start of every wave.
+            uint32_t wv[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) wv[r] = w[(r * P + wrap(ln.i + SH::template rowoff<SEC>(a, r), P)) >> 5];
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const int c = r * P + wrap(ln.i + SH::template rowoff<SEC>(a, r), P);
-                sbits |= ((w[c >> 5] >> (c & 31)) & 1u) << r;
+                sbits |= ((wv[r] >> (c & 31)) & 1u) << r;
             }
         } else {
             // the check update takes an entry's truthiness (DecoderCPU.h:178) and the syndrome tests
             // compare the entry exactly (:381): an entry other than 0 / 1 decodes as 1 and sets
             // kNonBinary, which fails every syndrome test of the sector (lane_syndrome_ok)
             uint32_t big = 0;
+            uint32_t bv[R];  // requested together, as the words above
+#pragma unroll
+            for (int r = 0; r < R; ++r) bv[r] = s[(size_t)b * m + r * P + wrap(ln.i + SH::template rowoff<SEC>(a, r), P)];
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const uint32_t v = s[(size_t)b * m + r * P + wrap(ln.i + SH::template rowoff<SEC>(a, r), P)];
-                sbits |= (uint32_t)(v != 0u) << r;
-                big |= v;
+                sbits |= (uint32_t)(bv[r] != 0u) << r;
+                big |= bv[r];
             }
             sbits |= big > 1u ? kNonBinary : 0u;
         }
@@ -1562,9 +1573,10 @@ constexpr int waves_per_block() { return TU::kWavesPerBlock; }
 // (stores its flags in the syndrome's merge word), 4: sector Z of a sector launch, enqueued after the X
 // launch on the same stream (stores the flags byte: the merge word OR its own flags).  Modes 3 and 4
 // compile one sector only, so each kernel's registers are allocated for that sector alone.
-template <int RX, int RZ, int L, int STOP, class SH, class TU, int MODE>
+// store_tab0: the kernel's deferred store of the iteration-0 tables (bp_decode_kernel), called once.
+template <int RX, int RZ, int L, int STOP, class SH, class TU, int MODE, class STORE>
 __device__ __forceinline__ void decode_group(const BpArgs& a, const float* __restrict__ tab0, uint8_t* __restrict__ stage,
-                                             int i, int gb, uint32_t b, bool in_range, bool doX)
+                                             int i, int gb, uint32_t b, bool in_range, bool doX, STORE&& store_tab0)
 {
     constexpr bool SPLIT = MODE != 0;
     constexpr bool kHasX = MODE != 4, kHasZ = MODE != 3;
@@ -1581,6 +1593,7 @@ __device__ __forceinline__ void decode_group(const BpArgs& a, const float* __res
     // both sectors' syndrome loads are issued up front: the Z load's latency hides behind X
     const uint32_t sbX = runX ? load_sbits<RX, 0, SH>(a, ln, b, in_range) : 0u;
     const uint32_t sbZ = runZ ? load_sbits<RZ, 1, SH>(a, ln, b, in_range) : 0u;
+    store_tab0();
     if constexpr (kHasX) {
         if (runX) decode_sector<RX, L, 0, STOP, SH, TU, GO>(a, ln, b, in_range, pp, sbX, tab0, flags, itX, stage);
     }
@@ -1645,18 +1658,46 @@ void bp_decode_kernel(const BpArgs a)
     const int gb = kGB ? (lane < kGB ? kGB : kGB + g * P) : g * P;
     // iteration-0 tables of both sectors (iteration0), built by the workgroup before any wave leaves
     constexpr int kTabX = (1 << RX) * RX, kTabZ = (1 << RZ) * RZ;
-    __shared__ float tab0[kTabX + kTabZ];
+    // A sector launch takes its own sector's table only.  From the kernel arguments the copy moves four
+    // entries per thread and instruction; where one such round covers the tables of a sector launch, the
+    // round's load is issued here and its LDS store and the barrier wait until the syndrome loads are under
+    // way (store_tab0, in decode_group), so the table's latency hides behind theirs.  With one wave per
+    // workgroup (P61) all this is per-syndrome work at the head of every wave: with load_sbits' loads
+    // requested together it took the headline from 4.58 to 4.39 ms.  (The one-launch kernels
+    // and the syndrome-stop sector launches keep the store here: holding the four entries across their
+    // syndrome loads spilled 8-20 B.)
+    __shared__ __attribute__((aligned(16))) float tab0[kTabX + kTabZ];
+    constexpr int kLo = MODE == 4 ? kTabX : 0, kHi = MODE == 3 ? kTabX : kTabX + kTabZ;
+    constexpr bool kVec = kTabX + kTabZ <= kMaxTab0 && kLo % 4 == 0 && kHi % 4 == 0;
+    constexpr bool kDeferred = kVec && (MODE == 3 || MODE == 4) && STOP != QEC_STOP_SYNDROME && (kHi - kLo) / 4 <= 64;
+    float4 tv = {0.0f, 0.0f, 0.0f, 0.0f};
+    const int te = kLo / 4 + (int)threadIdx.x;
     {
         const float ppt = 2.0f / 3.0f * a.errorProbability;
-        if constexpr (kTabX + kTabZ <= kMaxTab0) {
+        if constexpr (kVec) {
             (void)ppt;  // from the host (the same operations: same bits, launch_decode)
-            for (int e = threadIdx.x; e < kTabX + kTabZ; e += blockDim.x) tab0[e] = a.tab0[e];
+            const float4* __restrict__ src = reinterpret_cast<const float4*>(a.tab0);
+            if constexpr (kDeferred) {
+                if (te < kHi / 4) tv = src[te];
+            } else {
+                for (int e = te; e < kHi / 4; e += blockDim.x) reinterpret_cast<float4*>(tab0)[e] = src[e];
+            }
+        } else if constexpr (kTabX + kTabZ <= kMaxTab0) {
+            (void)ppt;
+            for (int e = kLo + threadIdx.x; e < kHi; e += blockDim.x) tab0[e] = a.tab0[e];
         } else {
-            for (int e = threadIdx.x; e < kTabX + kTabZ; e += blockDim.x)
+            for (int e = kLo + threadIdx.x; e < kHi; e += blockDim.x)
                 tab0[e] = e < kTabX ? table0_entry<RX, L>(ppt, e) : table0_entry<RZ, L>(ppt, e - kTabX);
         }
-        __syncthreads();
+        if constexpr (!kDeferred) __syncthreads();
     }
+    // every wave of the workgroup calls this exactly once (the barrier)
+    auto store_tab0 = [&]() {
+        if constexpr (kDeferred) {
+            if (te < kHi / 4) reinterpret_cast<float4*>(tab0)[te] = tv;
+            __syncthreads();
+        }
+    };
     // this wave's decision stage for packed records (emit_decisions)
     constexpr int kStage = stage_bytes_per_wave<L, SH>();
     __shared__ __attribute__((aligned(8))) uint8_t stage_all[waves_per_block<TU>() * kStage];
@@ -1701,20 +1742,23 @@ void bp_decode_kernel(const BpArgs a)
             // be hoisted out of this loop into live registers (they spilled at 3 waves per SIMD)
             int il = i, gbl = gb;
             asm volatile("" : "+v"(il), "+v"(gbl));
-            decode_group<RX, RZ, L, STOP, SH, StopTune<STOP, SH, TU>, MODE>(a, tab0, stage, il, gbl, b, in_range, doX);
+            decode_group<RX, RZ, L, STOP, SH, StopTune<STOP, SH, TU>, MODE>(a, tab0, stage, il, gbl, b, in_range, doX, [] {});
         }
         return;
     }
     const long long grp = SPLIT ? wave >> 1 : wave;
     const long long slot = grp * G + g;
     const bool in_range = (g < G) && (slot < a.B);
-    if (!__any(in_range)) return;
+    if (!__any(in_range)) {
+        store_tab0();
+        return;
+    }
     // the syndrome index in 32 bits (launch_decode caps B below 2^31): a 64-bit index live across both
     // sectors spilled at 96 VGPRs
     const bool doX = MODE == 3 || (MODE != 4 && (!SPLIT || (wave & 1) == 0));  // wave-uniform
     const long long pslot = (a.perm_sectors && !doX) ? slot + a.B : slot;
     const uint32_t b = (in_range && a.perm != nullptr) ? (uint32_t)a.perm[pslot] : (uint32_t)slot;
-    decode_group<RX, RZ, L, STOP, SH, StopTune<STOP, SH, TU>, MODE>(a, tab0, stage, i, gb, b, in_range, doX);
+    decode_group<RX, RZ, L, STOP, SH, StopTune<STOP, SH, TU>, MODE>(a, tab0, stage, i, gb, b, in_range, doX, store_tab0);
 }
 
 // ---- variant table ----------------------------------------------------------

@@ -20,6 +20,8 @@ common qec_ldpc_amd/csrc/code_model.cpp -x c++ &
 common qec_ldpc_amd/csrc/cpu_engine.cpp -x c++ &
 common qec_ldpc_amd/csrc/montecarlo.hip &
 common qec_ldpc_amd/csrc/bp_sparse.hip &
+common qec_ldpc_amd/csrc/osd.hip &
+common qec_ldpc_amd/csrc/osd_host.cpp -x c++ &
 wait
 SRC=${SRCDIR:-qec_ldpc_amd/csrc}
 build() {
