@@ -54,6 +54,9 @@ public:
     virtual void SetCorrelated(int order) = 0;
     // The BP schedule (QEC_OPT_BP_SCHEDULE of qec_ldpc.h; no reference analogue): 0 flooding, 1 serial
     virtual void SetBpSchedule(int schedule) = 0;
+    // The BP message rule (QEC_OPT_BP_METHOD / QEC_OPT_MINSUM_SCALE of qec_ldpc.h; no reference analogue): 0 the
+    // product rule, 1 scaled min-sum with alpha = scale / 256
+    virtual void SetBpMethod(int method, int scale = 160) = 0;
     // Per-qubit Pauli channel (qec_decoder_set_pauli_channel; no reference analogue), n entries each
     virtual void SetPauliChannel(const std::vector<float>& pX, const std::vector<float>& pY, const std::vector<float>& pZ) = 0;
     virtual CodeStatistics GetStatistics(int errorWeight, int numErrors, float errorProbability, int maxIterations) = 0;

@@ -88,6 +88,14 @@ public:
     // The BP schedule (QEC_OPT_BP_SCHEDULE): 0 = flooding (the default), 1 = the serial (layered) schedule.  Any other
     // value, and 1 together with SetCorrelated(1 | 2), throws the library's message.
     void SetBpSchedule(int schedule) override { check(qec_decoder_set_option(dec_, QEC_OPT_BP_SCHEDULE, schedule)); }
+    // The BP message rule (QEC_OPT_BP_METHOD): 0 = the product rule (the default), 1 = scaled min-sum in the LLR domain
+    // with alpha = scale / 256 (QEC_OPT_MINSUM_SCALE, 1 .. 256).  Any other value, 1 together with
+    // SetCorrelated(1 | 2) or SetBpSchedule(1) throws the library's message.
+    void SetBpMethod(int method, int scale = 160) override
+    {
+        check(qec_decoder_set_option(dec_, QEC_OPT_MINSUM_SCALE, scale));
+        check(qec_decoder_set_option(dec_, QEC_OPT_BP_METHOD, method));
+    }
     // Per-qubit Pauli channel (qec_decoder_set_pauli_channel): qubit v suffers X, Y or Z with probabilities pX[v],
     // pY[v], pZ[v] (n entries each; Y sets both bits).  Installs the marginal priors, the conditional tables of
     // SetCorrelated and the noise of the device Monte-Carlo run; a later SetPriors or ClearPriors drops it.

@@ -356,12 +356,35 @@ int qec_decoder_device(const qec_decoder* dec);         /* HIP device ordinal (o
  *     decode entry point honours it, the _dev ones read it at the call (a captured graph keeps the kernels it
  *     captured); the OSD stage's soft decode runs the same schedule, so the stage's result then also depends on
  *     the schedule (its column key reads q_final, here the posterior).  The near-hard jump never fires under 1.
- *     A group applies the value to every part. */
+ *     A group applies the value to every part.
+ *   QEC_OPT_BP_METHOD (default 0; 0 or 1, other values QEC_ERR_ARG): BP's message rule.  0 = the reference's fp32
+ *     probability-domain product rule, as ever (the same kernels).  1 = scaled min-sum in the LLR domain, flooding
+ *     ("The min-sum form"; LLR > 0 means the bit is 0).  The state is one fp32 LLR per real edge,
+ *     at the start the channel LLR lambda_v of the edge's variable: qec_minsum_llr of v's prior, or of
+ *     p' = 2.0f / 3.0f * p.  Check update: with a_k = bits(m_k) & 0x7FFFFFFF and g_k = bit 31 of input m_k, slot i
+ *     gets the magnitude alpha * float_of(min as unsigned integers of 0x49800000 (= 2^20) and every a_k, k != i) and
+ *     the sign t XOR the g_k of k != i, t = 1 iff the syndrome entry is non-zero.  Variable update: slot j gets the
+ *     left fold lambda_v + r_0 + r_1 + ... without r_j, in ascending check order; the posterior is the fold over all
+ *     r and the decision is posterior < 0.0f; in iteration N - 1 every slot of v gets the posterior.  A message M is
+ *     inside iff fabsf(M) < 4.5951198f (ln 99).  Stop rules: FIXED N iterations; SYNDROME after the first iteration
+ *     whose decisions satisfy the syndrome; REF at index % 10 == 0 when no real slot is inside.  CONVERGENCE_FAIL: a
+ *     real slot of the final state inside; SYNDROME_FAIL and the estimate from the decisions of the last executed
+ *     variable pass (N = 0: lambda_v < 0.0f); a variable in no check decides 0.  q_final holds the final slots as
+ *     LLRs (an unused slot of a general code +0.0f); every value is finite.  Sparse-graph engine (the MINSUM kernels
+ *     of bp_sparse.hip; plan, workspace, grid and describe string unchanged) and CPU engine; a wave-circulant handle
+ *     refuses 1 with QEC_ERR_UNSUPPORTED and the text says to create the decoder with QEC_ENGINE_SPARSE.  1 together
+ *     with QEC_OPT_CORRELATED != 0 or QEC_OPT_BP_SCHEDULE = 1 is refused with QEC_ERR_UNSUPPORTED by whichever
+ *     qec_decoder_set_option comes second (the handle stays as it was).  Every decode entry point honours it, the
+ *     _dev ones read it at the call and allocate nothing; the OSD stage's soft decode is min-sum too, and the stage,
+ *     qec_osd and qec_osd_dev then order the columns by LLR ascending (q_final is an LLR).  The near-hard jump never
+ *     fires under 1.  A group applies the value to every part.
+ *   QEC_OPT_MINSUM_SCALE (default 160; 1 .. 256, other values QEC_ERR_ARG): the factor of min-sum's check update,
+ *     alpha = (float)value / 256.0f (exact in fp32; the default is 0.625).  Read at the call, as the method is. */
 enum { QEC_OPT_HARD_PATHS = 1, QEC_OPT_CYCLE_JUMP = 2, QEC_OPT_SCHEDULE = 3, QEC_OPT_SECTOR_SPLIT = 4,
        QEC_OPT_PHASE_STATS = 5, QEC_OPT_TRIAGE = 6, QEC_OPT_LAST_PATH = 7, QEC_OPT_MC_DECODE_TIME = 8,
        QEC_OPT_OSD = 9, QEC_OPT_OSD_ITERATIONS = 10, QEC_OPT_OSD_SECTORS = 11, QEC_OPT_OSD_SWEEP = 12,
        QEC_OPT_OSD_ORDER = 13, QEC_OPT_OSD_CS_SECTORS = 14, QEC_OPT_NEAR_HARD_JUMP = 15, QEC_OPT_OSD_SCORE = 16,
-       QEC_OPT_CORRELATED = 17, QEC_OPT_BP_SCHEDULE = 18 };
+       QEC_OPT_CORRELATED = 17, QEC_OPT_BP_SCHEDULE = 18, QEC_OPT_BP_METHOD = 19, QEC_OPT_MINSUM_SCALE = 20 };
 enum {
     QEC_PATH_ORDERED = 1,          /* dispatch order pass (schedule.hip) */
     QEC_PATH_SECTOR_ORDER = 2,     /* ... in the per-sector form (each sector's waves by its own weight) */
@@ -373,7 +396,8 @@ enum {
     QEC_PATH_RECORDS = 128,        /* packed decision records out */
     QEC_PATH_OSD = 256,            /* the call ran the OSD stage (QEC_OPT_OSD) */
     QEC_PATH_CORRELATED = 512,     /* one sector decoded under priors conditioned on the other's estimate */
-    QEC_PATH_SERIAL = 1024         /* BP under the serial schedule (QEC_OPT_BP_SCHEDULE = 1) */
+    QEC_PATH_SERIAL = 1024,        /* BP under the serial schedule (QEC_OPT_BP_SCHEDULE = 1) */
+    QEC_PATH_MINSUM = 2048         /* scaled min-sum BP (QEC_OPT_BP_METHOD = 1) */
 };
 /* The near-hard jump's threshold for p' = pPrime (the float (2/3) errorProbability the decoder forms), R
  * checks per variable and L variables per check: *eps0 = the largest power of two in [2^-20, 2^-8] with
@@ -427,6 +451,14 @@ int qec_decoder_get_priors(const qec_decoder* dec, float* priorX, float* priorZ)
  * the option's value): 1 and the arrays filled (n entries each, 0 .. 4095; a NULL array is skipped) if
  * priors are set, 0 if not. */
 int qec_decoder_get_osd_weights(const qec_decoder* dec, int32_t* wX, int32_t* wZ);
+/* The channel LLR of the min-sum form (QEC_OPT_BP_METHOD = 1) for a prior pi: *llr = (float) log((1 - pi) / pi),
+ * the float taken exactly to double and the result rounded once, clamped to [-2^30, +2^30]: pi = 0 gives
+ * +1073741824.0f, pi = 1 gives -1073741824.0f and pi = 1/2 gives +0.0f.  Both engines decode with exactly these
+ * values. */
+int qec_minsum_llr(float prior, float* llr);
+/* The channel LLR tables that every qec_decoder_set_priors builds (whatever QEC_OPT_BP_METHOD says): the arrays
+ * filled (n floats each; a NULL array is skipped).  QEC_ERR_ARG if no priors are set. */
+int qec_decoder_get_minsum_llr(const qec_decoder* dec, float* llrX, float* llrZ);
 /* The scalar tables of QEC_OPT_CORRELATED for depolarising noise of strength p: *c1 = P(other bit | this bit
  * set) = 0.5f and *c0 = P(other bit | this bit clear) = (p / 3.0f) / (1.0f - 2.0f / 3.0f * p), every operation
  * in fp32.  Both engines decode with exactly these values. */

@@ -29,13 +29,16 @@ ENGINE = {"auto": 0, "circulant": 1, "sparse": 2, "cpu": 3}
 OPTION = {"hard_paths": 1, "cycle_jump": 2, "schedule": 3, "sector_split": 4, "phase_stats": 5, "triage": 6,
           "last_path": 7, "mc_decode_time": 8, "osd": 9, "osd_iterations": 10, "osd_sectors": 11,
           "osd_sweep": 12, "osd_order": 13, "osd_cs_sectors": 14, "near_hard": 15, "osd_score": 16,
-          "correlated": 17, "bp_schedule": 18}
+          "correlated": 17, "bp_schedule": 18, "bp_method": 19, "minsum_scale": 20}
 OPTIONS = OPTION
 # values of the "bp_schedule" option (QEC_OPT_BP_SCHEDULE)
 BP_SCHEDULE = {"flooding": 0, "serial": 1}
+# values of the "bp_method" option (QEC_OPT_BP_METHOD)
+BP_METHOD = {"product": 0, "minsum": 1}
 # QEC_PATH_* bits of QEC_OPT_LAST_PATH (include/qec_ldpc.h): the launch sequence of the last decode call
 PATH = {"ordered": 1, "sector_order": 2, "split_waves": 4, "sector_launches": 8, "triage": 16, "bit_rows": 32,
-        "sparse": 64, "records": 128, "osd": 256, "correlated": 512, "serial": 1024}
+        "sparse": 64, "records": 128, "osd": 256, "correlated": 512, "serial": 1024,
+        "minsum": 2048}
 
 # every symbol include/qec_ldpc.h declares
 EXPORTS = (
@@ -49,7 +52,7 @@ EXPORTS = (
     "qec_decoder_num_parts", "qec_decoder_part", "qec_decoder_device", "qec_decoder_describe",
     "qec_decoder_set_option", "qec_decoder_get_option", "qec_near_hard_threshold",
     "qec_decoder_set_priors", "qec_decoder_get_priors", "qec_decoder_get_osd_weights", "qec_sample_independent_dev",
-    "qec_correlated_priors", "qec_decoder_set_pauli_channel", "qec_decoder_get_pauli_channel",
+    "qec_correlated_priors", "qec_minsum_llr", "qec_decoder_get_minsum_llr", "qec_decoder_set_pauli_channel", "qec_decoder_get_pauli_channel",
     "qec_decoder_get_conditional_priors", "qec_sample_pauli_dev",
     "qec_decode_batch", "qec_decode_batch_dev", "qec_decode_batch_packed", "qec_decode_batch_packed_dev",
     "qec_decode_bits_packed_dev",
@@ -154,6 +157,8 @@ def lib():
             "qec_decoder_get_osd_weights": (i, [vp, vp, vp]),
             "qec_sample_independent_dev": (i, [vp, ctypes.c_uint64, ctypes.c_uint64, sz, vp, vp, vp]),
             "qec_correlated_priors": (i, [f, vp, vp]),
+            "qec_minsum_llr": (i, [f, vp]),
+            "qec_decoder_get_minsum_llr": (i, [vp, vp, vp]),
             "qec_decoder_set_pauli_channel": (i, [vp, vp, vp, vp]),
             "qec_decoder_get_pauli_channel": (i, [vp, vp, vp, vp]),
             "qec_decoder_get_conditional_priors": (i, [vp, vp, vp, vp, vp]),
@@ -210,6 +215,14 @@ def correlated_priors(p):
     c0, c1 = ctypes.c_float(0.0), ctypes.c_float(0.0)
     _check(lib().qec_correlated_priors(float(np.float32(p)), ctypes.byref(c0), ctypes.byref(c1)), "qec_correlated_priors")
     return np.float32(c0.value), np.float32(c1.value)
+
+
+def minsum_llr(prior):
+    """qec_minsum_llr: the channel LLR of min-sum BP (set_option("bp_method", 1)) for a prior (a float32), as
+    float32: (float) log((1 - prior) / prior) clamped to +-2^30; > 0 means the bit is 0."""
+    llr = ctypes.c_float(0.0)
+    _check(lib().qec_minsum_llr(float(np.float32(prior)), ctypes.byref(llr)), "qec_minsum_llr")
+    return np.float32(llr.value)
 
 
 def _check(rc, what):
@@ -557,6 +570,14 @@ class DecoderGPU:
         if rc < 0:
             raise QecError("qec_decoder_get_osd_weights failed (%d): %s" % (rc, last_error()))
         return (wX, wZ) if rc == 1 else None
+
+    def minsum_llr(self):
+        """(llrX, llrZ) as float32 arrays (qec_decoder_get_minsum_llr): the channel LLRs of the handle's priors,
+        which min-sum BP (set_option("bp_method", 1)) decodes under; raises QecError when no priors are set."""
+        lX = np.empty(self.code.n, dtype=np.float32)
+        lZ = np.empty(self.code.n, dtype=np.float32)
+        _check(lib().qec_decoder_get_minsum_llr(self._h, _ptr(lX), _ptr(lZ)), "qec_decoder_get_minsum_llr")
+        return lX, lZ
 
     def last_path(self):
         """The launch sequence of this handle's last decode call (QEC_OPT_LAST_PATH) as a set of

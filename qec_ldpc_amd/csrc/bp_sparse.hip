@@ -21,8 +21,8 @@
 // race-free; passes are separated by workgroup barriers.
 //
 // Two kernel entries, bp_sparse_kernel (regular codes) and bp_general_kernel (codes given by two matrices, any
-// degrees), run the same three decode bodies -- sp_flood_decode (the flooding schedule, scalar p' or PRIORS),
-// sp_corr_decode (CORR) and sp_serial_decode (SERIAL) -- each templated on GENERAL, which selects the table
+// degrees), run the same four decode bodies -- sp_flood_decode (the flooding schedule, scalar p' or PRIORS),
+// sp_corr_decode (CORR), sp_serial_decode (SERIAL) and sp_minsum_decode (MINSUM) -- each templated on GENERAL, which selects the table
 // sentinels, the packed syndrome byte and the update functions; everything around the updates (loops, stop tests,
 // post-processing, flags) is one text for both routes.  The plan keeps one table of kernels, by variant and stop rule.
 //
@@ -774,36 +774,225 @@ __device__ __forceinline__ void sp_serial_decode(const SparseArgs& a, const uint
     }
 }
 
+// ---- MINSUM: scaled min-sum in the LLR domain (QEC_OPT_BP_METHOD = 1) -----
+// The flooding schedule over LLRs (> 0: the bit is 0): the message array holds the variable->check message of every
+// edge after a variable pass and the check->variable message after a check pass, as in the flooding body, with the
+// barriers where that body has them.  Only fp32 adds, one fp32 multiply by alpha = k / 256 and integer operations on
+// bit patterns occur, so every value is finite.  The argument block is SparseArgs as it stands, so that the other
+// kernels' code does not move: errorProbability carries the scalar channel LLR lambda(p'), prior (workgroup-uniform:
+// null or not) the 2n channel LLRs of the handle's priors, c0 the factor alpha.
+//   * check pass: thread per check, one pass over its row for the first minimum, the second minimum and the argmin
+//     of the magnitudes' bit patterns (compared as unsigned integers, capped by K = the pattern of 2^20) and the XOR
+//     of the sign bits with the syndrome bit; a second pass stores alpha * (second minimum where the slot is the
+//     argmin, else the first) under the slot's sign.  Five live values instead of the product rule's MAXDC factors;
+//     the row is read twice from the workspace instead.  (Keeping the row's MAXDC patterns in registers between the
+//     passes, loaded together as sp_check loads them, measured 8 % faster per iteration on hgp_ham and 6 % / 9 %
+//     slower on QC_LDPC_CSS(3,3,6,13,3,2) / P61: profiles/minsum.json, cost_row_in_registers.)
+//   * a general code's unused slot holds the float K throughout: sign 0 and a magnitude that is not below the cap,
+//     so it changes neither a minimum nor the parity; it is stored back as K by a select on the check's degree, is
+//     outside the inside band by itself, and the export writes +0.0f for it.
+//   * variable pass: thread per variable, the prefix form of sp_var with + for * and no division.  A general code's
+//     padded entry enters the folds as +0.0f, chosen by a select, behind the real ones.  x + (+0.0f) == x bit for
+//     bit for every finite x but -0.0f, and a fold never holds -0.0f there: it starts from a channel LLR, which
+//     minsum_llr never returns as -0.0f, and a sum of two floats is -0.0f only when both are.  So the padding is
+//     exact without a predicate on the adds; entry j is skipped by a scalar branch when no lane of the wave has it.
+//     The fold over all entries is the posterior; its sign is the decision byte, written every iteration.
+//   * the post-processing reads the decision bytes of the last executed variable pass (N = 0: of the channel LLRs).
+__device__ __forceinline__ bool sp_minsum_inside(float x) { return __builtin_fabsf(x) < kMinSumInside; }
+
+template <bool GENERAL>
+__device__ __forceinline__ void sp_minsum_check(float* __restrict__ m, int dc, uint32_t sd, float alpha)
+{
+    uint32_t min1 = kMinSumCap, min2 = kMinSumCap;
+    uint32_t par = GENERAL ? ((sd & 3u) != 0u) : (sd != 0u);
+    int arg = -1;
+    for (int k = 0; k < dc; ++k) {
+        const uint32_t b = __float_as_uint(m[k]);
+        const uint32_t a = b & 0x7FFFFFFFu;
+        par ^= b >> 31;
+        const bool lt1 = a < min1, lt2 = a < min2;
+        min2 = lt1 ? min1 : lt2 ? a : min2;
+        arg = lt1 ? k : arg;
+        min1 = lt1 ? a : min1;
+    }
+    const uint32_t o1 = __float_as_uint(alpha * __uint_as_float(min1));
+    const uint32_t o2 = __float_as_uint(alpha * __uint_as_float(min2));
+    const int deg = GENERAL ? (int)(sd >> 2) : dc;
+    for (int i = 0; i < dc; ++i) {
+        const uint32_t b = __float_as_uint(m[i]);
+        const uint32_t o = (i == arg ? o2 : o1) | ((par ^ (b >> 31)) << 31);
+        m[i] = __uint_as_float(!GENERAL || i < deg ? o : kMinSumCap);  // an unused slot keeps K
+    }
+}
+
+// One variable's update from its channel LLR; returns its decision (posterior < 0; a variable in no check decides 0)
+template <int MAXDV, bool GENERAL>
+__device__ __forceinline__ bool sp_minsum_var(float* __restrict__ msg, const int32_t* __restrict__ ve, int dv, float lam,
+                                              bool last)
+{
+    int idx[MAXDV];
+    bool use[MAXDV];  // GENERAL: wave-uniform, some active lane has entry j
+    float r[MAXDV];
+#pragma unroll
+    for (int j = 0; j < MAXDV; ++j) {
+        idx[j] = -1;  // past the stride (which differs between the lanes of a wave that spans both sectors)
+        if (j < dv) idx[j] = ve[j];
+        use[j] = GENERAL ? __builtin_amdgcn_ballot_w64(idx[j] >= 0) != 0 : j < dv;
+    }
+#pragma unroll
+    for (int j = 0; j < MAXDV; ++j)
+        if (use[j]) {
+            const bool real = idx[j] >= 0;
+            // a padded lane reads slot 0, which its owner may be rewriting in this pass: the select drops the value
+            const float x = msg[real ? idx[j] : 0];
+            r[j] = real ? x : 0.0f;
+        }
+    float post = lam;
+    if (last) {  // the last iteration of the cap: every slot receives the posterior
+#pragma unroll
+        for (int k = 0; k < MAXDV; ++k)
+            if (use[k]) post = post + r[k];
+#pragma unroll
+        for (int j = 0; j < MAXDV; ++j)
+            if (use[j] && idx[j] >= 0) msg[idx[j]] = post;
+    } else {
+        // in place: every incoming message is in r[] already, and the edge has no other owner in this pass
+#pragma unroll
+        for (int j = 0; j < MAXDV; ++j)
+            if (use[j]) {
+                float t = post;  // lam + r_0 + ... + r_{j-1}
+#pragma unroll
+                for (int k = j + 1; k < MAXDV; ++k)
+                    if (use[k]) t = t + r[k];
+                if (idx[j] >= 0) msg[idx[j]] = t;
+                post = post + r[j];
+            }
+    }
+    return idx[0] >= 0 && post < 0.0f;
+}
+
+template <int STOP, int MAXDC, int MAXDV, bool GENERAL>
+__device__ __forceinline__ void sp_minsum_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws)
+{
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
+    const int EX = mX * dc, E = m * dc;
+    float* msg = reinterpret_cast<float*>(ws);            // E floats
+    uint8_t* syn = ws + (size_t)E * sizeof(float);        // m bytes: sX then sZ
+    uint8_t* hd = syn + m;                                // 2n bytes: X then Z decisions
+
+    const float lam0 = a.errorProbability, alpha = a.c0;
+    const float* llr = a.prior;
+    const bool tab = llr != nullptr;  // workgroup-uniform: per-variable channel LLRs or the scalar one
+    const int N = a.maxIter < 0 ? 0 : a.maxIter;
+
+    auto any_inside = [&](bool& bx, bool& bz) {
+        for (int e = tid; e < E; e += nt) {
+            const bool in = sp_minsum_inside(msg[e]);
+            if (e < EX) bx |= in; else bz |= in;
+        }
+    };
+
+    for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
+        sp_load_syndromes<GENERAL>(a, chkDeg, b, syn);
+        for (int e = tid; e < E; e += nt) {
+            const int v = (GENERAL || tab) ? a.chkVar[e] : 0;
+            float x = __uint_as_float(kMinSumCap);  // an unused slot of a general code
+            if (!GENERAL || v >= 0) x = tab ? llr[(e < EX ? 0 : n) + v] : lam0;
+            msg[e] = x;
+        }
+        for (int v = tid; v < 2 * n; v += nt) {  // the decisions of N = 0
+            int dv;
+            const int32_t* ve = sp_var_edges(a, v, dv);
+            hd[v] = dv > 0 && (!GENERAL || ve[0] >= 0) && (tab ? llr[v] : lam0) < 0.0f;
+        }
+        __syncthreads();
+
+        bool actX = true, actZ = true;  // workgroup-uniform
+        int itX = 0, itZ = 0;
+        for (int it = 0; it < N && (actX || actZ); ++it) {
+            const bool last = it == N - 1;
+            itX += actX;
+            itZ += actZ;
+            for (int c = tid; c < m; c += nt) {
+                if (c < mX ? !actX : !actZ) continue;
+                sp_minsum_check<GENERAL>(msg + (size_t)c * dc, dc, syn[c], alpha);
+            }
+            __syncthreads();
+            for (int v = tid; v < 2 * n; v += nt) {
+                if (v >= n ? !actZ : !actX) continue;
+                int dv;
+                const int32_t* ve = sp_var_edges(a, v, dv);
+                hd[v] = sp_minsum_var<MAXDV, GENERAL>(msg, ve, dv, tab ? llr[v] : lam0, last);
+            }
+            __syncthreads();
+            if (STOP == QEC_STOP_REF && it % 10 == 0) {
+                bool bx = false, bz = false;
+                any_inside(bx, bz);
+                const bool anyx = __syncthreads_or(bx), anyz = __syncthreads_or(bz);
+                if (actX && !anyx) actX = false;
+                if (actZ && !anyz) actZ = false;
+            } else if (STOP == QEC_STOP_SYNDROME) {
+                bool bx = false, bz = false;
+                sp_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
+                const bool badx = __syncthreads_or(bx), badz = __syncthreads_or(bz);
+                if (actX && !badx) actX = false;
+                if (actZ && !badz) actZ = false;
+            }
+        }
+
+        // ---- the final state: flags from the slots and from the decision bytes, q_final ----
+        bool bx = false, bz = false;
+        any_inside(bx, bz);
+        for (int v = tid; v < 2 * n; v += nt) {
+            if (v >= n) a.eZ[b * n + (v - n)] = hd[v]; else a.eX[b * n + v] = hd[v];
+        }
+        const bool convFailX = __syncthreads_or(bx), convFailZ = __syncthreads_or(bz);
+        bool sx = false, sz = false;
+        sp_syndrome_fails<GENERAL>(a, syn, hd, sx, sz);
+        const bool synFailX = __syncthreads_or(sx), synFailZ = __syncthreads_or(sz);
+        if (a.q != nullptr)
+            for (int e = tid; e < E; e += nt) a.q[b * E + e] = (!GENERAL || a.chkVar[e] >= 0) ? msg[e] : 0.0f;
+        sp_store_status(a, b, sp_fail_flags(synFailX, synFailZ, convFailX, convFailZ), itX, itZ);
+        __syncthreads();  // the workspace is reused by the next syndrome pair
+    }
+}
+
 // ---- the kernels ---------------------------------------------------------------
 // Both entries run the same bodies; they differ in GENERAL and in the degree bytes that a general code brings.
-template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false, bool SERIAL = false>
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false, bool SERIAL = false,
+          bool MINSUM = false>
 __global__ __launch_bounds__(kSparseThreads) void bp_sparse_kernel(const SparseArgs a)
 {
     uint8_t* ws = LDS ? sp_lds : a.scratch + (long long)blockIdx.x * a.ws_bytes;
-    if constexpr (SERIAL) sp_serial_decode<STOP, MAXDC, MAXDV, false>(a, nullptr, ws);
+    if constexpr (MINSUM) sp_minsum_decode<STOP, MAXDC, MAXDV, false>(a, nullptr, ws);
+    else if constexpr (SERIAL) sp_serial_decode<STOP, MAXDC, MAXDV, false>(a, nullptr, ws);
     else if constexpr (CORR) sp_corr_decode<STOP, MAXDC, MAXDV, false>(a, nullptr, ws);
     else sp_flood_decode<STOP, MAXDC, MAXDV, false, PRIORS>(a, nullptr, ws);
 }
 
-template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false, bool SERIAL = false>
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false, bool SERIAL = false,
+          bool MINSUM = false>
 __global__ __launch_bounds__(kSparseThreads) void bp_general_kernel(const GeneralArgs ga)
 {
     uint8_t* ws = LDS ? sp_lds : ga.s.scratch + (long long)blockIdx.x * ga.s.ws_bytes;
-    if constexpr (SERIAL) sp_serial_decode<STOP, MAXDC, MAXDV, true>(ga.s, ga.chkDeg, ws);
+    if constexpr (MINSUM) sp_minsum_decode<STOP, MAXDC, MAXDV, true>(ga.s, ga.chkDeg, ws);
+    else if constexpr (SERIAL) sp_serial_decode<STOP, MAXDC, MAXDV, true>(ga.s, ga.chkDeg, ws);
     else if constexpr (CORR) sp_corr_decode<STOP, MAXDC, MAXDV, true>(ga.s, ga.chkDeg, ws);
     else sp_flood_decode<STOP, MAXDC, MAXDV, true, PRIORS>(ga.s, ga.chkDeg, ws);
 }
 
 // ---- plan ------------------------------------------------------------------
-// The kernels of one shape, by variant and stop rule.  SERIAL takes priors as a runtime branch, CORR too.
-enum { kScalar = 0, kPriors = 1, kCorr = 2, kSerial = 3, kVariants = 4 };
+// The kernels of one shape, by variant and stop rule.  SERIAL takes priors as a runtime branch, CORR and MINSUM too.
+enum { kScalar = 0, kPriors = 1, kCorr = 2, kSerial = 3, kMinSum = 4, kVariants = 5 };
 using SparseKernels = const void* [kVariants][3];
 
-template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL, bool PRIORS, bool CORR, bool SERIAL>
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL, bool PRIORS, bool CORR, bool SERIAL, bool MINSUM = false>
 static const void* sparse_kernel()
 {
-    if constexpr (GENERAL) return reinterpret_cast<const void*>(&bp_general_kernel<STOP, MAXDC, MAXDV, LDS, PRIORS, CORR, SERIAL>);
-    else return reinterpret_cast<const void*>(&bp_sparse_kernel<STOP, MAXDC, MAXDV, LDS, PRIORS, CORR, SERIAL>);
+    if constexpr (GENERAL)
+        return reinterpret_cast<const void*>(&bp_general_kernel<STOP, MAXDC, MAXDV, LDS, PRIORS, CORR, SERIAL, MINSUM>);
+    else return reinterpret_cast<const void*>(&bp_sparse_kernel<STOP, MAXDC, MAXDV, LDS, PRIORS, CORR, SERIAL, MINSUM>);
 }
 
 template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL>
@@ -813,6 +1002,7 @@ static void sparse_kernels_of_stop(SparseKernels& fn)
     fn[kPriors][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, true, false, false>();
     fn[kCorr][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, true, false>();
     fn[kSerial][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, false, true>();
+    fn[kMinSum][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, false, false, true>();
 }
 
 template <int MAXDC, int MAXDV, bool LDS, bool GENERAL>
@@ -1010,6 +1200,10 @@ int launch_decode_sparse(void* plan, const SparseDecode& d, hipStream_t stream)
     if (d.B <= 0) return QEC_OK;
     if (d.corr && d.prior != nullptr && d.cond == nullptr) return fail(QEC_ERR_ARG, "bp_sparse launch: the correlated form needs its conditional tables");
     if (d.serial && d.corr) return fail(QEC_ERR_UNSUPPORTED, "bp_sparse launch: the serial schedule has no correlated form");
+    if (d.minsum && (d.corr || d.serial))
+        return fail(QEC_ERR_UNSUPPORTED, "bp_sparse launch: min-sum has no correlated form and no serial schedule");
+    if (d.minsum && d.prior != nullptr && d.llr == nullptr)
+        return fail(QEC_ERR_ARG, "bp_sparse launch: min-sum under priors needs its LLR tables");
     SparseArgs a{};
     a.sX = d.sX; a.sZ = d.sZ; a.eX = d.eX; a.eZ = d.eZ; a.flags = d.flags; a.iters = d.iters; a.q = d.q;
     a.chkVar = p->chkVar.data();
@@ -1027,9 +1221,14 @@ int launch_decode_sparse(void* plan, const SparseDecode& d, hipStream_t stream)
     a.layOrder = p->layers.data();
     a.layOff = p->layers.data() + p->mX + p->mZ;
     a.LX = p->LX; a.LZ = p->LZ;
+    if (d.minsum) {  // the MINSUM kernels' reading of the argument block (sp_minsum_decode)
+        a.errorProbability = d.lam;
+        a.prior = d.prior != nullptr ? d.llr : nullptr;
+        a.c0 = (float)d.minsum / 256.0f;
+    }
     GeneralArgs ga{a, p->chkDeg.data()};
     void* args[] = {p->general ? static_cast<void*>(&ga) : static_cast<void*>(&a)};  // the entry's one argument
-    const int variant = d.serial ? kSerial : d.corr ? kCorr : d.prior ? kPriors : kScalar;
+    const int variant = d.minsum ? kMinSum : d.serial ? kSerial : d.corr ? kCorr : d.prior ? kPriors : kScalar;
     const unsigned grid = (unsigned)std::min<long long>(d.B, p->grid);
     (void)hipLaunchKernel(p->fn[variant][d.stop], dim3(grid), dim3(p->threads), args, p->lds ? (size_t)p->ws_bytes : 0, stream);
     hipError_t err = hipGetLastError();

@@ -86,7 +86,8 @@ void cpu_plan_free(void* plan);
 int cpu_threads();
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
-                     bool near_hard, const float* prior, int corr, const float* cond, int serial);
+                     bool near_hard, const float* prior, int corr, const float* cond, int serial, int minsum,
+                     const float* llr);
 void correlated_priors(float p, float* c0, float* c1);
 int launch_pack_decisions(const uint8_t* eX, const uint8_t* eZ, const uint8_t* flags, long long B, int n, uint8_t* out,
                           hipStream_t st);
@@ -98,7 +99,7 @@ OsdDevPlan* osd_dev_create(const OsdPlan& P);
 void osd_dev_free(OsdDevPlan* D);
 int launch_osd(const OsdDevPlan* D, int sweep, int order, const uint8_t* sX, const uint8_t* sZ, long long B, const float* q,
                uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint32_t* repaired, uint32_t* swept, const int32_t* w,
-               hipStream_t st);
+               hipStream_t st, bool llr);
 int launch_osd_collect(const uint8_t* rec, int rstride, int n, long long B, int32_t* list, uint32_t* count,
                        hipStream_t st);
 int launch_osd_gather(const int32_t* list, long long cnt, const uint8_t* sX, const uint8_t* sZ, bool bits, int mX,
@@ -169,6 +170,16 @@ struct qec_decoder {
     // priors: c0 = c1 = the marginal; a Pauli channel: its four tables); device copy as dpri
     int correlated = 0;
     int bp_schedule = 0;            // QEC_OPT_BP_SCHEDULE: 0 flooding, 1 the serial schedule
+    // QEC_OPT_BP_METHOD (0 the product rule, 1 scaled min-sum; DESIGN.md section 2, "The min-sum form") and
+    // QEC_OPT_MINSUM_SCALE (alpha = k / 256); the channel LLRs of the priors, sector X [n] then Z [n], built by every
+    // set whatever the method says, as the OSD weight tables are; device copy as dpri
+    int bp_method = 0;
+    int minsum_scale = kMinSumDefaultScale;
+    std::vector<float> mllr;
+    DeviceArray<float> dmllr;
+    int minsum() const { return bp_method == 1 ? minsum_scale : 0; }  // the engines' argument: 0, or the scale
+    const float* llr_host() const { return has_priors ? mllr.data() : nullptr; }
+    const float* llr_dev() const { return has_priors ? dmllr.data() : nullptr; }
     std::vector<float> cond;
     DeviceArray<float> dcond;
     const float* cond_host() const { return has_priors ? cond.data() : nullptr; }
@@ -721,6 +732,10 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
             return fail(QEC_ERR_UNSUPPORTED,
                         "qec_decoder_set_option: QEC_OPT_CORRELATED has no form under the serial schedule; set "
                         "QEC_OPT_BP_SCHEDULE to 0 (flooding) first");
+        if (value && d->bp_method)
+            return fail(QEC_ERR_UNSUPPORTED,
+                        "qec_decoder_set_option: QEC_OPT_CORRELATED has no min-sum form; set QEC_OPT_BP_METHOD to 0 (the "
+                        "product rule) first");
         d->correlated = value;
         return QEC_OK;
     case QEC_OPT_BP_SCHEDULE:
@@ -735,7 +750,33 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
             return fail(QEC_ERR_UNSUPPORTED,
                         "qec_decoder_set_option: the serial schedule has no correlated form; set QEC_OPT_CORRELATED to 0 "
                         "first");
+        if (value && d->bp_method)
+            return fail(QEC_ERR_UNSUPPORTED,
+                        "qec_decoder_set_option: min-sum is built for the flooding schedule; set QEC_OPT_BP_METHOD to 0 (the "
+                        "product rule) first");
         d->bp_schedule = value;
+        return QEC_OK;
+    case QEC_OPT_BP_METHOD:
+        if (value != 0 && value != 1)
+            return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_BP_METHOD is 0 (the product rule) or 1 (scaled min-sum)");
+        if (value && d->parts.empty() && !d->cpu && d->engine != QEC_ENGINE_SPARSE)
+            return fail(QEC_ERR_UNSUPPORTED,
+                        "qec_decoder_set_option: QEC_OPT_BP_METHOD = 1 (min-sum) is not built for the wave-circulant engine, "
+                        "whose kernels and hard-message shortcuts are the product rule's; create the decoder with "
+                        "QEC_ENGINE_SPARSE (engine \"sparse\")");
+        if (value && d->correlated)
+            return fail(QEC_ERR_UNSUPPORTED,
+                        "qec_decoder_set_option: min-sum has no correlated form; set QEC_OPT_CORRELATED to 0 first");
+        if (value && d->bp_schedule)
+            return fail(QEC_ERR_UNSUPPORTED,
+                        "qec_decoder_set_option: min-sum is built for the flooding schedule; set QEC_OPT_BP_SCHEDULE to 0 "
+                        "(flooding) first");
+        d->bp_method = value;
+        return QEC_OK;
+    case QEC_OPT_MINSUM_SCALE:
+        if (value < 1 || value > 256)
+            return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_MINSUM_SCALE is 1 .. 256 (alpha = value / 256)");
+        d->minsum_scale = value;
         return QEC_OK;
     case QEC_OPT_OSD_CS_SECTORS:
         return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD_CS_SECTORS is read only");
@@ -772,6 +813,8 @@ static int install_priors(qec_decoder* d, const char* who, const float* priorX, 
     std::memcpy(host.data() + n, priorZ, n * sizeof(float));
     std::vector<int32_t> wts(host.size());  // the sweep's weight tables (QEC_OPT_OSD_SCORE = 1)
     for (size_t i = 0; i < host.size(); ++i) wts[i] = osd_weight(host[i]);
+    std::vector<float> llr(host.size());    // the channel LLRs of the min-sum form (QEC_OPT_BP_METHOD = 1)
+    for (size_t i = 0; i < host.size(); ++i) llr[i] = minsum_llr(host[i]);
     std::vector<float> cond(4 * (size_t)n), pauli;
     if (cond4) {
         std::memcpy(cond.data(), cond4, cond.size() * sizeof(float));
@@ -803,6 +846,7 @@ static int install_priors(qec_decoder* d, const char* who, const float* priorX, 
             d->dpri.reserve(host.size());
             d->dosw.reserve(wts.size());
             d->dcond.reserve(cond.size());
+            d->dmllr.reserve(llr.size());
             if (pauli3) d->dpth.reserve(thr.size());
         } catch (const std::exception& ex) {
             return fail(QEC_ERR_NOMEM, std::string(who) + ": " + ex.what());
@@ -810,11 +854,13 @@ static int install_priors(qec_decoder* d, const char* who, const float* priorX, 
         QEC_HIP_CHECK(hipMemcpy(d->dpri.data(), host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
         QEC_HIP_CHECK(hipMemcpy(d->dosw.data(), wts.data(), wts.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         QEC_HIP_CHECK(hipMemcpy(d->dcond.data(), cond.data(), cond.size() * sizeof(float), hipMemcpyHostToDevice));
+        QEC_HIP_CHECK(hipMemcpy(d->dmllr.data(), llr.data(), llr.size() * sizeof(float), hipMemcpyHostToDevice));
         if (pauli3) QEC_HIP_CHECK(hipMemcpy(d->dpth.data(), thr.data(), thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
     d->priors.swap(host);
     d->osw.swap(wts);
     d->cond.swap(cond);
+    d->mllr.swap(llr);
     d->pauli.swap(pauli);
     d->has_channel = pauli3 != nullptr;
     d->has_priors = true;
@@ -917,6 +963,24 @@ int qec_decoder_get_priors(const qec_decoder* d, float* priorX, float* priorZ)
     return 1;
 }
 
+int qec_minsum_llr(float prior, float* llr)
+{
+    if (!llr) return fail(QEC_ERR_ARG, "qec_minsum_llr: bad argument");
+    *llr = minsum_llr(prior);
+    return QEC_OK;
+}
+
+int qec_decoder_get_minsum_llr(const qec_decoder* d, float* llrX, float* llrZ)
+{
+    if (!d) return fail(QEC_ERR_ARG, "qec_decoder_get_minsum_llr: null decoder");
+    if (!d->has_priors)
+        return fail(QEC_ERR_ARG, "qec_decoder_get_minsum_llr: the decoder has no priors (qec_decoder_set_priors)");
+    const int n = d->code->n;
+    if (llrX) std::memcpy(llrX, d->mllr.data(), n * sizeof(float));
+    if (llrZ) std::memcpy(llrZ, d->mllr.data() + n, n * sizeof(float));
+    return QEC_OK;
+}
+
 int qec_decoder_get_osd_weights(const qec_decoder* d, int32_t* wX, int32_t* wZ)
 {
     if (!d) return fail(QEC_ERR_ARG, "qec_decoder_get_osd_weights: null decoder");
@@ -953,6 +1017,8 @@ int qec_decoder_get_option(const qec_decoder* d, int option, int* value)
     case QEC_OPT_OSD_SCORE: *value = d->osd_score; return QEC_OK;
     case QEC_OPT_CORRELATED: *value = d->correlated; return QEC_OK;
     case QEC_OPT_BP_SCHEDULE: *value = d->bp_schedule; return QEC_OK;
+    case QEC_OPT_BP_METHOD: *value = d->bp_method; return QEC_OK;
+    case QEC_OPT_MINSUM_SCALE: *value = d->minsum_scale; return QEC_OK;
     case QEC_OPT_OSD_CS_SECTORS: {
         unsigned long long t = d->osd_cs_sectors;
         for (const qec_decoder* p : d->parts) t += p->osd_cs_sectors;
@@ -1039,6 +1105,14 @@ int dispatch_decode(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, long l
         // QEC_OPT_BP_SCHEDULE, read at the call too: the SERIAL kernels (never together with corr: set_option refuses)
         sd.serial = d->bp_schedule;
         if (sd.serial) d->last_path |= QEC_PATH_SERIAL;
+        // QEC_OPT_BP_METHOD and QEC_OPT_MINSUM_SCALE, read at the call: the MINSUM kernels under the channel LLR of p',
+        // formed here on the host, or under the handle's LLR tables (never with corr or serial: set_option refuses)
+        sd.minsum = d->minsum();
+        if (sd.minsum) {
+            sd.lam = minsum_llr(2.0f / 3.0f * p);
+            sd.llr = d->llr_dev();
+            d->last_path |= QEC_PATH_MINSUM;
+        }
         rc = launch_decode_sparse(d->sparse, sd, st);
         if (!rc && rec != nullptr) rc = launch_pack_decisions(eX, eZ, flags, B, c.n, rec, st);
         if (rc) return rc;
@@ -1180,7 +1254,8 @@ int osd_compact_dev(qec_decoder* d, long long cnt, float p, bool count, hipStrea
     d->last_path = path;
     if (rc) return rc;
     return launch_osd(d->odev, d->osd_sweep, d->osd_order, d->osX.data(), d->osZ.data(), cnt, d->oq.data(), d->oeX.data(),
-                      d->oeZ.data(), d->ofl.data(), count ? d->ocnt.data() + 1 : nullptr, d->ocnt.data() + 2, d->osw_dev(), st);
+                      d->oeZ.data(), d->ofl.data(), count ? d->ocnt.data() + 1 : nullptr, d->ocnt.data() + 2, d->osw_dev(), st,
+                      d->bp_method == 1);
 }
 
 // The whole stage on a decoded host batch of one single-device handle (byte form, or records): find
@@ -1214,11 +1289,12 @@ int osd_repair_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t
             cFs.resize(cnt);
             const int rc = cpu_decode_batch(d->cpu, cX.data(), cZ.data(), (long long)cnt, p, d->osd_iters, QEC_STOP_FIXED,
                                             cEX.data(), cEZ.data(), cFs.data(), nullptr, nullptr, cq.data(), 0,
-                                            false, d->prior_host(), d->correlated, d->cond_host(), d->bp_schedule);
+                                            false, d->prior_host(), d->correlated, d->cond_host(), d->bp_schedule,
+                                            d->minsum(), d->llr_host());
             if (rc) return rc;
             long long swept = 0;
             osd_host_batch(*d->oplan, cX.data(), cZ.data(), (long long)cnt, cq.data(), cEX.data(), cEZ.data(), cF.data(), 0,
-                           d->osd_order, &swept, d->osw_host());
+                           d->osd_order, &swept, d->osw_host(), d->bp_method == 1);
             d->osd_cs_sectors += (unsigned long long)swept;
         } else {
             hipStream_t st = d->stream;
@@ -1333,8 +1409,9 @@ int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
     if (d->cpu) {
         const int rc = cpu_decode_batch(d->cpu, sX, sZ, (long long)B, p, maxIter, stop, eX, eZ, flags, rec, iters, q, 0,
                                         d->hard_paths && d->near_hard, d->prior_host(), d->correlated, d->cond_host(),
-                                        d->bp_schedule);
-        d->last_path = (d->correlated ? QEC_PATH_CORRELATED : 0) | (d->bp_schedule ? QEC_PATH_SERIAL : 0);
+                                        d->bp_schedule, d->minsum(), d->llr_host());
+        d->last_path = (d->correlated ? QEC_PATH_CORRELATED : 0) | (d->bp_schedule ? QEC_PATH_SERIAL : 0) |
+                       (d->bp_method ? QEC_PATH_MINSUM : 0);
         return rc || !d->osd ? rc : osd_repair_host(d, sX, sZ, B, p, eX, eZ, flags, rec);
     }
     QEC_DEVICE_SCOPE(d->device);
@@ -1687,7 +1764,8 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
         fl.resize(cnt);
         const int rc = cpu_decode_batch(d->cpu, sx.data(), sz.data(), cnt, p, maxIter, QEC_STOP_REF, ex.data(), ez.data(),
                                         fl.data(), nullptr, nullptr, nullptr, 0, d->hard_paths && d->near_hard,
-                                        d->prior_host(), d->correlated, d->cond_host(), d->bp_schedule);
+                                        d->prior_host(), d->correlated, d->cond_host(), d->bp_schedule, d->minsum(),
+                                        d->llr_host());
         if (rc) return rc;
         if (d->osd) {  // the counters describe the repaired estimates
             d->osd_sectors = 0;
@@ -1722,7 +1800,7 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
     d->osd_sectors = repaired;
     d->osd_cs_sectors = swept;
     d->last_path = (d->osd ? QEC_PATH_OSD : 0) | (d->correlated ? QEC_PATH_CORRELATED : 0) |
-                   (d->bp_schedule ? QEC_PATH_SERIAL : 0);
+                   (d->bp_schedule ? QEC_PATH_SERIAL : 0) | (d->bp_method ? QEC_PATH_MINSUM : 0);
     std::memset(out, 0, sizeof *out);
     out->randSeed = seed;
     out->numErrorsTested = (uint32_t)tested;
@@ -2017,7 +2095,7 @@ int qec_osd_dev(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
     QEC_DEVICE_SCOPE(d->device);
     // the kernel reads only the handle's tables: no workspace, no allocation, nothing to order
     return launch_osd(d->odev, d->osd_sweep, d->osd_order, sX, sZ, (long long)B, q, eX, eZ, flags, nullptr, nullptr,
-                      d->osw_dev(), static_cast<hipStream_t>(stream));
+                      d->osw_dev(), static_cast<hipStream_t>(stream), d->bp_method == 1);
 }
 
 int qec_osd(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, const float* q, uint8_t* eX, uint8_t* eZ,
@@ -2030,7 +2108,7 @@ int qec_osd(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, cons
     if (d->cpu) {
         long long swept = 0;
         d->osd_sectors = (unsigned long long)osd_host_batch(*d->oplan, sX, sZ, (long long)B, q, eX, eZ, flags, 0,
-                                                            d->osd_order, &swept, d->osw_host());
+                                                            d->osd_order, &swept, d->osw_host(), d->bp_method == 1);
         d->osd_cs_sectors = (unsigned long long)swept;
         return QEC_OK;
     }
@@ -2053,7 +2131,8 @@ int qec_osd(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, cons
         QEC_HIP_CHECK(hipMemcpyAsync(dq.data(), q, B * qn * sizeof(float), hipMemcpyHostToDevice, st));
         QEC_HIP_CHECK(hipMemsetAsync(w->ocnt.data() + 2, 0, sizeof(uint32_t), st));
         const int rc = launch_osd(w->odev, w->osd_sweep, w->osd_order, dsX.data(), dsZ.data(), (long long)B, dq.data(),
-                                  deX.data(), deZ.data(), dfl.data(), nullptr, w->ocnt.data() + 2, w->osw_dev(), st);
+                                  deX.data(), deZ.data(), dfl.data(), nullptr, w->ocnt.data() + 2, w->osw_dev(), st,
+                                  w->bp_method == 1);
         if (rc) return rc;
         QEC_HIP_CHECK(hipMemcpyAsync(&swept, w->ocnt.data() + 2, sizeof swept, hipMemcpyDeviceToHost, st));
         QEC_HIP_CHECK(hipMemcpyAsync(eX, deX.data(), B * c.n, hipMemcpyDeviceToHost, st));

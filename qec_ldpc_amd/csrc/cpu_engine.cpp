@@ -13,6 +13,7 @@
 // Samples are independent: a batch is split over std::threads, one workspace each (the
 // reference's one decoder per OpenMP thread, DecoderCPU.h:419-438).
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -89,6 +90,7 @@ void build_sector_general(const std::vector<uint8_t>& pcm, int m, int n, int D, 
 }
 
 inline bool outside(float x) { return !(x > 0.01f && x < 0.99f); }  // CheckConvergence, DecoderCPU.h:231-246
+inline bool minsum_inside(float x) { return std::fabs(x) < kMinSumInside; }  // the same band as an LLR: |M| < ln 99
 
 struct Work {
     std::vector<float> q, r, post;
@@ -391,7 +393,113 @@ int decode_sector_serial(const CpuSector& S, int n, bool general, const uint8_t*
     return it;
 }
 
+// One sector under scaled min-sum in the LLR domain (QEC_OPT_BP_METHOD = 1; DESIGN.md section 2, "The min-sum form"),
+// regular and general codes, flooding.  q[e] is the variable->check message of edge e as an LLR (> 0: the bit is 0),
+// lam[v] = the channel LLR of variable v (llr, or the scalar lam0).  The loop holds fp32 adds, one fp32 multiply by
+// alpha = scale / 256 and integer operations on bit patterns only; every value is finite.
+int decode_sector_minsum(const CpuSector& S, int n, bool general, const uint8_t* syn, float lam0, const float* llr,
+                         int scale, int N, int stop, Work& w, bool& conv_out, bool& syn_ok, float* q_out)
+{
+    const int m = S.m, D = S.dc, dvs = S.dv;
+    const size_t E = (size_t)m * D;
+    float* q = w.q.data();
+    float* r = w.r.data();
+    uint8_t* e = w.e.data();
+    const float alpha = (float)scale / 256.0f;
+    auto cdeg = [&](int c) { return general ? (int)S.chk_deg[c] : D; };
+    auto vdeg = [&](int v) { return general ? (int)S.var_deg[v] : dvs; };
+    auto lam = [&](int v) { return llr ? llr[v] : lam0; };
+    for (int c = 0; c < m; ++c)
+        for (int k = 0; k < D; ++k) q[(size_t)c * D + k] = k < cdeg(c) ? lam(S.chk_var[(size_t)c * D + k]) : 0.0f;
+    for (int v = 0; v < n; ++v) e[v] = vdeg(v) > 0 && lam(v) < 0.0f;  // N = 0
+    auto syndrome_ok = [&]() {
+        for (int c = 0; c < m; ++c) {
+            uint32_t x = 0;
+            for (int k = 0; k < cdeg(c); ++k) x ^= e[S.chk_var[(size_t)c * D + k]];
+            if ((x & 1u) != syn[c]) return false;
+        }
+        return true;
+    };
+    auto all_outside = [&]() {
+        for (int c = 0; c < m; ++c)
+            for (int k = 0; k < cdeg(c); ++k)
+                if (minsum_inside(q[(size_t)c * D + k])) return false;
+        return true;
+    };
+    bool conv = false;
+    int it = 0;
+    for (int iter = 0; iter < N; ++iter) {
+        if (stop == QEC_STOP_REF && conv) break;
+        ++it;
+        // check update: first minimum, second minimum and argmin of the magnitudes' patterns under the cap, and the
+        // XOR of the sign bits, in one pass
+        for (int c = 0; c < m; ++c) {
+            const float* qc = q + (size_t)c * D;
+            float* rc = r + (size_t)c * D;
+            const int dc = cdeg(c);
+            uint32_t min1 = kMinSumCap, min2 = kMinSumCap, par = syn[c] != 0;
+            int arg = -1;
+            for (int k = 0; k < dc; ++k) {
+                uint32_t b;
+                std::memcpy(&b, qc + k, sizeof b);
+                const uint32_t a = b & 0x7FFFFFFFu;
+                par ^= b >> 31;
+                if (a < min1) { min2 = min1; min1 = a; arg = k; }
+                else if (a < min2) min2 = a;
+            }
+            for (int i = 0; i < dc; ++i) {
+                uint32_t b, o;
+                std::memcpy(&b, qc + i, sizeof b);
+                const uint32_t mag = i == arg ? min2 : min1;
+                float f;
+                std::memcpy(&f, &mag, sizeof f);
+                f = alpha * f;
+                std::memcpy(&o, &f, sizeof o);
+                o |= (par ^ (b >> 31)) << 31;
+                std::memcpy(rc + i, &o, sizeof o);
+            }
+        }
+        // variable update: left folds from the channel LLR in ascending check order; the last iteration of the cap
+        // writes the posterior to every slot
+        const bool last = iter == N - 1;
+        for (int v = 0; v < n; ++v) {
+            const int32_t* ve = S.var_edge.data() + (size_t)v * dvs;
+            const int dv = vdeg(v);
+            float post = lam(v);
+            for (int k = 0; k < dv; ++k) post = post + r[ve[k]];
+            e[v] = dv > 0 && post < 0.0f;
+            for (int j = 0; j < dv; ++j) {
+                float t = post;
+                if (!last) {
+                    t = lam(v);
+                    for (int k = 0; k < dv; ++k)
+                        if (k != j) t = t + r[ve[k]];
+                }
+                q[ve[j]] = t;
+            }
+        }
+        if (stop == QEC_STOP_REF && iter % 10 == 0) conv = all_outside();
+        if (stop == QEC_STOP_SYNDROME && syndrome_ok()) break;
+    }
+    conv_out = all_outside();
+    syn_ok = syndrome_ok();
+    if (q_out) std::memcpy(q_out, q, E * sizeof(float));
+    return it;
+}
+
 }  // namespace
+
+// The channel LLR of the min-sum form (qec_minsum_llr): (float) log((1 - pi) / pi), the float prior taken exactly to
+// double and the result rounded once, clamped to [-2^30, +2^30]; pi <= 0 gives +2^30, pi >= 1 gives -2^30 and
+// pi = 1/2 gives +0.0f (never -0.0f: the kernels' padding relies on that).  Both engines decode with these values.
+float minsum_llr(float prior)
+{
+    const double pi = (double)prior;
+    if (!(pi > 0.0)) return kMinSumLlrMax;
+    if (pi >= 1.0) return -kMinSumLlrMax;
+    const float l = (float)std::log((1.0 - pi) / pi);
+    return std::min(kMinSumLlrMax, std::max(-kMinSumLlrMax, l)) + 0.0f;
+}
 
 void* cpu_plan_create(const Code& c)
 {
@@ -447,9 +555,13 @@ void correlated_priors(float p, float* c0, float* c1)
 // (with prior) = the tables c0_X [n], c1_X [n], c0_Z [n], c1_Z [n], without prior the pair correlated_priors(p).
 // The near-hard jump never fires for the second sector.
 // serial (QEC_OPT_BP_SCHEDULE): 1 = the serial schedule (decode_sector_serial; no near-hard jump, never with corr).
+// minsum (QEC_OPT_BP_METHOD = 1): 0, or the scale k of scaled min-sum (decode_sector_minsum; flooding, no near-hard
+// jump, never with corr or serial); llr (with prior) = the handle's channel LLR tables, sector X [n] then Z [n],
+// without prior the scalar minsum_llr(p').
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
-                     bool near_hard, const float* prior, int corr, const float* cond, int serial)
+                     bool near_hard, const float* prior, int corr, const float* cond, int serial, int minsum,
+                     const float* llr)
 {
     const CpuPlan& P = *static_cast<const CpuPlan*>(plan);
     const int n = P.n, nb = (n + 7) / 8;
@@ -457,10 +569,14 @@ int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long
     const size_t qper = (size_t)mX * P.sec[0].dc + (size_t)mZ * P.sec[1].dc;
     // near-hard jump (QEC_OPT_NEAR_HARD_JUMP): per-sector compare values for this p', as the kernels' launch
     uint32_t nearT[2] = {0u, 0u};
-    if (near_hard && !prior && !P.general && qf == nullptr && stop != QEC_STOP_SYNDROME)
+    if (near_hard && !minsum && !prior && !P.general && qf == nullptr && stop != QEC_STOP_SYNDROME)
         for (int sec = 0; sec < 2; ++sec) nearT[sec] = near_hard_threshold((2.0f / 3.0f) * p, P.sec[sec].dv, P.sec[sec].dc).T;
     if (corr && prior && !cond) return fail(QEC_ERR_ARG, "CPU engine: the correlated form needs its conditional tables");
     if (serial && corr) return fail(QEC_ERR_UNSUPPORTED, "CPU engine: the serial schedule has no correlated form");
+    if (minsum && (corr || serial))
+        return fail(QEC_ERR_UNSUPPORTED, "CPU engine: min-sum has no correlated form and no serial schedule");
+    if (minsum && prior && !llr) return fail(QEC_ERR_ARG, "CPU engine: min-sum under priors needs its LLR tables");
+    const float lam0 = minsum_llr(2.0f / 3.0f * p);
     float sc0 = 0.0f, sc1 = 0.0f;
     if (corr) correlated_priors(p, &sc0, &sc1);
     if (threads <= 0) threads = cpu_threads();
@@ -488,7 +604,9 @@ int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long
                     for (int v = 0; v < n; ++v) pi[v] = first[v] ? (cond ? t0[n + v] : sc1) : (cond ? t0[v] : sc0);
                     pri = pi.data();
                 }
-                const int it = serial ? decode_sector_serial(S, n, P.general, syn, p, pri, maxIter, stop, w, conv, ok, qo)
+                const int it = minsum ? decode_sector_minsum(S, n, P.general, syn, lam0, prior ? llr + (size_t)sec * n : nullptr,
+                                                             minsum, maxIter, stop, w, conv, ok, qo)
+                               : serial ? decode_sector_serial(S, n, P.general, syn, p, pri, maxIter, stop, w, conv, ok, qo)
                                : P.general ? decode_sector_general(S, n, syn, p, pri, maxIter, stop, w, conv, ok, qo)
                                            : decode_sector(S, n, syn, p, pri, maxIter, stop, w, conv, ok, qo,
                                                            second ? 0u : nearT[sec]);

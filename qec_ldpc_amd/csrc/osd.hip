@@ -78,8 +78,9 @@ __host__ __device__ inline uint32_t osd_lds_words(int mmax, int n, int Ws, int o
 // instruction what it was before the sweep existed: a shared body inlined into two kernels compiled
 // to a slower elimination loop).  WEIGHTED (with CS): the sweep scores a candidate by the sum of
 // wt[v] over its flips (section 1.4; wt = the two sectors' tables, [2][n]) instead of their number;
-// the other two instantiations never read wt.
-template <bool CS, bool WEIGHTED = false>
+// the other two instantiations never read wt.  LLR (QEC_OPT_BP_METHOD = 1): q holds LLRs and the keys are
+// osd_key_llr's; a template parameter, so the instantiations without it keep their instruction streams.
+template <bool CS, bool WEIGHTED = false, bool LLR = false>
 __global__ __launch_bounds__(64) void osd_kernel(OsdDev P, const uint8_t* __restrict__ sX,
                                                  const uint8_t* __restrict__ sZ, long long B,
                                                  const float* __restrict__ q, uint8_t* __restrict__ eX,
@@ -126,7 +127,8 @@ __global__ __launch_bounds__(64) void osd_kernel(OsdDev P, const uint8_t* __rest
     // keys, then each column's rank by counting: #{u : key(u) > key(v) or (key(u) = key(v) and u < v)}
     for (int v = lane; v < n; v += 64) {
         const int p = qpos[v];
-        keys[v] = p < 0 ? kOsdHalf : osd_key(__float_as_uint(qb[p]));
+        if (LLR) keys[v] = p < 0 ? kOsdLlrZero : osd_key_llr(__float_as_uint(qb[p]));
+        else keys[v] = p < 0 ? kOsdHalf : osd_key(__float_as_uint(qb[p]));
     }
     wave_sync();
     for (int v = lane; v < n; v += 64) {
@@ -538,15 +540,19 @@ void osd_dev_free(OsdDevPlan* D)
 
 int launch_osd(const OsdDevPlan* D, int sweep, int order, const uint8_t* sX, const uint8_t* sZ, long long B,
                const float* q, uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint32_t* repaired, uint32_t* swept,
-               const int32_t* w, hipStream_t st)
+               const int32_t* w, hipStream_t st, bool llr)
 {
     if (B <= 0) return QEC_OK;
     if (B >= (1LL << 30)) return fail(QEC_ERR_ARG, "OSD: batch too large");
     OsdDev P = D->d;
     P.sweep = sweep;
     if (order <= 0) {
-        hipLaunchKernelGGL(osd_kernel<false>, dim3((unsigned)(2 * B)), dim3(64), D->lds_bytes, st, P, sX, sZ, B, q, eX,
-                           eZ, flags, repaired, OsdCs{}, nullptr, nullptr);
+        if (llr)
+            hipLaunchKernelGGL((osd_kernel<false, false, true>), dim3((unsigned)(2 * B)), dim3(64), D->lds_bytes, st, P, sX,
+                               sZ, B, q, eX, eZ, flags, repaired, OsdCs{}, nullptr, nullptr);
+        else
+            hipLaunchKernelGGL(osd_kernel<false>, dim3((unsigned)(2 * B)), dim3(64), D->lds_bytes, st, P, sX, sZ, B, q, eX,
+                               eZ, flags, repaired, OsdCs{}, nullptr, nullptr);
         return launch_check("osd0");
     }
     // the sweep's column vectors behind the elimination's image (QEC_OPT_OSD_ORDER is refused where
@@ -557,12 +563,20 @@ int launch_osd(const OsdDevPlan* D, int sweep, int order, const uint8_t* sX, con
                                            : "OSD: the sweep does not fit in LDS");
     const OsdCs C{order, osd_rws(D->mmax)};
     if (w) {  // QEC_OPT_OSD_SCORE = 1 with priors set: the weight tables [2][n]
-        hipLaunchKernelGGL((osd_kernel<true, true>), dim3((unsigned)(2 * B)), dim3(64), lds, st, P, sX, sZ, B, q, eX, eZ,
-                           flags, repaired, C, swept, w);
+        if (llr)
+            hipLaunchKernelGGL((osd_kernel<true, true, true>), dim3((unsigned)(2 * B)), dim3(64), lds, st, P, sX, sZ, B, q,
+                               eX, eZ, flags, repaired, C, swept, w);
+        else
+            hipLaunchKernelGGL((osd_kernel<true, true>), dim3((unsigned)(2 * B)), dim3(64), lds, st, P, sX, sZ, B, q, eX, eZ,
+                               flags, repaired, C, swept, w);
         return launch_check("osd_cs_weighted");
     }
-    hipLaunchKernelGGL(osd_kernel<true>, dim3((unsigned)(2 * B)), dim3(64), lds, st, P, sX, sZ, B, q, eX, eZ, flags,
-                       repaired, C, swept, nullptr);
+    if (llr)
+        hipLaunchKernelGGL((osd_kernel<true, false, true>), dim3((unsigned)(2 * B)), dim3(64), lds, st, P, sX, sZ, B, q, eX,
+                           eZ, flags, repaired, C, swept, nullptr);
+    else
+        hipLaunchKernelGGL(osd_kernel<true>, dim3((unsigned)(2 * B)), dim3(64), lds, st, P, sX, sZ, B, q, eX, eZ, flags,
+                           repaired, C, swept, nullptr);
     return launch_check("osd_cs");
 }
 

@@ -66,7 +66,7 @@ int32_t osd_weight(float prior)
 }
 
 bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8_t* e, int order_cs, bool* swept,
-                     const int32_t* wt_tab)
+                     const int32_t* wt_tab, bool llr)
 {
     if (swept) *swept = false;
     const int m = S.m, n = S.n, W = S.W;
@@ -76,9 +76,9 @@ bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8
     std::vector<uint32_t> key(n);
     std::vector<int> order(n);
     for (int v = 0; v < n; ++v) {
-        uint32_t bits = kOsdHalf;
+        uint32_t bits = llr ? 0u : kOsdHalf;
         if (S.qpos[v] >= 0) std::memcpy(&bits, q + S.qpos[v], sizeof bits);
-        key[v] = osd_key(bits);
+        key[v] = llr ? osd_key_llr(bits) : osd_key(bits);
         order[v] = v;
     }
     std::sort(order.begin(), order.end(), [&](int a, int b) { return key[a] != key[b] ? key[a] > key[b] : a < b; });
@@ -160,7 +160,7 @@ bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8
 
 long long osd_host_batch(const OsdPlan& P, const uint8_t* sX, const uint8_t* sZ, long long B, const float* q,
                          uint8_t* eX, uint8_t* eZ, uint8_t* flags, int threads, int order, long long* swept,
-                         const int32_t* w)
+                         const int32_t* w, bool llr)
 {
     if (swept) *swept = 0;
     if (B <= 0) return 0;
@@ -179,7 +179,7 @@ long long osd_host_batch(const OsdPlan& P, const uint8_t* sX, const uint8_t* sZ,
                 bool sw = false;
                 if (osd_host_sector(S, q + (size_t)b * P.qn, (sec ? sZ : sX) + (size_t)b * S.m,
                                     (sec ? eZ : eX) + (size_t)b * S.n, order, &sw,
-                                    w ? w + (size_t)sec * S.n : nullptr)) {
+                                    w ? w + (size_t)sec * S.n : nullptr, llr)) {
                     flags[b] &= (uint8_t)~fbit;
                     ++fixed[t];
                     cs[t] += sw;

@@ -113,6 +113,14 @@ struct McArgsHost {
     long long B = 0;
 };
 
+// Scaled min-sum in the LLR domain (QEC_OPT_BP_METHOD = 1; DESIGN.md section 2, "The min-sum form"), both engines
+constexpr uint32_t kMinSumCap = 0x49800000u;        // K: the pattern of 2^20, the cap of a check's magnitudes
+constexpr float kMinSumLlrMax = 1073741824.0f;      // Lambda = 2^30: the clamp of a channel LLR
+constexpr float kMinSumInside = 4.5951198f;         // ln 99: a message M is inside iff |M| < this
+constexpr int kMinSumDefaultScale = 160;            // QEC_OPT_MINSUM_SCALE: alpha = k / 256
+// The channel LLR of a prior (qec_minsum_llr; cpu_engine.cpp): one host function for both engines
+float minsum_llr(float prior);
+
 // One decode launch of the sparse-graph engine (bp_sparse.hip, launch_decode_sparse); every pointer is a device pointer.
 struct SparseDecode {
     // the decode buffers and the arguments of Decode
@@ -133,6 +141,11 @@ struct SparseDecode {
     const float* cond = nullptr;    // CORR with prior set: the 4n conditional priors
     float c0 = 0.0f, c1 = 0.0f;     // CORR without prior: the scalar pair (correlated_priors)
     int serial = 0;                 // QEC_OPT_BP_SCHEDULE: 1 for the SERIAL kernels (scalar p' or prior; never with corr)
+    // QEC_OPT_BP_METHOD = 1: 0, or the scale k (alpha = k / 256) for the MINSUM kernels (never with corr or serial);
+    // they decode under lam = minsum_llr(p') or, with prior set, under llr = the 2n channel LLRs
+    int minsum = 0;
+    float lam = 0.0f;
+    const float* llr = nullptr;
 };
 
 }  // namespace qec

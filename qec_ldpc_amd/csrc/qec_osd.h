@@ -37,6 +37,19 @@ inline uint32_t osd_key(uint32_t bits)
     return a > 0x7F800000u ? kOsdHalf : a;
 }
 
+// Sort key of a soft value that is an LLR (QEC_OPT_BP_METHOD = 1: q_final holds LLRs, > 0 = the bit is 0): the
+// column order runs by LLR ascending, so the key is the complement of the usual order-preserving map of a float's
+// pattern onto unsigned integers.  -0.0f sorts directly before +0.0f; every LLR is finite.  The key of a variable in
+// no check is that of +0.0f.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint32_t osd_key_llr(uint32_t bits)
+{
+    return ~(bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u));
+}
+constexpr uint32_t kOsdLlrZero = 0x7FFFFFFFu;  // osd_key_llr of +0.0f
+
 void osd_plan_build(const Code& c, OsdPlan& out);
 
 constexpr int kOsdMaxOrder = 64;  // QEC_OPT_OSD_ORDER: lambda of the combination sweep, 0 .. 64
@@ -52,14 +65,15 @@ int32_t osd_weight(float prior);
 // whether it was.  order = lambda of section 1.3 (0: the OSD-0 estimate); *swept (nullable) tells
 // whether the lightest candidate was another than the OSD-0 estimate (index > 0).  w (nullable): the
 // sector's n weights of section 1.4; the candidate of least score wins instead of the lightest.
+// llr: q holds LLRs (osd_key_llr) instead of probabilities (osd_key); everything behind the key is the same.
 bool osd_host_sector(const OsdSector& S, const float* q, const uint8_t* s, uint8_t* e, int order = 0,
-                     bool* swept = nullptr, const int32_t* w = nullptr);
+                     bool* swept = nullptr, const int32_t* w = nullptr, bool llr = false);
 
 // Steps 2-7 on a decoded host batch, in place; returns the number of sectors repaired, and in
 // *swept (nullable) how many of them took a candidate of index > 0.  w (nullable): the weight tables
 // of section 1.4, sector X [n] then sector Z [n].
 long long osd_host_batch(const OsdPlan& P, const uint8_t* sX, const uint8_t* sZ, long long B, const float* q,
                          uint8_t* eX, uint8_t* eZ, uint8_t* flags, int threads, int order = 0,
-                         long long* swept = nullptr, const int32_t* w = nullptr);
+                         long long* swept = nullptr, const int32_t* w = nullptr, bool llr = false);
 
 }  // namespace qec

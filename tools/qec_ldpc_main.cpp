@@ -39,6 +39,10 @@
 //                      on the X estimate (xz), or Z first (zx).  Sparse-graph and CPU engines
 //   --bp-schedule flooding|serial   the order of BP's updates (QEC_OPT_BP_SCHEDULE): flooding (default), or the serial
 //                      (layered, check-sequential) schedule.  Sparse-graph and CPU engines; not with --correlated
+//   --bp-method product|minsum   BP's message rule (QEC_OPT_BP_METHOD): the product rule (default), or scaled min-sum
+//                      in the LLR domain.  Sparse-graph and CPU engines; not with --correlated or --bp-schedule serial
+//   --minsum-scale K   min-sum's factor alpha = K / 256 (QEC_OPT_MINSUM_SCALE, 1 .. 256, default 160); needs
+//                      --bp-method minsum
 //   --pauli FILE       per-qubit Pauli channel (qec_decoder_set_pauli_channel): FILE holds three lines of n decimal
 //                      floats, pX, pY and pZ.  BP decodes under its marginals (and --correlated under its conditional
 //                      tables), the init file's p is not used, and --rng philox draws its errors from the channel.
@@ -91,7 +95,8 @@ int usage(const std::string& why)
               << "usage: qec_ldpc [--engine gpu|sparse|cpu] [--gpus N | --devices i,j,...] [--rng msvc|philox]"
                  " [--stop ref|fixed|syndrome] [--batch B] [--seed S] [--logical file|reference|degenerate]"
                  " [--osd 0 [--osd-order L] [--osd-iterations K] [--osd-score hamming|priors]] [--priors FILE]"
-                 " [--correlated xz|zx] [--bp-schedule flooding|serial] [--pauli FILE] initFile"
+                 " [--correlated xz|zx] [--bp-schedule flooding|serial] [--bp-method product|minsum [--minsum-scale K]]"
+                 " [--pauli FILE] initFile"
               << std::endl;
     return 2;
 }
@@ -141,7 +146,8 @@ int main(int argc, char** argv)
     log << std::endl << std::ctime(&ts);
     std::vector<int> devices{0};
     std::string engine = "gpu", rng = "msvc", stopName = "ref", logical = "file", priorsFile, pauliFile;
-    int correlated = 0, bpSchedule = 0;
+    int correlated = 0, bpSchedule = 0, bpMethod = 0, minsumScale = 160;
+    bool minsumScaleFlag = false;
     bool deviceFlag = false, stopFlag = false, batchFlag = false, seedFlag = false, osd = false, osdIterFlag = false;
     bool osdOrderFlag = false, osdScoreFlag = false;
     int osdScore = 0;
@@ -208,6 +214,13 @@ int main(int argc, char** argv)
             } else if (flag == "--bp-schedule") {
                 if (val != "flooding" && val != "serial") return usage("--bp-schedule: flooding or serial");
                 bpSchedule = val == "serial" ? 1 : 0;
+            } else if (flag == "--bp-method") {
+                if (val != "product" && val != "minsum") return usage("--bp-method: product or minsum");
+                bpMethod = val == "minsum" ? 1 : 0;
+            } else if (flag == "--minsum-scale") {
+                minsumScale = std::stoi(val);
+                if (minsumScale < 1 || minsumScale > 256) return usage("--minsum-scale: 1 .. 256");
+                minsumScaleFlag = true;
             } else if (flag == "--seed") {
                 seed = std::stoull(val, nullptr, 0);
                 seedFlag = true;
@@ -226,6 +239,9 @@ int main(int argc, char** argv)
     if (osdOrderFlag && !osd) return usage("--osd-order needs --osd 0");
     if (osdScoreFlag && !osd) return usage("--osd-score needs --osd 0");
     if (bpSchedule && correlated) return usage("--bp-schedule serial and --correlated exclude each other");
+    if (minsumScaleFlag && !bpMethod) return usage("--minsum-scale needs --bp-method minsum");
+    if (bpMethod && correlated) return usage("--bp-method minsum and --correlated exclude each other");
+    if (bpMethod && bpSchedule) return usage("--bp-method minsum and --bp-schedule serial exclude each other");
     if (!pauliFile.empty() && !priorsFile.empty()) return usage("--pauli and --priors exclude each other");
     if (osdScore == 1 && priorsFile.empty()) return usage("--osd-score priors needs --priors FILE");
     if (argc - a != 1 || devices.empty()) {
@@ -272,6 +288,7 @@ int main(int argc, char** argv)
             if (!pauliFile.empty()) decoder.SetPauliChannel(pauli[0], pauli[1], pauli[2]);
             if (correlated) decoder.SetCorrelated(correlated);
             if (bpSchedule) decoder.SetBpSchedule(bpSchedule);
+            if (bpMethod) decoder.SetBpMethod(bpMethod, minsumScale);
             std::cout << "Engine: " << decoder.Describe() << std::endl;
             const int stop = stopName == "ref" ? QEC_STOP_REF : stopName == "fixed" ? QEC_STOP_FIXED : QEC_STOP_SYNDROME;
             std::stringstream fileName;
@@ -299,6 +316,7 @@ int main(int argc, char** argv)
             if (!pauliFile.empty()) c->SetPauliChannel(pauli[0], pauli[1], pauli[2]);
             if (correlated) c->SetCorrelated(correlated);
             if (bpSchedule) c->SetBpSchedule(bpSchedule);
+            if (bpMethod) c->SetBpMethod(bpMethod, minsumScale);
             std::cout << "Engine: CPU (" << std::thread::hardware_concurrency() << " threads)" << std::endl;
         } else {
             DecoderGPU* g = engine == "sparse" ? new DecoderGPU(code, 0, QEC_ENGINE_SPARSE) : new DecoderGPU(code, devices);
@@ -309,6 +327,7 @@ int main(int argc, char** argv)
             if (!pauliFile.empty()) g->SetPauliChannel(pauli[0], pauli[1], pauli[2]);
             if (correlated) g->SetCorrelated(correlated);
             if (bpSchedule) g->SetBpSchedule(bpSchedule);
+            if (bpMethod) g->SetBpMethod(bpMethod, minsumScale);
             std::cout << "Engine: " << g->Describe() << std::endl;
         }
         for (; w <= W; ++w) {
