@@ -379,7 +379,9 @@ def test_irregular_matrix_in_a_six_number_file_is_still_refused(tmp_path):
 # ---- OSD on the CPU engine --------------------------------------------------------------------------------
 class GeneralOsdYardstick(YardstickCS):
     """DESIGN.md sections 1.2 / 1.3 in numpy (test_osd_host / test_osd_cs_host) for the general layout:
-    slot stride D, and a variable in no check of the sector takes the key of 0.5."""
+    slot stride D, and a variable in no check of the sector takes the key of `absent` (0.5)."""
+
+    absent = F32(0.5)
 
     def __init__(self, HX, HZ):
         self.n = HX.shape[1]
@@ -390,7 +392,7 @@ class GeneralOsdYardstick(YardstickCS):
         self.pos = []
         base = 0
         for H in self.H:
-            pos = np.full(self.n, self.qn, dtype=np.int64)  # qn: the appended 0.5
+            pos = np.full(self.n, self.qn, dtype=np.int64)  # qn: the appended value
             for v in range(self.n):
                 cs = np.nonzero(H[:, v])[0]
                 if len(cs):
@@ -399,7 +401,7 @@ class GeneralOsdYardstick(YardstickCS):
             base += H.shape[0] * self.L
 
     def reduce(self, sec, s, qrow):
-        return super().reduce(sec, s, np.append(qrow, F32(0.5)))
+        return super().reduce(sec, s, np.append(qrow, self.absent))
 
 
 OSD_P, OSD_N, OSD_B = 0.08, 20, 256

@@ -7,7 +7,8 @@ import torch
 
 import qec_ldpc_amd as q
 from qec_ldpc_amd.gather import pack_records
-from test_osd_host import MAIN, check_main_conditions, env, forced_batch, main_case  # noqa: F401 (env: fixture)
+from test_osd_host import (FAIL, MAIN, check_main_conditions, env, forced_batch, inconsistent_syndrome,  # noqa: F401 (env: fixture)
+                           main_case)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
@@ -211,3 +212,56 @@ def test_osd_dev_in_a_graph(env):
     torch.cuda.synchronize()
     assert torch.equal(cX, oX) and torch.equal(cZ, oZ) and torch.equal(cF, oF)
     assert np.array_equal(cX.cpu().numpy(), wX) and np.array_equal(cF.cpu().numpy(), wf)
+
+
+def osd_dev_on(dec, sX, sZ, qf, eX, eZ, flags):
+    """osd_dev on guarded copies -> (eX, eZ, flags) as numpy, the guards checked."""
+    B = len(flags)
+    t = [torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for a in (sX, sZ, qf)]
+    gX, vX = guarded(eX)
+    gZ, vZ = guarded(eZ)
+    gF, vF = guarded(flags, offset=5)
+    dec.osd_dev(*t, vX, vZ, vF)
+    torch.cuda.synchronize()
+    assert guards_intact(gX, B) and guards_intact(gZ, B) and guards_intact(gF, B, offset=5)
+    return vX.cpu().numpy(), vZ.cpu().numpy(), vF.cpu().numpy()
+
+
+@pytest.mark.parametrize("key", ["P7", "G13", "P61"])
+def test_osd_dev_leaves_an_inconsistent_syndrome_alone(env, decoders, key):
+    """The device twin of test_osd_host.test_inconsistent_syndrome_is_left_alone: the kernel returns before it
+    writes, and the other sectors of the batch are repaired."""
+    code, _, _, ys = env[key]
+    rng = np.random.default_rng(5)
+    sX, sZ, qf, eX, eZ, flags = forced_batch(code, rng, 4)
+    deficient = [sec for sec in (0, 1) if ys.rank[sec] < ys.H[sec].shape[0]]
+    assert deficient, "every shipped matrix is rank deficient"
+    for sec in deficient:
+        s = (sX, sZ)[sec]
+        s[1] = inconsistent_syndrome(ys, sec, s[1], rng)
+    wX, wZ, wf, cnt = ys.repair(sX, sZ, qf, eX, eZ, flags)
+    assert cnt == 8 - len(deficient)
+    dec = decoders(key)
+    gX, gZ, gf = osd_dev_on(dec, sX, sZ, qf, eX, eZ, flags)
+    assert np.array_equal(gX, wX) and np.array_equal(gZ, wZ) and np.array_equal(gf, wf)
+    for sec in deficient:  # estimate and flag as BP left them
+        assert gf[1] & FAIL[sec]
+        assert np.array_equal((gX, gZ)[sec][1], (eX, eZ)[sec][1])
+    hX, hZ, hf = dec.osd(sX, sZ, qf, eX, eZ, flags)
+    assert np.array_equal(hX, wX) and np.array_equal(hZ, wZ) and np.array_equal(hf, wf)
+    assert dec.get_option("osd_sectors") == cnt
+
+
+@pytest.mark.parametrize("key", ["P7", "G13", "P61"])
+def test_osd_dev_leaves_sectors_without_their_fail_bit_alone(env, decoders, key):
+    """The device twin of the partial-flags half of test_osd_host.test_qec_osd_matches_numpy_on_random_soft_input."""
+    (sX, sZ, qf, eX, eZ, flags), (wX, wZ, wf, _) = forced_case(env, key)
+    part = flags.copy()
+    part[::2] &= ~1 & 0xFF
+    part[1::3] &= ~2 & 0xFF
+    gX, gZ, gf = osd_dev_on(decoders(key), sX, sZ, qf, eX, eZ, part)
+    keepX, keepZ = (part & 1) == 0, (part & 2) == 0
+    assert keepX.any() and keepZ.any() and (~keepX).any() and (~keepZ).any()
+    assert np.array_equal(gX[keepX], eX[keepX]) and np.array_equal(gZ[keepZ], eZ[keepZ])
+    assert np.array_equal(gX[~keepX], wX[~keepX]) and np.array_equal(gZ[~keepZ], wZ[~keepZ])
+    assert np.array_equal(gf, part & 12)

@@ -13,8 +13,8 @@ import qec_ldpc_amd as q
 from qec_ldpc_amd.gather import pack_records
 from test_gpu_general_code import count, logical_code
 from test_gpu_osd import guarded, guards_intact
-from test_osd_weighted_host import (FORCED_SMALL, FORCED_B, SAMPLED, forced, osd_options, priors_of, sampled, want,
-                                    weights_of, yardstick)
+from test_osd_weighted_host import (FORCED_SMALL, FORCED_B, SAMPLED, forced, lds_words, osd_options, priors_of, sampled,
+                                    want, weights_of, yardstick)
 from test_priors import F32, code_of, matrices, prior_vectors
 
 pytestmark = pytest.mark.gpu
@@ -227,18 +227,6 @@ def test_weighted_osd_dev_in_a_graph_follows_set_priors():
 
 
 # ---- 6. LDS refusal -----------------------------------------------------------------------------------------------------------
-def lds_words(mmax, n, order, weighted):
-    """osd_lds_words of osd.hip: the elimination's image, the sweep's column vectors, the weighted sweep's arrays."""
-    W = (n + 1 + 31) // 32
-    rws = (2 * ((mmax + 63) // 64)) | 1
-    words = mmax * (W | 1) + n + (n + 1) // 2 + (mmax + 1) // 2
-    if order > 0:
-        words += (order + 1) * rws
-        if weighted:
-            words += 12 * rws + (mmax + 1) // 2
-    return words
-
-
 def test_lds_refusal_of_the_weighted_arrays():
     """HX = HZ = [I | I] with 460 checks on 920 qubits: the sweep at lambda = 64 fits one workgroup's 64 KiB under
     the Hamming score and not with the weighted score's arrays; whichever call would make the weighted sweep run

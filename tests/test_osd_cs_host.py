@@ -23,6 +23,8 @@ FORCED_B = {"P7": 32, "G13": 32, "P61": 8}
 class YardstickCS(Yardstick):
     """The yardstick of section 1.2 with the sweep of section 1.3 behind it."""
 
+    key_fn = staticmethod(osd_keys)  # the soft value's sort key; an instance may carry another (osd_key_llr)
+
     def __init__(self, ys):
         self.__dict__.update(ys.__dict__)  # the matrices, ranks and q_final offsets, computed once
 
@@ -30,7 +32,7 @@ class YardstickCS(Yardstick):
         """Section 1.2 steps 1-5: (R with s' as column n, pivots [(row, column)], the column order), or
         None if [H | s] is inconsistent."""
         H, n = self.H[sec], self.n
-        key = osd_keys(qrow[self.pos[sec]]).astype(np.int64)
+        key = self.key_fn(qrow[self.pos[sec]]).astype(np.int64)
         order = np.lexsort((np.arange(n), -key))  # key descending, ties by v ascending
         A = np.concatenate([H, np.asarray(s, dtype=np.uint8)[:, None] & 1], axis=1).astype(np.uint8)
         used = np.zeros(H.shape[0], dtype=bool)

@@ -41,7 +41,16 @@ def priors_of(n, kind):
 # ---- the yardstick: section 1.4 in numpy -----------------------------------------------------------------
 class WeightedYardstick(GeneralOsdYardstick):
     """The sweep of test_osd_cs_host.YardstickCS with each candidate scored by the sum of w over its flips
-    (w = None: their number, the parent's rule); the first minimum wins."""
+    (w = None: their number, the parent's rule); the first minimum wins.  key_fn: the soft value's sort key
+    (osd_keys, the product rule's, unless given: osd_key_llr of test_minsum.py for min-sum); absent: the soft value
+    that a column in no check of the sector stands for (0.5f, or +0.0f under min-sum)."""
+
+    def __init__(self, HX, HZ, key_fn=None, absent=None):
+        super().__init__(HX, HZ)
+        if key_fn is not None:
+            self.key_fn = key_fn
+        if absent is not None:
+            self.absent = F32(absent)
 
     def sweep_literal(self, red, lam, w=None):
         """YardstickCS.sweep word for word but for the weights -> (estimate, index, f, candidates at the minimum)."""
@@ -224,6 +233,21 @@ def assert_repair(dec, data, lam, score, expect, what, counters=True):
         assert np.array_equal(gX, expect[0]) and np.array_equal(gZ, expect[1]) and np.array_equal(gf, expect[2]), what
         if counters:
             assert dec.get_option("osd_sectors") == expect[3] and dec.get_option("osd_cs_sectors") == expect[4], what
+
+
+def lds_words(mmax, n, order, weighted):
+    """osd_lds_words of osd.hip: the elimination's image, the sweep's column vectors, the weighted sweep's arrays."""
+    W = (n + 1 + 31) // 32
+    rws = (2 * ((mmax + 63) // 64)) | 1
+    words = mmax * (W | 1) + n + (n + 1) // 2 + (mmax + 1) // 2
+    if order > 0:
+        words += (order + 1) * rws
+        if weighted:
+            words += 12 * rws + (mmax + 1) // 2
+    return words
+
+
+LDS_LIMIT = 64 * 1024 // 4  # words of one workgroup's LDS allocation (kOsdMaxLds)
 
 
 # ---- 1. the weight table ---------------------------------------------------------------------------------------
