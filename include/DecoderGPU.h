@@ -176,6 +176,16 @@ public:
         check(qec_decoder_set_option(dec_, QEC_OPT_MINSUM_SCALE, scale));
         check(qec_decoder_set_option(dec_, QEC_OPT_BP_METHOD, method));
     }
+    // Relay-BP (qec_decoder_set_relay): `legs` legs of memory min-sum under SetBpMethod(1), gammaX / gammaZ the memory
+    // strengths [legs][n] (|gamma| <= 1), stopping at the first solution or at the lightest of the first `solutions`.
+    // The sparse-graph engine takes them; a wave-circulant decoder throws the library's message.
+    void SetRelay(const std::vector<float>& gammaX, const std::vector<float>& gammaZ, int legs, int solutions = 1)
+    {
+        if (legs < 1 || gammaX.size() != (size_t)legs * _code.n || gammaZ.size() != (size_t)legs * _code.n)
+            throw std::string("SetRelay: gammaX and gammaZ need legs * n entries each");
+        check(qec_decoder_set_relay(dec_, gammaX.data(), gammaZ.data(), legs, solutions));
+    }
+    void ClearRelay() { check(qec_decoder_set_relay(dec_, nullptr, nullptr, 0, 0)); }
     // Per-qubit Pauli channel (qec_decoder_set_pauli_channel): qubit v suffers X, Y or Z with probabilities pX[v],
     // pY[v], pZ[v] (n entries each; Y sets both bits).  Installs the marginal priors, the conditional tables of
     // SetCorrelated and the noise of the device Monte-Carlo run; a later SetPriors or ClearPriors drops it.

@@ -397,7 +397,8 @@ enum {
     QEC_PATH_OSD = 256,            /* the call ran the OSD stage (QEC_OPT_OSD) */
     QEC_PATH_CORRELATED = 512,     /* one sector decoded under priors conditioned on the other's estimate */
     QEC_PATH_SERIAL = 1024,        /* BP under the serial schedule (QEC_OPT_BP_SCHEDULE = 1) */
-    QEC_PATH_MINSUM = 2048         /* scaled min-sum BP (QEC_OPT_BP_METHOD = 1) */
+    QEC_PATH_MINSUM = 2048,        /* scaled min-sum BP (QEC_OPT_BP_METHOD = 1) */
+    QEC_PATH_RELAY = 4096          /* ... as a relay of memory min-sum legs (qec_decoder_set_relay) */
 };
 /* The near-hard jump's threshold for p' = pPrime (the float (2/3) errorProbability the decoder forms), R
  * checks per variable and L variables per check: *eps0 = the largest power of two in [2^-20, 2^-8] with
@@ -459,6 +460,35 @@ int qec_minsum_llr(float prior, float* llr);
 /* The channel LLR tables that every qec_decoder_set_priors builds (whatever QEC_OPT_BP_METHOD says): the arrays
  * filled (n floats each; a NULL array is skipped).  QEC_ERR_ARG if no priors are set. */
 int qec_decoder_get_minsum_llr(const qec_decoder* dec, float* llrX, float* llrZ);
+/* Relay-BP ("The relay form"): min-sum with one fp32 memory M_v per variable, run as a chain of
+ * `legs` legs; a message-passing-only route to the syndromes that plain BP leaves unsatisfied.  gammaX, gammaZ: HOST
+ * tables [legs][n] of memory strengths, each finite with |gamma| <= 1 (negative values are legal); solutions = S, the
+ * solutions to collect.  1 <= legs <= 1024 with legs * n <= 2^22, 1 <= S <= 64; an illegal value gives QEC_ERR_ARG and
+ * leaves the handle as it was.  (NULL, NULL, 0, 0) clears: the handle behaves as one that never had tables.
+ *   - The tables are data, like QEC_OPT_MINSUM_SCALE: they take effect in every decode while QEC_OPT_BP_METHOD = 1 and
+ *     have no effect under the product rule.  Everything not said here is the min-sum form (channel LLRs, check
+ *     update, K, alpha, the inside band, flags, layout).  X and Z relay independently.
+ *   - Leg 0 starts with M_v = lambda_v, leg l >= 1 with the posteriors of leg l - 1's last variable pass; every leg
+ *     starts with every real slot at its variable's lambda_v.  Variable update, every operation fp32 and uncontracted:
+ *     b = ((1.0f - gamma) * lambda_v + gamma * M_v) + 0.0f takes lambda_v's place in the folds, and M_v = the
+ *     posterior.  The call's stop rule and maxIter = N end a leg, counted within the leg.
+ *   - A leg whose final decisions satisfy the syndrome is a solution of weight W = sum of w_v over its set bits (an
+ *     unsigned 32-bit sum; w_v = 1, or with priors the entry of qec_decoder_get_osd_weights).  The sector ends at its
+ *     S-th solution or after its last leg and returns the solution of least W (ties: the earlier leg), or without a
+ *     solution the last leg's decisions with SYNDROME_FAIL set.  CONVERGENCE_FAIL and q_final describe the last executed
+ *     leg's final state, iters counts the iterations of all legs; N = 0 runs one leg and equals min-sum's N = 0.
+ *     With legs = 1 and every gamma = 0 every output bit equals the plain min-sum call.
+ *   - Engines: the sparse-graph engine (the RELAY kernels of bp_sparse.hip; plan, workspace, grid and describe string
+ *     unchanged) and the CPU engine.  A wave-circulant handle refuses with QEC_ERR_UNSUPPORTED and the text says to
+ *     create the decoder with QEC_ENGINE_SPARSE.  A group passes the tables to every part.
+ *   - Synchronous.  The first set allocates the device copy (at its largest legal size, so no later set moves it) and
+ *     the kernels' per-workgroup state; qec_decoder_set_option and the _dev entry points allocate nothing, and a
+ *     captured graph replayed after a later set reads the new table values (legs and S as captured).
+ *   - QEC_PATH_RELAY is set in QEC_OPT_LAST_PATH whenever the relay ran.  The OSD stage runs behind it on the sectors
+ *     it leaves failed; the stage's own soft decode ignores the tables (plain min-sum). */
+int qec_decoder_set_relay(qec_decoder* dec, const float* gammaX, const float* gammaZ, int legs, int solutions);
+/* *legs and *solutions (0 and 0 without tables; a NULL pointer is skipped) and, where given, the tables ([legs][n]). */
+int qec_decoder_get_relay(const qec_decoder* dec, float* gammaX, float* gammaZ, int* legs, int* solutions);
 /* The scalar tables of QEC_OPT_CORRELATED for depolarising noise of strength p: *c1 = P(other bit | this bit
  * set) = 0.5f and *c0 = P(other bit | this bit clear) = (p / 3.0f) / (1.0f - 2.0f / 3.0f * p), every operation
  * in fp32.  Both engines decode with exactly these values. */

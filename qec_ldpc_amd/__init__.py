@@ -38,7 +38,7 @@ BP_METHOD = {"product": 0, "minsum": 1}
 # QEC_PATH_* bits of QEC_OPT_LAST_PATH (include/qec_ldpc.h): the launch sequence of the last decode call
 PATH = {"ordered": 1, "sector_order": 2, "split_waves": 4, "sector_launches": 8, "triage": 16, "bit_rows": 32,
         "sparse": 64, "records": 128, "osd": 256, "correlated": 512, "serial": 1024,
-        "minsum": 2048}
+        "minsum": 2048, "relay": 4096}
 
 # every symbol include/qec_ldpc.h declares
 EXPORTS = (
@@ -53,6 +53,7 @@ EXPORTS = (
     "qec_decoder_set_option", "qec_decoder_get_option", "qec_near_hard_threshold",
     "qec_decoder_set_priors", "qec_decoder_get_priors", "qec_decoder_get_osd_weights", "qec_sample_independent_dev",
     "qec_correlated_priors", "qec_minsum_llr", "qec_decoder_get_minsum_llr", "qec_decoder_set_pauli_channel", "qec_decoder_get_pauli_channel",
+    "qec_decoder_set_relay", "qec_decoder_get_relay",
     "qec_decoder_get_conditional_priors", "qec_sample_pauli_dev",
     "qec_decode_batch", "qec_decode_batch_dev", "qec_decode_batch_packed", "qec_decode_batch_packed_dev",
     "qec_decode_bits_packed_dev",
@@ -159,6 +160,8 @@ def lib():
             "qec_correlated_priors": (i, [f, vp, vp]),
             "qec_minsum_llr": (i, [f, vp]),
             "qec_decoder_get_minsum_llr": (i, [vp, vp, vp]),
+            "qec_decoder_set_relay": (i, [vp, vp, vp, i, i]),
+            "qec_decoder_get_relay": (i, [vp, vp, vp, vp, vp]),
             "qec_decoder_set_pauli_channel": (i, [vp, vp, vp, vp]),
             "qec_decoder_get_pauli_channel": (i, [vp, vp, vp, vp]),
             "qec_decoder_get_conditional_priors": (i, [vp, vp, vp, vp, vp]),
@@ -223,6 +226,15 @@ def minsum_llr(prior):
     llr = ctypes.c_float(0.0)
     _check(lib().qec_minsum_llr(float(np.float32(prior)), ctypes.byref(llr)), "qec_minsum_llr")
     return np.float32(llr.value)
+
+
+def relay_gammas(n, legs, gamma0=0.125, lo=-0.24, hi=0.66, seed=0):
+    """Memory strengths for set_relay as float32 [legs, n]: row 0 is gamma0 everywhere, the other rows are
+    numpy.random.default_rng(seed).uniform(lo, hi, (legs - 1, n))."""
+    g = np.empty((int(legs), int(n)), dtype=np.float32)
+    g[0] = gamma0
+    g[1:] = np.random.default_rng(seed).uniform(lo, hi, (int(legs) - 1, int(n)))
+    return g
 
 
 def _check(rc, what):
@@ -578,6 +590,44 @@ class DecoderGPU:
         lZ = np.empty(self.code.n, dtype=np.float32)
         _check(lib().qec_decoder_get_minsum_llr(self._h, _ptr(lX), _ptr(lZ)), "qec_decoder_get_minsum_llr")
         return lX, lZ
+
+    def set_relay(self, gammaX, gammaZ, solutions=1):
+        """Relay-BP (qec_decoder_set_relay): min-sum with one memory per variable, run as a chain of legs that stops at
+        the first solution or at the lightest of the first `solutions` ones.  gammaX / gammaZ: the memory strengths,
+        |gamma| <= 1 -- arrays of shape [legs, n], an [n] array for one leg, or a scalar for one uniform leg;
+        set_relay(None, None) clears.  In effect in every decode while set_option("bp_method", 1); relay_gammas makes
+        tables.  Sparse-graph and CPU engines; a wave-circulant decoder refuses (create it with engine="sparse")."""
+        if (gammaX is None) != (gammaZ is None):
+            raise QecError("set_relay: gammaX and gammaZ must both be given, or both be None (clear)")
+        if gammaX is None:
+            _check(lib().qec_decoder_set_relay(self._h, None, None, 0, 0), "qec_decoder_set_relay")
+            return
+        arrs = []
+        for name, g in (("gammaX", gammaX), ("gammaZ", gammaZ)):
+            a = np.asarray(g, dtype=np.float32)
+            if a.ndim == 0:
+                a = np.full((1, self.code.n), a, dtype=np.float32)
+            if a.ndim == 1:
+                a = a[None, :]
+            if a.ndim != 2 or a.shape[1] != self.code.n:
+                raise QecError("set_relay: %s must be a scalar, or have shape [n] or [legs, n] with n = %d, has shape %s"
+                               % (name, self.code.n, a.shape))
+            arrs.append(np.ascontiguousarray(a))
+        if arrs[0].shape != arrs[1].shape:
+            raise QecError("set_relay: gammaX and gammaZ must have the same number of legs")
+        _check(lib().qec_decoder_set_relay(self._h, _ptr(arrs[0]), _ptr(arrs[1]), arrs[0].shape[0], int(solutions)),
+               "qec_decoder_set_relay")
+
+    def get_relay(self):
+        """(gammaX, gammaZ, solutions) with float32 tables [legs, n] (qec_decoder_get_relay), or None without tables."""
+        legs, sol = ctypes.c_int(0), ctypes.c_int(0)
+        _check(lib().qec_decoder_get_relay(self._h, None, None, ctypes.byref(legs), ctypes.byref(sol)), "qec_decoder_get_relay")
+        if legs.value == 0:
+            return None
+        gX = np.empty((legs.value, self.code.n), dtype=np.float32)
+        gZ = np.empty((legs.value, self.code.n), dtype=np.float32)
+        _check(lib().qec_decoder_get_relay(self._h, _ptr(gX), _ptr(gZ), None, None), "qec_decoder_get_relay")
+        return gX, gZ, sol.value
 
     def last_path(self):
         """The launch sequence of this handle's last decode call (QEC_OPT_LAST_PATH) as a set of

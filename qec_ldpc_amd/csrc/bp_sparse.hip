@@ -24,7 +24,9 @@
 // degrees), run the same four decode bodies -- sp_flood_decode (the flooding schedule, scalar p' or PRIORS),
 // sp_corr_decode (CORR), sp_serial_decode (SERIAL) and sp_minsum_decode (MINSUM) -- each templated on GENERAL, which selects the table
 // sentinels, the packed syndrome byte and the update functions; everything around the updates (loops, stop tests,
-// post-processing, flags) is one text for both routes.  The plan keeps one table of kernels, by variant and stop rule.
+// post-processing, flags) is one text for both routes.  A third entry, bp_relay_kernel, runs sp_relay_decode (RELAY: the
+// min-sum body with a memory per variable and a chain of legs) for both routes under an argument block of its own.  The
+// plan keeps one table of kernels, by variant and stop rule.
 //
 // Arithmetic is the same as the wave-circulant engine's (and so the reference's):
 // left folds in ascending neighbour order (prefix reuse only), IEEE fp32 with
@@ -958,6 +960,249 @@ __device__ __forceinline__ void sp_minsum_decode(const SparseArgs& a, const uint
     }
 }
 
+// ---- RELAY: chained memory min-sum legs (qec_decoder_set_relay; DESIGN.md section 2, "The relay form") -----
+// The min-sum body with one fp32 memory M_v per variable and a chain of legs: each leg starts from channel-LLR slots and
+// the previous leg's posteriors in M, runs under the call's stop rule counted within the leg, and a leg whose final
+// decisions satisfy the syndrome is a solution; the sector ends at its S-th solution or after its last leg and returns
+// the lightest solution.  The check update is sp_minsum_check, the variable update sp_minsum_var's folds started from
+// the bias b = ((1 - g) lam + g M) + 0.0f (never -0.0f, as that function's padding needs).
+// The entry bp_relay_kernel has its own argument block: SparseArgs as the MINSUM kernels read it, a general code's
+// degree bytes, and the relay's tables, so that no field of the other kernels' blocks moves.  Workspace, grid and
+// workgroup are the scalar plan's; the extra state -- M (2n floats) and the best decisions (2n bytes) -- lives in the
+// workgroup's slice of a global region (relayWs), where entry v is read and written by v's own thread only (the same
+// thread in every pass, v = tid + k nt), so it needs no barrier of its own.
+//   * the leg counter, the iteration counter within the leg, the solution count and the best weight of each sector are
+//     workgroup-uniform; one loop trip advances every running sector by one iteration, `last` is per sector;
+//   * a sector that ends a leg without ending the relay re-initialises its own slots behind the trip's barriers while the
+//     other sector's slots stay as they are; a sector that ends the relay keeps the slots and decision bytes of its last
+//     executed leg for the flags and the export;
+//   * the weight W of a solution is formed only with S > 1 (workgroup-uniform): per-thread sums of w_v over the set
+//     decision bytes, added into two static LDS words (integer adds: the order does not matter), no global atomics.
+struct RelayArgs {
+    SparseArgs s;            // as the MINSUM kernels read it (errorProbability = lambda(p'), prior = the LLRs, c0 = alpha)
+    const uint8_t* chkDeg;   // a general code's degree bytes (null: regular)
+    const float* gamma;      // [legs][sector][n]
+    const int32_t* weight;   // null (w_v = 1), or sector X [n] then Z [n]: the handle's integer weight tables
+    uint8_t* relayWs;        // per workgroup: M [2n] floats, best [2n] bytes
+    long long relayStride;   // bytes per workgroup
+    int legs, solutions;
+};
+
+// sp_minsum_var from the bias b; returns the posterior, decides through `dec`
+template <int MAXDV, bool GENERAL>
+__device__ __forceinline__ float sp_relay_var(float* __restrict__ msg, const int32_t* __restrict__ ve, int dv, float b,
+                                              bool last, bool& dec)
+{
+    int idx[MAXDV];
+    bool use[MAXDV];  // GENERAL: wave-uniform, some active lane has entry j
+    float r[MAXDV];
+#pragma unroll
+    for (int j = 0; j < MAXDV; ++j) {
+        idx[j] = -1;
+        if (j < dv) idx[j] = ve[j];
+        use[j] = GENERAL ? __builtin_amdgcn_ballot_w64(idx[j] >= 0) != 0 : j < dv;
+    }
+#pragma unroll
+    for (int j = 0; j < MAXDV; ++j)
+        if (use[j]) {
+            const bool real = idx[j] >= 0;
+            const float x = msg[real ? idx[j] : 0];  // a padded lane's value is dropped by the select
+            r[j] = real ? x : 0.0f;
+        }
+    float post = b;
+    if (last) {
+#pragma unroll
+        for (int k = 0; k < MAXDV; ++k)
+            if (use[k]) post = post + r[k];
+#pragma unroll
+        for (int j = 0; j < MAXDV; ++j)
+            if (use[j] && idx[j] >= 0) msg[idx[j]] = post;
+    } else {
+#pragma unroll
+        for (int j = 0; j < MAXDV; ++j)
+            if (use[j]) {
+                float t = post;  // b + r_0 + ... + r_{j-1}
+#pragma unroll
+                for (int k = j + 1; k < MAXDV; ++k)
+                    if (use[k]) t = t + r[k];
+                if (idx[j] >= 0) msg[idx[j]] = t;
+                post = post + r[j];
+            }
+    }
+    dec = idx[0] >= 0 && post < 0.0f;
+    return post;
+}
+
+template <int STOP, int MAXDC, int MAXDV, bool GENERAL>
+__device__ __forceinline__ void sp_relay_decode(const RelayArgs& ra, uint8_t* ws)
+{
+    __shared__ uint32_t wsum[2];  // the weights of sector X's and sector Z's solution (S > 1)
+    const SparseArgs& a = ra.s;
+    const uint8_t* __restrict__ chkDeg = ra.chkDeg;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
+    const int EX = mX * dc, E = m * dc;
+    float* msg = reinterpret_cast<float*>(ws);            // E floats
+    uint8_t* syn = ws + (size_t)E * sizeof(float);        // m bytes: sX then sZ
+    uint8_t* hd = syn + m;                                // 2n bytes: X then Z decisions
+    uint8_t* rws = ra.relayWs + (long long)blockIdx.x * ra.relayStride;
+    float* mem = reinterpret_cast<float*>(rws);           // M: 2n floats, X then Z
+    uint8_t* best = rws + (size_t)2 * n * sizeof(float);  // 2n bytes: the best solution's decisions
+
+    const float lam0 = a.errorProbability, alpha = a.c0;
+    const float* llr = a.prior;
+    const bool tab = llr != nullptr;  // workgroup-uniform: per-variable channel LLRs or the scalar one
+    const int N = a.maxIter < 0 ? 0 : a.maxIter;
+    const int L = ra.legs, S = ra.solutions;
+    const bool weigh = S > 1;
+
+    // the slots of sector X (doX) / Z (doZ) at the start of a leg: the channel LLR of the slot's variable
+    auto init_slots = [&](bool doX, bool doZ) {
+        for (int e = tid; e < E; e += nt) {
+            if (e < EX ? !doX : !doZ) continue;
+            const int v = (GENERAL || tab) ? a.chkVar[e] : 0;
+            float x = __uint_as_float(kMinSumCap);  // an unused slot of a general code
+            if (!GENERAL || v >= 0) x = tab ? llr[(e < EX ? 0 : n) + v] : lam0;
+            msg[e] = x;
+        }
+    };
+
+    for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
+        sp_load_syndromes<GENERAL>(a, chkDeg, b, syn);
+        init_slots(true, true);
+        for (int v = tid; v < 2 * n; v += nt) {  // leg 0: M = lambda; the decisions of N = 0
+            int dv;
+            const int32_t* ve = sp_var_edges(a, v, dv);
+            const float lam = tab ? llr[v] : lam0;
+            mem[v] = lam;
+            hd[v] = dv > 0 && (!GENERAL || ve[0] >= 0) && lam < 0.0f;
+        }
+        __syncthreads();
+
+        // workgroup-uniform, per sector (0 = X, 1 = Z)
+        bool act[2] = {true, true};
+        int leg[2] = {0, 0}, k[2] = {0, 0}, its[2] = {0, 0}, sols[2] = {0, 0};
+        uint32_t wbest[2] = {0u, 0u};
+        while (act[0] || act[1]) {
+            bool bad[2] = {true, true};  // SYNDROME: of this trip's decisions
+            if (N > 0) {
+                const bool lastX = k[0] == N - 1, lastZ = k[1] == N - 1;
+                its[0] += act[0];
+                its[1] += act[1];
+                for (int c = tid; c < m; c += nt) {
+                    if (c < mX ? !act[0] : !act[1]) continue;
+                    sp_minsum_check<GENERAL>(msg + (size_t)c * dc, dc, syn[c], alpha);
+                }
+                __syncthreads();
+                for (int v = tid; v < 2 * n; v += nt) {
+                    const bool z = v >= n;
+                    if (z ? !act[1] : !act[0]) continue;
+                    int dv;
+                    const int32_t* ve = sp_var_edges(a, v, dv);
+                    const float lam = tab ? llr[v] : lam0;
+                    const float g = ra.gamma[((size_t)(z ? leg[1] : leg[0]) * 2 + z) * n + (z ? v - n : v)];
+                    const float t0 = 1.0f - g;
+                    const float t1 = t0 * lam;
+                    const float t2 = g * mem[v];
+                    float bias = t1 + t2;
+                    bias = bias + 0.0f;  // -0.0f becomes +0.0f
+                    bool h;
+                    mem[v] = sp_relay_var<MAXDV, GENERAL>(msg, ve, dv, bias, z ? lastZ : lastX, h);
+                    hd[v] = h;
+                }
+                __syncthreads();
+                k[0] += act[0];
+                k[1] += act[1];
+            }
+            // which sectors end their leg here (the call's stop rule, counted within the leg)
+            bool end[2];
+            end[0] = act[0] && k[0] == N;
+            end[1] = act[1] && k[1] == N;
+            if (STOP == QEC_STOP_REF && N > 0) {
+                const bool tx = act[0] && (k[0] - 1) % 10 == 0, tz = act[1] && (k[1] - 1) % 10 == 0;
+                if (tx || tz) {
+                    bool bx = false, bz = false;
+                    for (int e = tid; e < E; e += nt) {
+                        const bool in = sp_minsum_inside(msg[e]);
+                        if (e < EX) bx |= in; else bz |= in;
+                    }
+                    const bool anyx = __syncthreads_or(bx), anyz = __syncthreads_or(bz);
+                    if (tx && !anyx) end[0] = true;
+                    if (tz && !anyz) end[1] = true;
+                }
+            } else if (STOP == QEC_STOP_SYNDROME && N > 0) {
+                bool bx = false, bz = false;
+                sp_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
+                bad[0] = __syncthreads_or(bx);
+                bad[1] = __syncthreads_or(bz);
+                if (act[0] && !bad[0]) end[0] = true;
+                if (act[1] && !bad[1]) end[1] = true;
+            }
+            if (!end[0] && !end[1]) continue;
+
+            // ---- the end of a leg: a solution?  the next leg, or the end of the sector's relay ----
+            if (STOP != QEC_STOP_SYNDROME || N == 0) {
+                bool bx = false, bz = false;
+                sp_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
+                bad[0] = __syncthreads_or(bx);
+                bad[1] = __syncthreads_or(bz);
+            }
+            const bool solved[2] = {end[0] && !bad[0], end[1] && !bad[1]};
+            uint32_t W[2] = {0u, 0u};
+            if (weigh && (solved[0] || solved[1])) {
+                if (tid < 2) wsum[tid] = 0u;
+                __syncthreads();
+                uint32_t wx = 0u, wz = 0u;
+                for (int v = tid; v < 2 * n; v += nt) {
+                    const bool z = v >= n;
+                    if (!(z ? solved[1] : solved[0]) || !hd[v]) continue;
+                    const uint32_t w = ra.weight != nullptr ? (uint32_t)ra.weight[v] : 1u;
+                    if (z) wz += w; else wx += w;
+                }
+                if (wx) atomicAdd(&wsum[0], wx);
+                if (wz) atomicAdd(&wsum[1], wz);
+                __syncthreads();
+                W[0] = wsum[0];
+                W[1] = wsum[1];
+            }
+            bool keep[2], next[2];
+            for (int sec = 0; sec < 2; ++sec) {
+                keep[sec] = solved[sec] && (sols[sec] == 0 || W[sec] < wbest[sec]);  // ties keep the earlier leg
+                if (keep[sec]) wbest[sec] = W[sec];
+                sols[sec] += solved[sec];
+                const bool done = end[sec] && (sols[sec] == S || leg[sec] == L - 1 || N == 0);
+                next[sec] = end[sec] && !done;
+                if (done) act[sec] = false;
+                if (next[sec]) { ++leg[sec]; k[sec] = 0; }
+            }
+            if (keep[0] || keep[1])
+                for (int v = tid; v < 2 * n; v += nt)
+                    if (v >= n ? keep[1] : keep[0]) best[v] = hd[v];
+            if (next[0] || next[1]) {
+                init_slots(next[0], next[1]);
+                __syncthreads();
+            }
+        }
+
+        // ---- the final state: the last executed leg's slots and decision bytes, the best solution ----
+        bool bx = false, bz = false;
+        for (int e = tid; e < E; e += nt) {
+            const bool in = sp_minsum_inside(msg[e]);
+            if (e < EX) bx |= in; else bz |= in;
+        }
+        for (int v = tid; v < 2 * n; v += nt) {
+            const bool z = v >= n;
+            const uint8_t h = (z ? sols[1] : sols[0]) ? best[v] : hd[v];
+            if (z) a.eZ[b * n + (v - n)] = h; else a.eX[b * n + v] = h;
+        }
+        const bool convFailX = __syncthreads_or(bx), convFailZ = __syncthreads_or(bz);
+        if (a.q != nullptr)
+            for (int e = tid; e < E; e += nt) a.q[b * E + e] = (!GENERAL || a.chkVar[e] >= 0) ? msg[e] : 0.0f;
+        sp_store_status(a, b, sp_fail_flags(sols[0] == 0, sols[1] == 0, convFailX, convFailZ), its[0], its[1]);
+        __syncthreads();  // the workspace is reused by the next syndrome pair
+    }
+}
+
 // ---- the kernels ---------------------------------------------------------------
 // Both entries run the same bodies; they differ in GENERAL and in the degree bytes that a general code brings.
 template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false, bool SERIAL = false,
@@ -982,9 +1227,17 @@ __global__ __launch_bounds__(kSparseThreads) void bp_general_kernel(const Genera
     else sp_flood_decode<STOP, MAXDC, MAXDV, true, PRIORS>(ga.s, ga.chkDeg, ws);
 }
 
+// The relay's one entry for both routes (its argument block carries the degree bytes)
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL>
+__global__ __launch_bounds__(kSparseThreads) void bp_relay_kernel(const RelayArgs ra)
+{
+    uint8_t* ws = LDS ? sp_lds : ra.s.scratch + (long long)blockIdx.x * ra.s.ws_bytes;
+    sp_relay_decode<STOP, MAXDC, MAXDV, GENERAL>(ra, ws);
+}
+
 // ---- plan ------------------------------------------------------------------
-// The kernels of one shape, by variant and stop rule.  SERIAL takes priors as a runtime branch, CORR and MINSUM too.
-enum { kScalar = 0, kPriors = 1, kCorr = 2, kSerial = 3, kMinSum = 4, kVariants = 5 };
+// The kernels of one shape, by variant and stop rule.  SERIAL takes priors as a runtime branch, CORR, MINSUM and RELAY too.
+enum { kScalar = 0, kPriors = 1, kCorr = 2, kSerial = 3, kMinSum = 4, kRelay = 5, kVariants = 6 };
 using SparseKernels = const void* [kVariants][3];
 
 template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL, bool PRIORS, bool CORR, bool SERIAL, bool MINSUM = false>
@@ -1003,6 +1256,7 @@ static void sparse_kernels_of_stop(SparseKernels& fn)
     fn[kCorr][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, true, false>();
     fn[kSerial][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, false, true>();
     fn[kMinSum][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, false, false, true>();
+    fn[kRelay][STOP] = reinterpret_cast<const void*>(&bp_relay_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL>);
 }
 
 template <int MAXDC, int MAXDV, bool LDS, bool GENERAL>
@@ -1035,6 +1289,10 @@ struct SparsePlan {
     int LX = 0, LZ = 0;
     DeviceArray<int32_t> chkVar, varEdge;
     DeviceArray<uint8_t> scratch;
+    // the RELAY kernels' state, grid x relay_stride bytes: allocated by the first qec_decoder_set_relay
+    // (sparse_plan_relay_reserve), never by a decode call
+    DeviceArray<uint8_t> relay_ws;
+    long long relay_stride = 0;
     std::string name;
 };
 
@@ -1194,6 +1452,20 @@ void* sparse_plan_create(const Code& c, int device)
 const int32_t* sparse_plan_chkvar(const void* plan) { return static_cast<const SparsePlan*>(plan)->chkVar.data(); }
 const int32_t* sparse_plan_varedge(const void* plan) { return static_cast<const SparsePlan*>(plan)->varEdge.data(); }
 
+// The RELAY kernels' per-workgroup state (M: 2n floats, the best decisions: 2n bytes); the caller has made the plan's
+// device current.  Allocates once.
+int sparse_plan_relay_reserve(void* plan)
+{
+    auto* p = static_cast<SparsePlan*>(plan);
+    p->relay_stride = (10LL * p->n + 15) / 16 * 16;
+    try {
+        p->relay_ws.reserve((size_t)p->grid * p->relay_stride);
+    } catch (const std::exception& ex) {
+        return fail(QEC_ERR_NOMEM, std::string("sparse engine: relay workspace: ") + ex.what());
+    }
+    return QEC_OK;
+}
+
 int launch_decode_sparse(void* plan, const SparseDecode& d, hipStream_t stream)
 {
     auto* p = static_cast<SparsePlan*>(plan);
@@ -1228,7 +1500,22 @@ int launch_decode_sparse(void* plan, const SparseDecode& d, hipStream_t stream)
     }
     GeneralArgs ga{a, p->chkDeg.data()};
     void* args[] = {p->general ? static_cast<void*>(&ga) : static_cast<void*>(&a)};  // the entry's one argument
-    const int variant = d.minsum ? kMinSum : d.serial ? kSerial : d.corr ? kCorr : d.prior ? kPriors : kScalar;
+    int variant = d.minsum ? kMinSum : d.serial ? kSerial : d.corr ? kCorr : d.prior ? kPriors : kScalar;
+    RelayArgs ra{};
+    if (d.minsum && d.gamma != nullptr) {  // min-sum with relay tables: the RELAY kernels
+        if (d.legs < 1 || d.solutions < 1 || p->relay_ws.data() == nullptr)
+            return fail(QEC_ERR_ARG, "bp_sparse launch: the relay needs its tables and its workspace (qec_decoder_set_relay)");
+        ra.s = a;
+        ra.chkDeg = p->general ? p->chkDeg.data() : nullptr;
+        ra.gamma = d.gamma;
+        ra.weight = d.relay_weight;
+        ra.relayWs = p->relay_ws.data();
+        ra.relayStride = p->relay_stride;
+        ra.legs = d.legs;
+        ra.solutions = d.solutions;
+        args[0] = &ra;
+        variant = kRelay;
+    }
     const unsigned grid = (unsigned)std::min<long long>(d.B, p->grid);
     (void)hipLaunchKernel(p->fn[variant][d.stop], dim3(grid), dim3(p->threads), args, p->lds ? (size_t)p->ws_bytes : 0, stream);
     hipError_t err = hipGetLastError();

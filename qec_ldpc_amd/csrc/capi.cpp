@@ -87,7 +87,8 @@ int cpu_threads();
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
                      bool near_hard, const float* prior, int corr, const float* cond, int serial, int minsum,
-                     const float* llr);
+                     const float* llr, const float* gamma, int legs, int solutions, const int32_t* weight);
+int sparse_plan_relay_reserve(void* plan);
 void correlated_priors(float p, float* c0, float* c1);
 int launch_pack_decisions(const uint8_t* eX, const uint8_t* eZ, const uint8_t* flags, long long B, int n, uint8_t* out,
                           hipStream_t st);
@@ -180,6 +181,21 @@ struct qec_decoder {
     int minsum() const { return bp_method == 1 ? minsum_scale : 0; }  // the engines' argument: 0, or the scale
     const float* llr_host() const { return has_priors ? mllr.data() : nullptr; }
     const float* llr_dev() const { return has_priors ? dmllr.data() : nullptr; }
+    // qec_decoder_set_relay ("The relay form"): L legs of per-variable memory strengths, [leg][sector][n],
+    // and S = the solutions to collect; data like minsum_scale, in effect while bp_method = 1.  The device copy is
+    // allocated once, by the first set, at the largest legal size (2 * 2^22 floats), and rewritten in place afterwards,
+    // so that no later set moves it under a captured graph; the kernels' workspace is allocated with it (the plan).
+    // relay_hold: the OSD stage's soft decode runs without the tables.
+    int relay_legs = 0, relay_solutions = 0;
+    bool relay_hold = false;
+    std::vector<float> relay;
+    DeviceArray<float> drelay;
+    bool relay_on() const { return relay_legs > 0 && bp_method == 1 && !relay_hold; }
+    const float* relay_host() const { return relay_on() ? relay.data() : nullptr; }
+    const float* relay_dev() const { return relay_on() ? drelay.data() : nullptr; }
+    // the weights of a relay solution: the integer tables of the priors (as qec_decoder_get_osd_weights), or none
+    const int32_t* relay_w_host() const { return has_priors ? osw.data() : nullptr; }
+    const int32_t* relay_w_dev() const { return has_priors ? dosw.data() : nullptr; }
     std::vector<float> cond;
     DeviceArray<float> dcond;
     const float* cond_host() const { return has_priors ? cond.data() : nullptr; }
@@ -981,6 +997,82 @@ int qec_decoder_get_minsum_llr(const qec_decoder* d, float* llrX, float* llrZ)
     return QEC_OK;
 }
 
+// Installs validated relay tables ([legs][sector][n]) on a handle and on every part of a group
+static int install_relay(qec_decoder* d, const std::vector<float>& tab, int legs, int solutions)
+{
+    for (qec_decoder* p : d->parts) {
+        const int rc = install_relay(p, tab, legs, solutions);
+        if (rc) return rc;
+    }
+    if (d->parts.empty() && !d->cpu) {
+        QEC_DEVICE_SCOPE(d->device);
+        // synchronous: the handle's last launch may still read the buffer this call rewrites
+        QEC_HIP_CHECK(hipStreamSynchronize(d->stream));
+        if (d->ws_used) QEC_HIP_CHECK(hipEventSynchronize(d->ws_ev));
+        try {
+            d->drelay.reserve(2 * (size_t)kRelayMaxEntries);  // once, at the largest legal size: it never moves
+        } catch (const std::exception& ex) {
+            return fail(QEC_ERR_NOMEM, std::string("qec_decoder_set_relay: ") + ex.what());
+        }
+        const int rc = sparse_plan_relay_reserve(d->sparse);
+        if (rc) return rc;
+        QEC_HIP_CHECK(hipMemcpy(d->drelay.data(), tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    d->relay = tab;
+    d->relay_legs = legs;
+    d->relay_solutions = solutions;
+    return QEC_OK;
+}
+
+int qec_decoder_set_relay(qec_decoder* d, const float* gammaX, const float* gammaZ, int legs, int solutions)
+{
+    if (!d) return fail(QEC_ERR_ARG, "qec_decoder_set_relay: null decoder");
+    if (!gammaX && !gammaZ && legs == 0 && solutions == 0) {  // clear: the handle behaves as one that never had tables
+        for (qec_decoder* p : d->parts) p->relay_legs = p->relay_solutions = 0;
+        d->relay_legs = d->relay_solutions = 0;
+        return QEC_OK;
+    }
+    if (!gammaX || !gammaZ)
+        return fail(QEC_ERR_ARG, "qec_decoder_set_relay: gammaX and gammaZ must both be given, or (NULL, NULL, 0, 0) to clear");
+    const int n = d->code->n;
+    if (legs < 1 || legs > kRelayMaxLegs || (long long)legs * n > kRelayMaxEntries)
+        return fail(QEC_ERR_ARG, "qec_decoder_set_relay: legs is 1 .. 1024 with legs * n <= 2^22");
+    if (solutions < 1 || solutions > kRelayMaxSolutions)
+        return fail(QEC_ERR_ARG, "qec_decoder_set_relay: solutions is 1 .. 64");
+    for (int sec = 0; sec < 2; ++sec) {
+        const float* g = sec ? gammaZ : gammaX;
+        for (size_t i = 0; i < (size_t)legs * n; ++i)
+            if (!(g[i] >= -1.0f && g[i] <= 1.0f))  // a NaN fails both comparisons
+                return fail(QEC_ERR_ARG, std::string("qec_decoder_set_relay: gamma") + (sec ? "Z[" : "X[") + std::to_string(i / n) +
+                                             "][" + std::to_string(i % n) + "] = " + std::to_string(g[i]) + " is not in [-1, 1]");
+    }
+    bool sparse = true;
+    for (const qec_decoder* p : parts_of(d)) sparse = sparse && (p->cpu || p->engine == QEC_ENGINE_SPARSE);
+    if (!sparse)
+        return fail(QEC_ERR_UNSUPPORTED,
+                    "qec_decoder_set_relay: the relay is min-sum with memory, which is not built for the wave-circulant engine; "
+                    "create the decoder with QEC_ENGINE_SPARSE (engine \"sparse\")");
+    std::vector<float> tab(2 * (size_t)legs * n);
+    for (int l = 0; l < legs; ++l) {
+        std::memcpy(tab.data() + (2 * (size_t)l) * n, gammaX + (size_t)l * n, n * sizeof(float));
+        std::memcpy(tab.data() + (2 * (size_t)l + 1) * n, gammaZ + (size_t)l * n, n * sizeof(float));
+    }
+    return install_relay(d, tab, legs, solutions);
+}
+
+int qec_decoder_get_relay(const qec_decoder* d, float* gammaX, float* gammaZ, int* legs, int* solutions)
+{
+    if (!d) return fail(QEC_ERR_ARG, "qec_decoder_get_relay: null decoder");
+    if (legs) *legs = d->relay_legs;
+    if (solutions) *solutions = d->relay_solutions;
+    const int n = d->code->n;
+    for (int l = 0; l < d->relay_legs; ++l) {
+        if (gammaX) std::memcpy(gammaX + (size_t)l * n, d->relay.data() + (2 * (size_t)l) * n, n * sizeof(float));
+        if (gammaZ) std::memcpy(gammaZ + (size_t)l * n, d->relay.data() + (2 * (size_t)l + 1) * n, n * sizeof(float));
+    }
+    return QEC_OK;
+}
+
 int qec_decoder_get_osd_weights(const qec_decoder* d, int32_t* wX, int32_t* wZ)
 {
     if (!d) return fail(QEC_ERR_ARG, "qec_decoder_get_osd_weights: null decoder");
@@ -1112,6 +1204,14 @@ int dispatch_decode(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, long l
             sd.lam = minsum_llr(2.0f / 3.0f * p);
             sd.llr = d->llr_dev();
             d->last_path |= QEC_PATH_MINSUM;
+            // qec_decoder_set_relay, read at the call: the RELAY kernels under the handle's tables
+            sd.gamma = d->relay_dev();
+            if (sd.gamma) {
+                sd.legs = d->relay_legs;
+                sd.solutions = d->relay_solutions;
+                sd.relay_weight = d->relay_w_dev();
+                d->last_path |= QEC_PATH_RELAY;
+            }
         }
         rc = launch_decode_sparse(d->sparse, sd, st);
         if (!rc && rec != nullptr) rc = launch_pack_decisions(eX, eZ, flags, B, c.n, rec, st);
@@ -1249,8 +1349,10 @@ int osd_reserve(qec_decoder* d, size_t cnt)
 int osd_compact_dev(qec_decoder* d, long long cnt, float p, bool count, hipStream_t st)
 {
     const int path = d->last_path;
+    d->relay_hold = true;  // the soft decode is plain min-sum (or the product rule), whatever relay tables the handle has
     int rc = dispatch_decode(d, d->osX.data(), d->osZ.data(), cnt, p, d->osd_iters, QEC_STOP_FIXED, d->oeX.data(),
                              d->oeZ.data(), d->ofs.data(), nullptr, nullptr, d->oq.data(), st);
+    d->relay_hold = false;
     d->last_path = path;
     if (rc) return rc;
     return launch_osd(d->odev, d->osd_sweep, d->osd_order, d->osX.data(), d->osZ.data(), cnt, d->oq.data(), d->oeX.data(),
@@ -1290,7 +1392,7 @@ int osd_repair_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t
             const int rc = cpu_decode_batch(d->cpu, cX.data(), cZ.data(), (long long)cnt, p, d->osd_iters, QEC_STOP_FIXED,
                                             cEX.data(), cEZ.data(), cFs.data(), nullptr, nullptr, cq.data(), 0,
                                             false, d->prior_host(), d->correlated, d->cond_host(), d->bp_schedule,
-                                            d->minsum(), d->llr_host());
+                                            d->minsum(), d->llr_host(), nullptr, 0, 0, nullptr);  // never the relay
             if (rc) return rc;
             long long swept = 0;
             osd_host_batch(*d->oplan, cX.data(), cZ.data(), (long long)cnt, cq.data(), cEX.data(), cEZ.data(), cF.data(), 0,
@@ -1409,9 +1511,10 @@ int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
     if (d->cpu) {
         const int rc = cpu_decode_batch(d->cpu, sX, sZ, (long long)B, p, maxIter, stop, eX, eZ, flags, rec, iters, q, 0,
                                         d->hard_paths && d->near_hard, d->prior_host(), d->correlated, d->cond_host(),
-                                        d->bp_schedule, d->minsum(), d->llr_host());
+                                        d->bp_schedule, d->minsum(), d->llr_host(), d->relay_host(), d->relay_legs,
+                                        d->relay_solutions, d->relay_w_host());
         d->last_path = (d->correlated ? QEC_PATH_CORRELATED : 0) | (d->bp_schedule ? QEC_PATH_SERIAL : 0) |
-                       (d->bp_method ? QEC_PATH_MINSUM : 0);
+                       (d->bp_method ? QEC_PATH_MINSUM : 0) | (d->relay_on() ? QEC_PATH_RELAY : 0);
         return rc || !d->osd ? rc : osd_repair_host(d, sX, sZ, B, p, eX, eZ, flags, rec);
     }
     QEC_DEVICE_SCOPE(d->device);
@@ -1765,7 +1868,7 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
         const int rc = cpu_decode_batch(d->cpu, sx.data(), sz.data(), cnt, p, maxIter, QEC_STOP_REF, ex.data(), ez.data(),
                                         fl.data(), nullptr, nullptr, nullptr, 0, d->hard_paths && d->near_hard,
                                         d->prior_host(), d->correlated, d->cond_host(), d->bp_schedule, d->minsum(),
-                                        d->llr_host());
+                                        d->llr_host(), d->relay_host(), d->relay_legs, d->relay_solutions, d->relay_w_host());
         if (rc) return rc;
         if (d->osd) {  // the counters describe the repaired estimates
             d->osd_sectors = 0;
@@ -1800,7 +1903,8 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
     d->osd_sectors = repaired;
     d->osd_cs_sectors = swept;
     d->last_path = (d->osd ? QEC_PATH_OSD : 0) | (d->correlated ? QEC_PATH_CORRELATED : 0) |
-                   (d->bp_schedule ? QEC_PATH_SERIAL : 0) | (d->bp_method ? QEC_PATH_MINSUM : 0);
+                   (d->bp_schedule ? QEC_PATH_SERIAL : 0) | (d->bp_method ? QEC_PATH_MINSUM : 0) |
+                   (d->relay_on() ? QEC_PATH_RELAY : 0);
     std::memset(out, 0, sizeof *out);
     out->randSeed = seed;
     out->numErrorsTested = (uint32_t)tested;

@@ -487,6 +487,126 @@ int decode_sector_minsum(const CpuSector& S, int n, bool general, const uint8_t*
     return it;
 }
 
+// One sector under the relay form (qec_decoder_set_relay; DESIGN.md section 2, "The relay form"): min-sum legs chained
+// through one fp32 memory per variable.  gam: the sector's rows of the tables, leg l at gam + l * gstride; wt: nullptr
+// (w_v = 1) or the sector's integer weights.  Leg l starts from channel-LLR slots and the memory of leg l - 1 (leg 0:
+// the channel LLRs), runs under the stop rule counted within the leg, and is a solution when its final decisions satisfy
+// the syndrome; the sector ends at its S-th solution or after leg L - 1.  w.e holds the best solution (none: the last
+// leg's decisions), q_out and conv_out the last executed leg's final state, syn_ok whether there is a solution; returns
+// the iterations over all legs.  The check update and the folds are decode_sector_minsum's.
+int decode_sector_relay(const CpuSector& S, int n, bool general, const uint8_t* syn, float lam0, const float* llr,
+                        int scale, int N, int stop, const float* gam, size_t gstride, int L, int nsol, const int32_t* wt,
+                        Work& w, bool& conv_out, bool& syn_ok, float* q_out)
+{
+    const int m = S.m, D = S.dc, dvs = S.dv;
+    const size_t E = (size_t)m * D;
+    float* q = w.q.data();
+    float* r = w.r.data();
+    uint8_t* e = w.e.data();
+    w.post.resize(n);
+    float* mem = w.post.data();
+    std::vector<uint8_t> best;
+    const float alpha = (float)scale / 256.0f;
+    auto cdeg = [&](int c) { return general ? (int)S.chk_deg[c] : D; };
+    auto vdeg = [&](int v) { return general ? (int)S.var_deg[v] : dvs; };
+    auto lam = [&](int v) { return llr ? llr[v] : lam0; };
+    auto syndrome_ok = [&]() {
+        for (int c = 0; c < m; ++c) {
+            uint32_t x = 0;
+            for (int k = 0; k < cdeg(c); ++k) x ^= e[S.chk_var[(size_t)c * D + k]];
+            if ((x & 1u) != syn[c]) return false;
+        }
+        return true;
+    };
+    auto all_outside = [&]() {
+        for (int c = 0; c < m; ++c)
+            for (int k = 0; k < cdeg(c); ++k)
+                if (minsum_inside(q[(size_t)c * D + k])) return false;
+        return true;
+    };
+    for (int v = 0; v < n; ++v) {
+        mem[v] = lam(v);
+        e[v] = vdeg(v) > 0 && lam(v) < 0.0f;  // N = 0
+    }
+    int total = 0, found = 0;
+    uint32_t wbest = 0;
+    for (int leg = 0; leg < L; ++leg) {
+        const float* g = gam + (size_t)leg * gstride;
+        for (int c = 0; c < m; ++c)
+            for (int k = 0; k < D; ++k) q[(size_t)c * D + k] = k < cdeg(c) ? lam(S.chk_var[(size_t)c * D + k]) : 0.0f;
+        bool conv = false;
+        for (int iter = 0; iter < N; ++iter) {
+            if (stop == QEC_STOP_REF && conv) break;
+            ++total;
+            for (int c = 0; c < m; ++c) {
+                const float* qc = q + (size_t)c * D;
+                float* rc = r + (size_t)c * D;
+                const int dc = cdeg(c);
+                uint32_t min1 = kMinSumCap, min2 = kMinSumCap, par = syn[c] != 0;
+                int arg = -1;
+                for (int k = 0; k < dc; ++k) {
+                    uint32_t b;
+                    std::memcpy(&b, qc + k, sizeof b);
+                    const uint32_t a = b & 0x7FFFFFFFu;
+                    par ^= b >> 31;
+                    if (a < min1) { min2 = min1; min1 = a; arg = k; }
+                    else if (a < min2) min2 = a;
+                }
+                for (int i = 0; i < dc; ++i) {
+                    uint32_t b, o;
+                    std::memcpy(&b, qc + i, sizeof b);
+                    const uint32_t mag = i == arg ? min2 : min1;
+                    float f;
+                    std::memcpy(&f, &mag, sizeof f);
+                    f = alpha * f;
+                    std::memcpy(&o, &f, sizeof o);
+                    o |= (par ^ (b >> 31)) << 31;
+                    std::memcpy(rc + i, &o, sizeof o);
+                }
+            }
+            const bool last = iter == N - 1;
+            for (int v = 0; v < n; ++v) {
+                const int32_t* ve = S.var_edge.data() + (size_t)v * dvs;
+                const int dv = vdeg(v);
+                if (dv == 0) { e[v] = 0; continue; }  // no check: decides 0, no memory
+                const float t0 = 1.0f - g[v];
+                const float t1 = t0 * lam(v);
+                const float t2 = g[v] * mem[v];
+                float bias = t1 + t2;
+                bias = bias + 0.0f;  // -0.0f becomes +0.0f
+                float post = bias;
+                for (int k = 0; k < dv; ++k) post = post + r[ve[k]];
+                e[v] = post < 0.0f;
+                mem[v] = post;
+                for (int j = 0; j < dv; ++j) {
+                    float t = post;
+                    if (!last) {
+                        t = bias;
+                        for (int k = 0; k < dv; ++k)
+                            if (k != j) t = t + r[ve[k]];
+                    }
+                    q[ve[j]] = t;
+                }
+            }
+            if (stop == QEC_STOP_REF && iter % 10 == 0) conv = all_outside();
+            if (stop == QEC_STOP_SYNDROME && syndrome_ok()) break;
+        }
+        if (syndrome_ok()) {  // a solution: the lightest so far wins, ties keep the earlier leg
+            uint32_t W = 0;
+            for (int v = 0; v < n; ++v)
+                if (e[v]) W += wt ? (uint32_t)wt[v] : 1u;
+            if (found == 0 || W < wbest) { wbest = W; best.assign(e, e + n); }
+            ++found;
+        }
+        if (found == nsol || N == 0) break;
+    }
+    conv_out = all_outside();
+    syn_ok = found > 0;
+    if (q_out) std::memcpy(q_out, q, E * sizeof(float));
+    if (found) std::memcpy(e, best.data(), n);
+    return total;
+}
+
 }  // namespace
 
 // The channel LLR of the min-sum form (qec_minsum_llr): (float) log((1 - pi) / pi), the float prior taken exactly to
@@ -558,10 +678,12 @@ void correlated_priors(float p, float* c0, float* c1)
 // minsum (QEC_OPT_BP_METHOD = 1): 0, or the scale k of scaled min-sum (decode_sector_minsum; flooding, no near-hard
 // jump, never with corr or serial); llr (with prior) = the handle's channel LLR tables, sector X [n] then Z [n],
 // without prior the scalar minsum_llr(p').
+// gamma (with minsum; qec_decoder_set_relay): nullptr, or the relay tables [legs][sector][n] for decode_sector_relay, with
+// solutions = S and weight = nullptr (w_v = 1) or the integer weights of the priors, sector X [n] then Z [n].
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
                      bool near_hard, const float* prior, int corr, const float* cond, int serial, int minsum,
-                     const float* llr)
+                     const float* llr, const float* gamma, int legs, int solutions, const int32_t* weight)
 {
     const CpuPlan& P = *static_cast<const CpuPlan*>(plan);
     const int n = P.n, nb = (n + 7) / 8;
@@ -604,7 +726,11 @@ int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long
                     for (int v = 0; v < n; ++v) pi[v] = first[v] ? (cond ? t0[n + v] : sc1) : (cond ? t0[v] : sc0);
                     pri = pi.data();
                 }
-                const int it = minsum ? decode_sector_minsum(S, n, P.general, syn, lam0, prior ? llr + (size_t)sec * n : nullptr,
+                const int it = minsum && gamma ? decode_sector_relay(S, n, P.general, syn, lam0, prior ? llr + (size_t)sec * n : nullptr,
+                                                                     minsum, maxIter, stop, gamma + (size_t)sec * n, 2 * (size_t)n, legs,
+                                                                     solutions, weight ? weight + (size_t)sec * n : nullptr, w, conv,
+                                                                     ok, qo)
+                               : minsum ? decode_sector_minsum(S, n, P.general, syn, lam0, prior ? llr + (size_t)sec * n : nullptr,
                                                              minsum, maxIter, stop, w, conv, ok, qo)
                                : serial ? decode_sector_serial(S, n, P.general, syn, p, pri, maxIter, stop, w, conv, ok, qo)
                                : P.general ? decode_sector_general(S, n, syn, p, pri, maxIter, stop, w, conv, ok, qo)

@@ -146,6 +146,16 @@ struct SparseDecode {
     int minsum = 0;
     float lam = 0.0f;
     const float* llr = nullptr;
+    // qec_decoder_set_relay (with minsum): the RELAY kernels under gamma = the tables [legs][sector][n], solutions = S and
+    // relay_weight = nullptr (w_v = 1) or the 2n integer weights of the handle's priors; gamma = nullptr: plain min-sum
+    const float* gamma = nullptr;
+    int legs = 0, solutions = 0;
+    const int32_t* relay_weight = nullptr;
 };
+
+// The relay form: the limits of qec_decoder_set_relay
+constexpr int kRelayMaxLegs = 1024;
+constexpr long long kRelayMaxEntries = 1LL << 22;   // legs x n
+constexpr int kRelayMaxSolutions = 64;
 
 }  // namespace qec

@@ -43,6 +43,10 @@
 //                      in the LLR domain.  Sparse-graph and CPU engines; not with --correlated or --bp-schedule serial
 //   --minsum-scale K   min-sum's factor alpha = K / 256 (QEC_OPT_MINSUM_SCALE, 1 .. 256, default 160); needs
 //                      --bp-method minsum
+//   --relay FILE       Relay-BP (qec_decoder_set_relay): FILE holds 2 L lines of n decimal floats, the memory strengths
+//                      of the L legs of sector X, then of the L legs of sector Z (each |gamma| <= 1); needs
+//                      --bp-method minsum
+//   --relay-solutions S   the relay stops at the lightest of its first S solutions (1 .. 64, default 1); needs --relay
 //   --pauli FILE       per-qubit Pauli channel (qec_decoder_set_pauli_channel): FILE holds three lines of n decimal
 //                      floats, pX, pY and pZ.  BP decodes under its marginals (and --correlated under its conditional
 //                      tables), the init file's p is not used, and --rng philox draws its errors from the channel.
@@ -95,8 +99,8 @@ int usage(const std::string& why)
               << "usage: qec_ldpc [--engine gpu|sparse|cpu] [--gpus N | --devices i,j,...] [--rng msvc|philox]"
                  " [--stop ref|fixed|syndrome] [--batch B] [--seed S] [--logical file|reference|degenerate]"
                  " [--osd 0 [--osd-order L] [--osd-iterations K] [--osd-score hamming|priors]] [--priors FILE]"
-                 " [--correlated xz|zx] [--bp-schedule flooding|serial] [--bp-method product|minsum [--minsum-scale K]]"
-                 " [--pauli FILE] initFile"
+                 " [--correlated xz|zx] [--bp-schedule flooding|serial] [--bp-method product|minsum [--minsum-scale K]"
+                 " [--relay FILE [--relay-solutions S]]] [--pauli FILE] initFile"
               << std::endl;
     return 2;
 }
@@ -133,6 +137,32 @@ void read_pauli(const std::string& path, int n, std::vector<float> (&out)[3])
     }
 }
 
+// --relay FILE: 2 L lines of n decimal floats (the L legs of sector X, then the L legs of sector Z); returns L
+int read_relay(const std::string& path, int n, std::vector<float>& gX, std::vector<float>& gZ)
+{
+    std::ifstream in(path);
+    if (!in.is_open()) throw std::string("--relay: unable to open " + path);
+    std::vector<float> all;
+    std::string line;
+    int lines = 0;
+    while (std::getline(in, line)) {
+        if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+        std::stringstream ss(line);
+        float v;
+        int k = 0;
+        while (ss >> v) { all.push_back(v); ++k; }
+        if (!ss.eof() || k != n)
+            throw std::string("--relay: each line of " + path + " needs n = " + std::to_string(n) + " decimal floats");
+        ++lines;
+    }
+    if (lines == 0 || lines % 2)
+        throw std::string("--relay: " + path + " needs 2 L lines of n floats (the L legs of X, then the L legs of Z)");
+    const size_t half = all.size() / 2;
+    gX.assign(all.begin(), all.begin() + half);
+    gZ.assign(all.begin() + half, all.end());
+    return lines / 2;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -145,7 +175,9 @@ int main(int argc, char** argv)
     std::time_t ts = std::chrono::system_clock::to_time_t(std::chrono::system_clock::now());
     log << std::endl << std::ctime(&ts);
     std::vector<int> devices{0};
-    std::string engine = "gpu", rng = "msvc", stopName = "ref", logical = "file", priorsFile, pauliFile;
+    std::string engine = "gpu", rng = "msvc", stopName = "ref", logical = "file", priorsFile, pauliFile, relayFile;
+    int relaySolutions = 1;
+    bool relaySolutionsFlag = false;
     int correlated = 0, bpSchedule = 0, bpMethod = 0, minsumScale = 160;
     bool minsumScaleFlag = false;
     bool deviceFlag = false, stopFlag = false, batchFlag = false, seedFlag = false, osd = false, osdIterFlag = false;
@@ -221,6 +253,13 @@ int main(int argc, char** argv)
                 minsumScale = std::stoi(val);
                 if (minsumScale < 1 || minsumScale > 256) return usage("--minsum-scale: 1 .. 256");
                 minsumScaleFlag = true;
+            } else if (flag == "--relay") {
+                relayFile = val;
+            } else if (flag == "--relay-solutions") {
+                size_t used = 0;
+                relaySolutions = std::stoi(val, &used);
+                relaySolutionsFlag = true;
+                if (used != val.size() || relaySolutions < 1 || relaySolutions > 64) return usage("--relay-solutions: 1 .. 64");
             } else if (flag == "--seed") {
                 seed = std::stoull(val, nullptr, 0);
                 seedFlag = true;
@@ -242,6 +281,8 @@ int main(int argc, char** argv)
     if (minsumScaleFlag && !bpMethod) return usage("--minsum-scale needs --bp-method minsum");
     if (bpMethod && correlated) return usage("--bp-method minsum and --correlated exclude each other");
     if (bpMethod && bpSchedule) return usage("--bp-method minsum and --bp-schedule serial exclude each other");
+    if (!relayFile.empty() && !bpMethod) return usage("--relay needs --bp-method minsum");
+    if (relaySolutionsFlag && relayFile.empty()) return usage("--relay-solutions needs --relay FILE");
     if (!pauliFile.empty() && !priorsFile.empty()) return usage("--pauli and --priors exclude each other");
     if (osdScore == 1 && priorsFile.empty()) return usage("--osd-score priors needs --priors FILE");
     if (argc - a != 1 || devices.empty()) {
@@ -278,6 +319,8 @@ int main(int argc, char** argv)
         if (!priorsFile.empty()) read_priors(priorsFile, code.n, priorX, priorZ);
         std::vector<float> pauli[3];
         if (!pauliFile.empty()) read_pauli(pauliFile, code.n, pauli);
+        std::vector<float> gammaX, gammaZ;
+        const int relayLegs = relayFile.empty() ? 0 : read_relay(relayFile, code.n, gammaX, gammaZ);
         if (rng == "philox") {
             std::unique_ptr<DecoderGPU> dp(engine == "sparse" ? new DecoderGPU(code, 0, QEC_ENGINE_SPARSE)
                                                                : new DecoderGPU(code, devices));
@@ -289,6 +332,7 @@ int main(int argc, char** argv)
             if (correlated) decoder.SetCorrelated(correlated);
             if (bpSchedule) decoder.SetBpSchedule(bpSchedule);
             if (bpMethod) decoder.SetBpMethod(bpMethod, minsumScale);
+            if (relayLegs) decoder.SetRelay(gammaX, gammaZ, relayLegs, relaySolutions);
             std::cout << "Engine: " << decoder.Describe() << std::endl;
             const int stop = stopName == "ref" ? QEC_STOP_REF : stopName == "fixed" ? QEC_STOP_FIXED : QEC_STOP_SYNDROME;
             std::stringstream fileName;
@@ -317,6 +361,7 @@ int main(int argc, char** argv)
             if (correlated) c->SetCorrelated(correlated);
             if (bpSchedule) c->SetBpSchedule(bpSchedule);
             if (bpMethod) c->SetBpMethod(bpMethod, minsumScale);
+            if (relayLegs) c->SetRelay(gammaX, gammaZ, relayLegs, relaySolutions);
             std::cout << "Engine: CPU (" << std::thread::hardware_concurrency() << " threads)" << std::endl;
         } else {
             DecoderGPU* g = engine == "sparse" ? new DecoderGPU(code, 0, QEC_ENGINE_SPARSE) : new DecoderGPU(code, devices);
@@ -328,6 +373,7 @@ int main(int argc, char** argv)
             if (correlated) g->SetCorrelated(correlated);
             if (bpSchedule) g->SetBpSchedule(bpSchedule);
             if (bpMethod) g->SetBpMethod(bpMethod, minsumScale);
+            if (relayLegs) g->SetRelay(gammaX, gammaZ, relayLegs, relaySolutions);
             std::cout << "Engine: " << g->Describe() << std::endl;
         }
         for (; w <= W; ++w) {
