@@ -176,6 +176,11 @@ public:
         check(qec_decoder_set_option(dec_, QEC_OPT_MINSUM_SCALE, scale));
         check(qec_decoder_set_option(dec_, QEC_OPT_BP_METHOD, method));
     }
+    // The kernels of plain min-sum decodes (QEC_OPT_MINSUM_WAVE): 0 = the sparse-graph MINSUM kernels (the default),
+    // 1 = the register-resident wave kernels, bit-identical, for circulant codes with P <= 64 and a block shape of the
+    // runtime-shift table (qec_code_has_wave_minsum).  A kernel choice of a sparse-engine decoder: 1 on any other
+    // decoder or code throws the library's message.  In effect while SetBpMethod(1) is and no relay is set.
+    void SetMinSumWave(int on) { check(qec_decoder_set_option(dec_, QEC_OPT_MINSUM_WAVE, on)); }
     // Relay-BP (qec_decoder_set_relay): `legs` legs of memory min-sum under SetBpMethod(1), gammaX / gammaZ the memory
     // strengths [legs][n] (|gamma| <= 1), stopping at the first solution or at the lightest of the first `solutions`.
     // The sparse-graph engine takes them; a wave-circulant decoder throws the library's message.

@@ -121,6 +121,10 @@ int qec_code_degrees(const qec_code* code, int* out5);
  * variable with c.  colour: numEqs entries, nullable.  Returns the number of layers (< 0 on error).  Checks of
  * one colour share no variable; a circulant-permutation QC code gives colour c / P. */
 int qec_code_layers(const qec_code* code, int sector, int32_t* colour);
+/* 1 if the code has wave min-sum kernels (QEC_OPT_MINSUM_WAVE): a circulant-permutation code with 1 <= P <= 64 whose
+ * block shape (J, K, L) is one of (4,5,10) (3,3,6) (2,3,6) (3,4,8) (4,4,8) (3,5,10) (4,6,12) (2,2,4); else 0.  A host
+ * query: no device is touched.  (< 0 on error.) */
+int qec_code_has_wave_minsum(const qec_code* code);
 /* Replaces the QC_LDPC_CSS(J,K,L,P,sigma,tau) generator (QEC_LDPC/QEC_LDPC_CSS.cu:5-131).
  * Generated codes carry no I-P matrix (the reference never generates one); qec_code_with_logical
  * derives the check from the two matrices. */
@@ -190,6 +194,10 @@ int qec_decoder_destroy(qec_decoder* dec);
  * a single-device handle: call them on qec_decoder_part(dec, k).  Every ordinal must be >= 0
  * (QEC_ERR_ARG otherwise: a group is GPU-only). */
 qec_decoder* qec_decoder_create_multi(const qec_code* code, const int* devices, int ndevices, size_t max_batch);
+/* The same with every part created by qec_decoder_create_engine(.., engine): QEC_ENGINE_AUTO (as above),
+ * QEC_ENGINE_CIRCULANT or QEC_ENGINE_SPARSE (QEC_ENGINE_CPU: QEC_ERR_ARG). */
+qec_decoder* qec_decoder_create_multi_engine(const qec_code* code, const int* devices, int ndevices, size_t max_batch,
+                                             int engine);
 int qec_decoder_num_parts(const qec_decoder* dec);      /* 1 for a single-device decoder */
 qec_decoder* qec_decoder_part(qec_decoder* dec, int k); /* part k (the handle itself for k = 0 of a single one) */
 int qec_decoder_device(const qec_decoder* dec);         /* HIP device ordinal (of part 0 for a group) */
@@ -379,12 +387,24 @@ int qec_decoder_device(const qec_decoder* dec);         /* HIP device ordinal (o
  *     qec_osd and qec_osd_dev then order the columns by LLR ascending (q_final is an LLR).  The near-hard jump never
  *     fires under 1.  A group applies the value to every part.
  *   QEC_OPT_MINSUM_SCALE (default 160; 1 .. 256, other values QEC_ERR_ARG): the factor of min-sum's check update,
- *     alpha = (float)value / 256.0f (exact in fp32; the default is 0.625).  Read at the call, as the method is. */
+ *     alpha = (float)value / 256.0f (exact in fp32; the default is 0.625).  Read at the call, as the method is.
+ *   QEC_OPT_MINSUM_WAVE (default 0; 0 or 1, other values QEC_ERR_ARG): a kernel choice of a sparse-engine handle.
+ *     1 = the handle's plain min-sum decodes run the register-resident wave kernels (bp_wave_minsum.hip; DESIGN.md
+ *     section 2, "The min-sum form in the wave layout"): one wave per G = 64 / P syndrome pairs, a sector's messages
+ *     in registers, the same rule in the same evaluation order, so every output (estimates, flags, iteration
+ *     counts, q_final) is the MINSUM kernels' bit for bit, with the scalar p or with the handle's priors.  The value
+ *     is data, like QEC_OPT_MINSUM_SCALE: it takes effect in every decode while QEC_OPT_BP_METHOD = 1 and no relay
+ *     tables are set; under the product rule it does nothing, and with relay tables the RELAY kernels run as before.
+ *     QEC_PATH_WAVE is set in QEC_OPT_LAST_PATH exactly when the wave kernels ran.  The _dev entry points read it at
+ *     the call and allocate nothing.  1 is refused with QEC_ERR_UNSUPPORTED (the handle stays as it was, the text
+ *     names the reason) on a sparse handle whose code has no wave min-sum kernel (qec_code_has_wave_minsum), on a
+ *     wave-circulant handle and on a CPU handle.  A group applies the value to every part. */
 enum { QEC_OPT_HARD_PATHS = 1, QEC_OPT_CYCLE_JUMP = 2, QEC_OPT_SCHEDULE = 3, QEC_OPT_SECTOR_SPLIT = 4,
        QEC_OPT_PHASE_STATS = 5, QEC_OPT_TRIAGE = 6, QEC_OPT_LAST_PATH = 7, QEC_OPT_MC_DECODE_TIME = 8,
        QEC_OPT_OSD = 9, QEC_OPT_OSD_ITERATIONS = 10, QEC_OPT_OSD_SECTORS = 11, QEC_OPT_OSD_SWEEP = 12,
        QEC_OPT_OSD_ORDER = 13, QEC_OPT_OSD_CS_SECTORS = 14, QEC_OPT_NEAR_HARD_JUMP = 15, QEC_OPT_OSD_SCORE = 16,
-       QEC_OPT_CORRELATED = 17, QEC_OPT_BP_SCHEDULE = 18, QEC_OPT_BP_METHOD = 19, QEC_OPT_MINSUM_SCALE = 20 };
+       QEC_OPT_CORRELATED = 17, QEC_OPT_BP_SCHEDULE = 18, QEC_OPT_BP_METHOD = 19, QEC_OPT_MINSUM_SCALE = 20,
+       QEC_OPT_MINSUM_WAVE = 21 };
 enum {
     QEC_PATH_ORDERED = 1,          /* dispatch order pass (schedule.hip) */
     QEC_PATH_SECTOR_ORDER = 2,     /* ... in the per-sector form (each sector's waves by its own weight) */
@@ -398,7 +418,8 @@ enum {
     QEC_PATH_CORRELATED = 512,     /* one sector decoded under priors conditioned on the other's estimate */
     QEC_PATH_SERIAL = 1024,        /* BP under the serial schedule (QEC_OPT_BP_SCHEDULE = 1) */
     QEC_PATH_MINSUM = 2048,        /* scaled min-sum BP (QEC_OPT_BP_METHOD = 1) */
-    QEC_PATH_RELAY = 4096          /* ... as a relay of memory min-sum legs (qec_decoder_set_relay) */
+    QEC_PATH_RELAY = 4096,         /* ... as a relay of memory min-sum legs (qec_decoder_set_relay) */
+    QEC_PATH_WAVE = 8192           /* ... by the register-resident wave kernels (QEC_OPT_MINSUM_WAVE = 1) */
 };
 /* The near-hard jump's threshold for p' = pPrime (the float (2/3) errorProbability the decoder forms), R
  * checks per variable and L variables per check: *eps0 = the largest power of two in [2^-20, 2^-8] with

@@ -29,7 +29,8 @@ ENGINE = {"auto": 0, "circulant": 1, "sparse": 2, "cpu": 3}
 OPTION = {"hard_paths": 1, "cycle_jump": 2, "schedule": 3, "sector_split": 4, "phase_stats": 5, "triage": 6,
           "last_path": 7, "mc_decode_time": 8, "osd": 9, "osd_iterations": 10, "osd_sectors": 11,
           "osd_sweep": 12, "osd_order": 13, "osd_cs_sectors": 14, "near_hard": 15, "osd_score": 16,
-          "correlated": 17, "bp_schedule": 18, "bp_method": 19, "minsum_scale": 20}
+          "correlated": 17, "bp_schedule": 18, "bp_method": 19, "minsum_scale": 20,
+          "minsum_wave": 21}
 OPTIONS = OPTION
 # values of the "bp_schedule" option (QEC_OPT_BP_SCHEDULE)
 BP_SCHEDULE = {"flooding": 0, "serial": 1}
@@ -38,17 +39,19 @@ BP_METHOD = {"product": 0, "minsum": 1}
 # QEC_PATH_* bits of QEC_OPT_LAST_PATH (include/qec_ldpc.h): the launch sequence of the last decode call
 PATH = {"ordered": 1, "sector_order": 2, "split_waves": 4, "sector_launches": 8, "triage": 16, "bit_rows": 32,
         "sparse": 64, "records": 128, "osd": 256, "correlated": 512, "serial": 1024,
-        "minsum": 2048, "relay": 4096}
+        "minsum": 2048, "relay": 4096, "wave": 8192}
 
 # every symbol include/qec_ldpc.h declares
 EXPORTS = (
     "qec_last_error", "qec_abi_version", "qec_build_id",
     "qec_code_load", "qec_code_generate", "qec_code_from_matrices", "qec_code_degrees", "qec_code_layers",
+    "qec_code_has_wave_minsum",
     "qec_code_free",
     "qec_code_params", "qec_code_exponents",
     "qec_code_pcm", "qec_code_describe", "qec_code_syndrome", "qec_code_check_logical",
     "qec_code_with_logical", "qec_code_logical_mode", "qec_code_logical_rows", "qec_code_imp",
-    "qec_decoder_create", "qec_decoder_create_engine", "qec_decoder_create_multi", "qec_decoder_destroy",
+    "qec_decoder_create", "qec_decoder_create_engine", "qec_decoder_create_multi", "qec_decoder_create_multi_engine",
+    "qec_decoder_destroy",
     "qec_decoder_num_parts", "qec_decoder_part", "qec_decoder_device", "qec_decoder_describe",
     "qec_decoder_set_option", "qec_decoder_get_option", "qec_near_hard_threshold",
     "qec_decoder_set_priors", "qec_decoder_get_priors", "qec_decoder_get_osd_weights", "qec_sample_independent_dev",
@@ -131,6 +134,7 @@ def lib():
             "qec_code_from_matrices": (vp, [i, i, vp, i, vp]),
             "qec_code_degrees": (i, [vp, vp]),
             "qec_code_layers": (i, [vp, i, vp]),
+            "qec_code_has_wave_minsum": (i, [vp]),
             "qec_code_free": (i, [vp]),
             "qec_code_params": (i, [vp, vp]),
             "qec_code_exponents": (i, [vp, i, vp]),
@@ -145,6 +149,7 @@ def lib():
             "qec_decoder_create": (vp, [vp, i, sz]),
             "qec_decoder_create_engine": (vp, [vp, i, sz, i]),
             "qec_decoder_create_multi": (vp, [vp, vp, i, sz]),
+            "qec_decoder_create_multi_engine": (vp, [vp, vp, i, sz, i]),
             "qec_decoder_destroy": (i, [vp]),
             "qec_decoder_num_parts": (i, [vp]),
             "qec_decoder_part": (vp, [vp, i]),
@@ -218,6 +223,11 @@ def correlated_priors(p):
     c0, c1 = ctypes.c_float(0.0), ctypes.c_float(0.0)
     _check(lib().qec_correlated_priors(float(np.float32(p)), ctypes.byref(c0), ctypes.byref(c1)), "qec_correlated_priors")
     return np.float32(c0.value), np.float32(c1.value)
+
+
+def has_wave_minsum(code):
+    """qec_code_has_wave_minsum: whether a sparse-engine decoder of `code` takes set_option("minsum_wave", 1)."""
+    return code.has_wave_minsum()
 
 
 def minsum_llr(prior):
@@ -312,6 +322,14 @@ class Quantum_LDPC_Code:
         v = np.zeros(5, dtype=np.int32)
         _check(lib().qec_code_degrees(self._h, _ptr(v)), "qec_code_degrees")
         return tuple(int(x) for x in v)
+
+    def has_wave_minsum(self):
+        """Whether set_option("minsum_wave", 1) has kernels for this code (qec_code_has_wave_minsum): a
+        circulant-permutation code with P <= 64 and a block shape of the runtime-shift table.  A host query."""
+        r = lib().qec_code_has_wave_minsum(self._h)
+        if r < 0:
+            raise QecError("qec_code_has_wave_minsum failed: %s" % last_error())
+        return bool(r)
 
     def layers(self, sector):
         """The colour of every check of the sector under the serial BP schedule (qec_code_layers): int32
@@ -443,7 +461,8 @@ class DecoderGPU:
     "circulant" or "sparse" (include/qec_ldpc.h, QEC_ENGINE_*).
     max_batch: sizes the device-pointer workspace so the *_dev decodes allocate nothing for
     batches up to it (graph capture); larger batches grow it on demand.
-    devices: a list of HIP device ordinals for a multi-device decoder (qec_decoder_create_multi):
+    devices: a list of HIP device ordinals for a multi-device decoder (qec_decoder_create_multi_engine, every part
+    on `engine`):
     the host-buffer calls, GetStatistics and monte_carlo shard their samples over the devices;
     the *_dev calls go to one of parts()."""
 
@@ -454,7 +473,7 @@ class DecoderGPU:
             h = _handle
         elif devices is not None:
             devs = (ctypes.c_int * len(devices))(*[int(x) for x in devices])
-            h = lib().qec_decoder_create_multi(code.handle, devs, len(devices), int(max_batch))
+            h = lib().qec_decoder_create_multi_engine(code.handle, devs, len(devices), int(max_batch), ENGINE[engine])
         else:
             h = lib().qec_decoder_create_engine(code.handle, int(device), int(max_batch), ENGINE[engine])
         if not h:

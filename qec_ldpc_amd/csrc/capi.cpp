@@ -77,6 +77,9 @@ const char* sparse_plan_name(const void* plan);
 const int32_t* sparse_plan_chkvar(const void* plan);
 const int32_t* sparse_plan_varedge(const void* plan);
 int launch_decode_sparse(void* plan, const SparseDecode& d, hipStream_t stream);
+const void* select_wave_minsum(const Code& c);
+std::string wave_minsum_name(const Code& c);
+int launch_wave_minsum(const void* shape, const Code& c, const SparseDecode& d, hipStream_t stream);
 int launch_sample_pauli(uint64_t seed, uint64_t start, long long B, int n, const uint64_t* thr, uint8_t* x, uint8_t* z,
                         hipStream_t st);
 int launch_sample_independent(uint64_t seed, uint64_t start, long long B, int n, const float* prior, uint8_t* x,
@@ -179,6 +182,9 @@ struct qec_decoder {
     std::vector<float> mllr;
     DeviceArray<float> dmllr;
     int minsum() const { return bp_method == 1 ? minsum_scale : 0; }  // the engines' argument: 0, or the scale
+    // QEC_OPT_MINSUM_WAVE: a sparse-engine handle's plain min-sum decodes run the wave kernels (bp_wave_minsum.hip);
+    // data like minsum_scale, in effect while bp_method = 1 and no relay tables are set
+    int minsum_wave = 0;
     const float* llr_host() const { return has_priors ? mllr.data() : nullptr; }
     const float* llr_dev() const { return has_priors ? dmllr.data() : nullptr; }
     // qec_decoder_set_relay ("The relay form"): L legs of per-variable memory strengths, [leg][sector][n],
@@ -395,6 +401,12 @@ int qec_code_degrees(const qec_code* h, int* out)
     return QEC_OK;
 }
 
+int qec_code_has_wave_minsum(const qec_code* h)
+{
+    if (!h) return fail(QEC_ERR_ARG, "qec_code_has_wave_minsum: null code");
+    return select_wave_minsum(h->c) != nullptr ? 1 : 0;
+}
+
 int qec_code_layers(const qec_code* h, int sector, int32_t* colour)
 {
     if (!h || (sector != 0 && sector != 1)) return fail(QEC_ERR_ARG, "qec_code_layers: bad argument");
@@ -603,6 +615,16 @@ qec_decoder* qec_decoder_create_engine(const qec_code* h, int device, size_t max
 
 qec_decoder* qec_decoder_create_multi(const qec_code* h, const int* devices, int ndevices, size_t max_batch)
 {
+    return qec_decoder_create_multi_engine(h, devices, ndevices, max_batch, QEC_ENGINE_AUTO);
+}
+
+qec_decoder* qec_decoder_create_multi_engine(const qec_code* h, const int* devices, int ndevices, size_t max_batch,
+                                             int engine)
+{
+    if (engine == QEC_ENGINE_CPU) {
+        fail(QEC_ERR_ARG, "qec_decoder_create_multi_engine: a group is GPU-only (QEC_ENGINE_AUTO, _CIRCULANT or _SPARSE)");
+        return nullptr;
+    }
     if (!h || !devices || ndevices <= 0) { fail(QEC_ERR_ARG, "qec_decoder_create_multi: bad argument"); return nullptr; }
     for (int k = 0; k < ndevices; ++k)
         if (devices[k] < 0) {
@@ -615,7 +637,7 @@ qec_decoder* qec_decoder_create_multi(const qec_code* h, const int* devices, int
     std::unique_ptr<qec_decoder> g(new (std::nothrow) qec_decoder);
     if (!g) { fail(QEC_ERR_NOMEM, "qec_decoder_create_multi: out of memory"); return nullptr; }
     for (int k = 0; k < ndevices; ++k) {
-        qec_decoder* p = qec_decoder_create(h, devices[k], max_batch);
+        qec_decoder* p = qec_decoder_create_engine(h, devices[k], max_batch, engine);
         if (!p) return nullptr;  // parts created so far are freed with g
         g->parts.push_back(p);
     }
@@ -664,7 +686,10 @@ int qec_decoder_destroy(qec_decoder* d)
 int qec_decoder_describe(const qec_decoder* d, char* buf, size_t len)
 {
     if (!d || !buf || !len) return fail(QEC_ERR_ARG, "qec_decoder_describe: bad argument");
-    std::snprintf(buf, len, "%s", d->variant_name.c_str());
+    if (d->minsum_wave)  // the kernels of the handle's plain min-sum decodes
+        std::snprintf(buf, len, "%s [min-sum: %s]", d->variant_name.c_str(), wave_minsum_name(*d->code).c_str());
+    else
+        std::snprintf(buf, len, "%s", d->variant_name.c_str());
     return QEC_OK;
 }
 
@@ -793,6 +818,27 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
         if (value < 1 || value > 256)
             return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_MINSUM_SCALE is 1 .. 256 (alpha = value / 256)");
         d->minsum_scale = value;
+        return QEC_OK;
+    case QEC_OPT_MINSUM_WAVE:
+        if (value != 0 && value != 1)
+            return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_MINSUM_WAVE is 0 (the sparse-graph kernels) or 1 (the "
+                                     "wave kernels)");
+        if (value && d->parts.empty()) {
+            if (d->cpu)
+                return fail(QEC_ERR_UNSUPPORTED,
+                            "qec_decoder_set_option: QEC_OPT_MINSUM_WAVE = 1 chooses GPU kernels; the CPU engine has one "
+                            "min-sum implementation");
+            if (d->engine != QEC_ENGINE_SPARSE)
+                return fail(QEC_ERR_UNSUPPORTED,
+                            "qec_decoder_set_option: QEC_OPT_MINSUM_WAVE = 1 is a kernel choice of a sparse-engine handle, "
+                            "which alone decodes by min-sum; create the decoder with QEC_ENGINE_SPARSE (engine \"sparse\")");
+            if (!select_wave_minsum(*d->code))
+                return fail(QEC_ERR_UNSUPPORTED,
+                            "qec_decoder_set_option: QEC_OPT_MINSUM_WAVE = 1: no wave min-sum kernel for this code (" +
+                                d->code->describe() + "): needs circulant-permutation blocks, P <= 64 and a block shape "
+                                "(J,K,L) of the runtime-shift table");
+        }
+        d->minsum_wave = value;
         return QEC_OK;
     case QEC_OPT_OSD_CS_SECTORS:
         return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD_CS_SECTORS is read only");
@@ -1111,6 +1157,7 @@ int qec_decoder_get_option(const qec_decoder* d, int option, int* value)
     case QEC_OPT_BP_SCHEDULE: *value = d->bp_schedule; return QEC_OK;
     case QEC_OPT_BP_METHOD: *value = d->bp_method; return QEC_OK;
     case QEC_OPT_MINSUM_SCALE: *value = d->minsum_scale; return QEC_OK;
+    case QEC_OPT_MINSUM_WAVE: *value = d->minsum_wave; return QEC_OK;
     case QEC_OPT_OSD_CS_SECTORS: {
         unsigned long long t = d->osd_cs_sectors;
         for (const qec_decoder* p : d->parts) t += p->osd_cs_sectors;
@@ -1213,7 +1260,13 @@ int dispatch_decode(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, long l
                 d->last_path |= QEC_PATH_RELAY;
             }
         }
-        rc = launch_decode_sparse(d->sparse, sd, st);
+        // QEC_OPT_MINSUM_WAVE, read at the call: plain min-sum in the wave layout (set_option has checked the code)
+        if (sd.minsum && sd.gamma == nullptr && d->minsum_wave) {
+            d->last_path |= QEC_PATH_WAVE;
+            rc = launch_wave_minsum(select_wave_minsum(c), c, sd, st);
+        } else {
+            rc = launch_decode_sparse(d->sparse, sd, st);
+        }
         if (!rc && rec != nullptr) rc = launch_pack_decisions(eX, eZ, flags, B, c.n, rec, st);
         if (rc) return rc;
         return ws_release(d, st);

@@ -43,6 +43,9 @@
 //                      in the LLR domain.  Sparse-graph and CPU engines; not with --correlated or --bp-schedule serial
 //   --minsum-scale K   min-sum's factor alpha = K / 256 (QEC_OPT_MINSUM_SCALE, 1 .. 256, default 160); needs
 //                      --bp-method minsum
+//   --minsum-wave 0|1  the kernels of plain min-sum decodes (QEC_OPT_MINSUM_WAVE): 1 = the register-resident wave
+//                      kernels (circulant codes, P <= 64, a block shape of the runtime-shift table); needs
+//                      --engine sparse and --bp-method minsum
 //   --relay FILE       Relay-BP (qec_decoder_set_relay): FILE holds 2 L lines of n decimal floats, the memory strengths
 //                      of the L legs of sector X, then of the L legs of sector Z (each |gamma| <= 1); needs
 //                      --bp-method minsum
@@ -99,7 +102,7 @@ int usage(const std::string& why)
               << "usage: qec_ldpc [--engine gpu|sparse|cpu] [--gpus N | --devices i,j,...] [--rng msvc|philox]"
                  " [--stop ref|fixed|syndrome] [--batch B] [--seed S] [--logical file|reference|degenerate]"
                  " [--osd 0 [--osd-order L] [--osd-iterations K] [--osd-score hamming|priors]] [--priors FILE]"
-                 " [--correlated xz|zx] [--bp-schedule flooding|serial] [--bp-method product|minsum [--minsum-scale K]"
+                 " [--correlated xz|zx] [--bp-schedule flooding|serial] [--bp-method product|minsum [--minsum-scale K] [--minsum-wave 0|1]"
                  " [--relay FILE [--relay-solutions S]]] [--pauli FILE] initFile"
               << std::endl;
     return 2;
@@ -180,6 +183,7 @@ int main(int argc, char** argv)
     bool relaySolutionsFlag = false;
     int correlated = 0, bpSchedule = 0, bpMethod = 0, minsumScale = 160;
     bool minsumScaleFlag = false;
+    int minsumWave = 0;
     bool deviceFlag = false, stopFlag = false, batchFlag = false, seedFlag = false, osd = false, osdIterFlag = false;
     bool osdOrderFlag = false, osdScoreFlag = false;
     int osdScore = 0;
@@ -253,6 +257,9 @@ int main(int argc, char** argv)
                 minsumScale = std::stoi(val);
                 if (minsumScale < 1 || minsumScale > 256) return usage("--minsum-scale: 1 .. 256");
                 minsumScaleFlag = true;
+            } else if (flag == "--minsum-wave") {
+                if (val != "0" && val != "1") return usage("--minsum-wave: 0 or 1");
+                minsumWave = val == "1" ? 1 : 0;
             } else if (flag == "--relay") {
                 relayFile = val;
             } else if (flag == "--relay-solutions") {
@@ -279,6 +286,7 @@ int main(int argc, char** argv)
     if (osdScoreFlag && !osd) return usage("--osd-score needs --osd 0");
     if (bpSchedule && correlated) return usage("--bp-schedule serial and --correlated exclude each other");
     if (minsumScaleFlag && !bpMethod) return usage("--minsum-scale needs --bp-method minsum");
+    if (minsumWave && (!bpMethod || engine != "sparse")) return usage("--minsum-wave 1 needs --engine sparse and --bp-method minsum");
     if (bpMethod && correlated) return usage("--bp-method minsum and --correlated exclude each other");
     if (bpMethod && bpSchedule) return usage("--bp-method minsum and --bp-schedule serial exclude each other");
     if (!relayFile.empty() && !bpMethod) return usage("--relay needs --bp-method minsum");
@@ -332,6 +340,7 @@ int main(int argc, char** argv)
             if (correlated) decoder.SetCorrelated(correlated);
             if (bpSchedule) decoder.SetBpSchedule(bpSchedule);
             if (bpMethod) decoder.SetBpMethod(bpMethod, minsumScale);
+            if (minsumWave) decoder.SetMinSumWave(minsumWave);
             if (relayLegs) decoder.SetRelay(gammaX, gammaZ, relayLegs, relaySolutions);
             std::cout << "Engine: " << decoder.Describe() << std::endl;
             const int stop = stopName == "ref" ? QEC_STOP_REF : stopName == "fixed" ? QEC_STOP_FIXED : QEC_STOP_SYNDROME;
@@ -373,6 +382,7 @@ int main(int argc, char** argv)
             if (correlated) g->SetCorrelated(correlated);
             if (bpSchedule) g->SetBpSchedule(bpSchedule);
             if (bpMethod) g->SetBpMethod(bpMethod, minsumScale);
+            if (minsumWave) g->SetMinSumWave(minsumWave);
             if (relayLegs) g->SetRelay(gammaX, gammaZ, relayLegs, relaySolutions);
             std::cout << "Engine: " << g->Describe() << std::endl;
         }
