@@ -1346,7 +1346,6 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
                                               uint32_t sbits, const float* __restrict__ tab0, uint32_t& flags,
                                               int& iters_out, uint8_t* __restrict__ stage)
 {
-    const int i = ln.i;
     const int P = SH::P(a);
 
     // Zero syndrome under the syndrome stop rule (most sectors at low p: P61 at p = 0.002, 44 %):
@@ -1382,16 +1381,20 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
             return;
         }
     }
-    // InitVarNodes: every edge starts at p' (DecoderCPU.h:135-148, 265-267)
+    // InitVarNodes: every edge starts at p' (DecoderCPU.h:135-148, 265-267).  Only when iteration 0 is not
+    // made by table (N < 2, wave-uniform): the table writes every register of every lane (below), so with it
+    // the R L moves of this fill would be dead at the head of every wave.
     float msg[R][L];
+    const int N = a.maxIter;
+    if (N < 2) {
 #pragma unroll
-    for (int r = 0; r < R; ++r)
+        for (int r = 0; r < R; ++r)
 #pragma unroll
-        for (int l = 0; l < L; ++l) msg[r][l] = pp;
+            for (int l = 0; l < L; ++l) msg[r][l] = pp;
+    }
 
     const float one_minus_pp = 1.0f - pp;
     bool hard = false;  // the initial messages p' are not hard (0 < p' < 1 is required anyway)
-    const int N = a.maxIter;
     bool active = in_range;  // group-uniform
     int it = 0;
     int n = 0;
@@ -1403,6 +1406,9 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
     bool agreed = false, vagree = false;
     // near-hard jump: this iteration's new state meets C(eps0) (iteration)
     bool near = false;
+    // near_done: this group left through the near-hard jump; its registers hold the soft state that met
+    // C(eps0), not a hard one (group-uniform)
+    bool near_done = false;
     int ph_soft = 0, ph_hard = 0, ph_agree = 0, ph_jump = 0;  // QEC_PHASE_STATS
     // syndrome stop rule: the hard decision of the last executed iteration and its syndrome test
     // (hd_valid: the current state is that iteration's output, i.e. not reached by a cycle jump).
@@ -1416,13 +1422,26 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
     bool cv0 = true, msg_built = true;
     unsigned long long hdpat = 0, cvpat = 0;
     if constexpr (STOP == QEC_STOP_SYNDROME && !GO) pattern_masks<R>(tab0, hdpat, cvpat);
-    if (N >= 2 && active) {  // iteration 0 by table (see iteration0)
-        ++it;
-        syn_last = iteration0<R, L, SEC, STOP, SH, GO>(a, msg, sbits, ln, tab0, hd_last, cv0, msg_built, hdpat, cvpat);
-        hd_valid = true;
-        if (STOP == QEC_STOP_SYNDROME && !GO) seen[0] = hd_last;  // tested (a group going on failed it)
-        if (syn_last) active = false;
-        if constexpr (QEC_PHASE_STATS) ph_soft += 1;
+    if (N >= 2) {  // iteration 0 by table (see iteration0)
+        // On every lane of the wave, in range or not, so that the condition is wave-uniform and the table,
+        // not the fill above, defines every lane's registers.  A lane outside the batch has sbits = 0: it
+        // gathers within its own group (multi-group waves) or from in-bounds lanes, and reads pattern-0
+        // entries.  The idle lanes [0, kGroupBase) of a one-group wave with pushed rotations now push too, and
+        // still lose every collision: each group lane is the destination of exactly one group lane's push (the
+        // group's pushes are a bijection on it), that source is numbered above every idle lane, and the
+        // highest-numbered source wins (rotations by push, above).  What the idle lanes
+        // receive is never stored.  it, active and the stop bookkeeping stay per group.
+        uint32_t hd0 = 0;
+        const bool stop0 = iteration0<R, L, SEC, STOP, SH, GO>(a, msg, sbits, ln, tab0, hd0, cv0, msg_built, hdpat, cvpat);
+        if (active) {
+            ++it;
+            syn_last = stop0;
+            hd_last = hd0;
+            hd_valid = true;
+            if (STOP == QEC_STOP_SYNDROME && !GO) seen[0] = hd_last;  // tested (a group going on failed it)
+            if (syn_last) active = false;
+            if constexpr (QEC_PHASE_STATS) ph_soft += 1;
+        }
         n = 1;
     }
     // iterations n .. N-2 (DecoderCPU.h:280-291); the last one is peeled below
@@ -1453,16 +1472,20 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
                 // near-hard jump: C(eps0) holds from here on with this state's h, so
                 // the final decisions are h, both flags are clear and the sector ends where cycle_end puts it
                 // (under the reference stop a state tested at this n has already stopped: active is clear).
-                // The registers take h itself (+0 / 1.0 by each message's side of 0.5): a hard state whose
-                // variables agree and whose checks hold, which the agreeing-state post-processing below reads
-                // to exactly those outputs (the messages are not an output of such a launch).
+                // The registers keep the soft near-hard state (the messages are not an output of such a launch)
+                // and the group is marked near_done, not st_agreed: the agreeing-state post-processing XORs bit
+                // patterns and is only right on exactly +0 / 1.0 registers (st_agreed stays var_pass's vagree,
+                // which is about these very registers).
                 if constexpr (STOP != QEC_STOP_SYNDROME) {
                     if (near && active) {
+                        near_done = true;
+                        // (laundered: no instruction, but the registers' live ranges end here as they did when
+                        // this block rewrote them; as one range from the loop into the post-processing the P61 X
+                        // sector kernels spilled 36-40 B at 80 VGPRs)
 #pragma unroll
                         for (int r = 0; r < R; ++r)
 #pragma unroll
-                            for (int l = 0; l < L; ++l) msg[r][l] = msg[r][l] >= 0.5f ? 1.0f : 0.0f;
-                        st_agreed = true;
+                            for (int l = 0; l < L; ++l) asm volatile("" : "+v"(msg[r][l]));
                         const int last = cycle_end<STOP>(n, N);
                         it += last - n;
                         if constexpr (QEC_PHASE_STATS) ph_jump = last - n;
@@ -1488,7 +1511,21 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
     const int* et = SH::template table<SEC>(a);
     bool conv, syn_ok;
     uint32_t hdmask = 0;  // e[v] of this lane's variables (l, (i + C[l]) mod P), bit l
-    if (STOP == QEC_STOP_SYNDROME && all_live(hd_valid, in_range)) {
+    if (STOP != QEC_STOP_SYNDROME && TU::kSaturate && all_live(near_done, in_range)) {
+        // Every live group left through the near-hard jump: its registers meet C(eps0)
+        // with H h = s (var_pass's near and lane_parity_ok, which also excludes an entry other than 0 / 1), and
+        // by the lemma so does the state after iteration N - 1, with the same h.  Every message of a variable
+        // lies on h_v's side of 0.5, so "some message >= 0.5" is row 0's side (rotation S[0][l], 0 with the
+        // relabelling); the syndrome of h is s; eps0 <= 2^-8 < 0.01 puts every message outside (0.01, 0.99).
+        // A wave that also holds groups that stopped another way takes the general branch below, which gives a
+        // near-exited group these same three results from its soft registers (never the agreeing branch, unless
+        // that state is itself hard and agreeing: st_agreed is var_pass's word on it).
+#pragma unroll
+        for (int l = 0; l < L; ++l)
+            hdmask |= (uint32_t)(rot<SH>(msg[0][l], ln, SH::template shift<SEC, L>(et, 0, l)) >= 0.5f) << l;
+        conv = true;
+        syn_ok = true;
+    } else if (STOP == QEC_STOP_SYNDROME && all_live(hd_valid, in_range)) {
         // the last iteration's hard decision and syndrome test are the post-processing's
         conv = group_all_sh<SH>(__any(in_range && msg_built) ? lane_converged<R, L>(msg) : cv0, ln, P);
         hdmask = hd_last;
@@ -1534,6 +1571,7 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
     iters_out = QEC_PHASE_STATS ? (ph_soft | ph_hard << 8 | ph_agree << 16 | ph_jump << 24) : it;
 
     if (a.q != nullptr && in_range) {
+        const int i = lane_i<SH>(ln);  // recomputed (see lane_i): not held across the sector for this store alone
         const long long qb = b * (long long)(a.mX + a.mZ) * L + (SEC ? (long long)a.mX * L : 0);
 #pragma unroll
         for (int r = 0; r < R; ++r)
