@@ -7,7 +7,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-f
 CSRC     := qec_ldpc_amd/csrc
 OBJ      := build/obj
 LIB      := qec_ldpc_amd/libqecldpc.so
-OBJS     := $(OBJ)/bp_decode.o $(OBJ)/bp_decode_p61.o $(OBJ)/bp_decode_phase.o $(OBJ)/bp_sparse.o $(OBJ)/bp_wave_minsum.o $(OBJ)/schedule.o $(OBJ)/triage.o $(OBJ)/montecarlo.o $(OBJ)/code_model.o $(OBJ)/cpu_engine.o $(OBJ)/osd.o $(OBJ)/osd_host.o $(OBJ)/capi.o
+OBJS     := $(OBJ)/bp_decode.o $(OBJ)/bp_decode_p61.o $(OBJ)/bp_decode_phase.o $(OBJ)/bp_sparse.o $(OBJ)/bp_wave_minsum.o $(OBJ)/bp_wave_relay.o $(OBJ)/schedule.o $(OBJ)/triage.o $(OBJ)/montecarlo.o $(OBJ)/code_model.o $(OBJ)/cpu_engine.o $(OBJ)/osd.o $(OBJ)/osd_host.o $(OBJ)/capi.o
 HDRS     := include/qec_ldpc.h include/HostDeviceArray.h $(CSRC)/qec_internal.h $(CSRC)/qec_device.h $(CSRC)/qec_mc.h $(CSRC)/qec_launch.h $(CSRC)/qec_osd.h $(CSRC)/qec_near.h
 # build id: hash of every library source and this Makefile (identical for every rebuild of one tree);
 # profiles/pmc_*.json carry it and bench.py uses a profile only with the library it was taken on
@@ -34,6 +34,9 @@ $(OBJ)/bp_sparse.o: $(CSRC)/bp_sparse.hip $(HDRS) | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(OBJ)/bp_wave_minsum.o: $(CSRC)/bp_wave_minsum.hip $(HDRS) | $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(OBJ)/bp_wave_relay.o: $(CSRC)/bp_wave_relay.hip $(HDRS) | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(OBJ)/schedule.o: $(CSRC)/schedule.hip $(HDRS) | $(OBJ)

@@ -181,6 +181,11 @@ public:
     // runtime-shift table (qec_code_has_wave_minsum).  A kernel choice of a sparse-engine decoder: 1 on any other
     // decoder or code throws the library's message.  In effect while SetBpMethod(1) is and no relay is set.
     void SetMinSumWave(int on) { check(qec_decoder_set_option(dec_, QEC_OPT_MINSUM_WAVE, on)); }
+    // The kernels of relay decodes (QEC_OPT_RELAY_WAVE): 0 = the sparse-graph RELAY kernels (the default), 1 = the
+    // register-resident wave relay kernels, bit-identical, for the codes of SetMinSumWave.  Independent of
+    // SetMinSumWave; in effect while SetBpMethod(1) is and a relay is set.  1 on any other decoder or code throws the
+    // library's message.
+    void SetRelayWave(int on) { check(qec_decoder_set_option(dec_, QEC_OPT_RELAY_WAVE, on)); }
     // Relay-BP (qec_decoder_set_relay): `legs` legs of memory min-sum under SetBpMethod(1), gammaX / gammaZ the memory
     // strengths [legs][n] (|gamma| <= 1), stopping at the first solution or at the lightest of the first `solutions`.
     // The sparse-graph engine takes them; a wave-circulant decoder throws the library's message.

@@ -398,13 +398,26 @@ int qec_decoder_device(const qec_decoder* dec);         /* HIP device ordinal (o
  *     QEC_PATH_WAVE is set in QEC_OPT_LAST_PATH exactly when the wave kernels ran.  The _dev entry points read it at
  *     the call and allocate nothing.  1 is refused with QEC_ERR_UNSUPPORTED (the handle stays as it was, the text
  *     names the reason) on a sparse handle whose code has no wave min-sum kernel (qec_code_has_wave_minsum), on a
- *     wave-circulant handle and on a CPU handle.  A group applies the value to every part. */
+ *     wave-circulant handle and on a CPU handle.  A group applies the value to every part.
+ *   QEC_OPT_RELAY_WAVE (default 0; 0 or 1, other values QEC_ERR_ARG): a kernel choice of a sparse-engine handle,
+ *     independent of QEC_OPT_MINSUM_WAVE.  1 = the handle's relay decodes (qec_decoder_set_relay) run the
+ *     register-resident wave kernels (bp_wave_relay.hip; DESIGN.md section 2, "The relay form in the wave layout"):
+ *     one wave per G = 64 / P syndrome pairs, a sector's messages, memories and best solution in registers, each
+ *     group of the wave in a leg of its own, the same rule in the same evaluation order, so every output (estimates,
+ *     flags, iteration counts, q_final) is the RELAY kernels' bit for bit, with the scalar p or with the handle's
+ *     priors.  The value is data: it takes effect in every decode while QEC_OPT_BP_METHOD = 1 and relay tables are
+ *     set; without tables or under the product rule it does nothing (plain min-sum follows QEC_OPT_MINSUM_WAVE, and so
+ *     does the OSD stage's soft decode).  QEC_PATH_WAVE is then set beside QEC_PATH_RELAY in QEC_OPT_LAST_PATH; with
+ *     the option at 0 a relay decode never sets it.  The _dev entry points read it at the call and allocate nothing.
+ *     1 is refused with QEC_ERR_UNSUPPORTED (the handle stays as it was, the text names the reason) on a sparse
+ *     handle whose code has no wave kernel (qec_code_has_wave_minsum answers for both options), on a wave-circulant
+ *     handle and on a CPU handle.  A group applies the value to every part. */
 enum { QEC_OPT_HARD_PATHS = 1, QEC_OPT_CYCLE_JUMP = 2, QEC_OPT_SCHEDULE = 3, QEC_OPT_SECTOR_SPLIT = 4,
        QEC_OPT_PHASE_STATS = 5, QEC_OPT_TRIAGE = 6, QEC_OPT_LAST_PATH = 7, QEC_OPT_MC_DECODE_TIME = 8,
        QEC_OPT_OSD = 9, QEC_OPT_OSD_ITERATIONS = 10, QEC_OPT_OSD_SECTORS = 11, QEC_OPT_OSD_SWEEP = 12,
        QEC_OPT_OSD_ORDER = 13, QEC_OPT_OSD_CS_SECTORS = 14, QEC_OPT_NEAR_HARD_JUMP = 15, QEC_OPT_OSD_SCORE = 16,
        QEC_OPT_CORRELATED = 17, QEC_OPT_BP_SCHEDULE = 18, QEC_OPT_BP_METHOD = 19, QEC_OPT_MINSUM_SCALE = 20,
-       QEC_OPT_MINSUM_WAVE = 21 };
+       QEC_OPT_MINSUM_WAVE = 21, QEC_OPT_RELAY_WAVE = 22 };
 enum {
     QEC_PATH_ORDERED = 1,          /* dispatch order pass (schedule.hip) */
     QEC_PATH_SECTOR_ORDER = 2,     /* ... in the per-sector form (each sector's waves by its own weight) */
@@ -419,7 +432,8 @@ enum {
     QEC_PATH_SERIAL = 1024,        /* BP under the serial schedule (QEC_OPT_BP_SCHEDULE = 1) */
     QEC_PATH_MINSUM = 2048,        /* scaled min-sum BP (QEC_OPT_BP_METHOD = 1) */
     QEC_PATH_RELAY = 4096,         /* ... as a relay of memory min-sum legs (qec_decoder_set_relay) */
-    QEC_PATH_WAVE = 8192           /* ... by the register-resident wave kernels (QEC_OPT_MINSUM_WAVE = 1) */
+    QEC_PATH_WAVE = 8192           /* ... by the register-resident wave kernels (QEC_OPT_MINSUM_WAVE = 1, or
+                                      QEC_OPT_RELAY_WAVE = 1 on a relay decode) */
 };
 /* The near-hard jump's threshold for p' = pPrime (the float (2/3) errorProbability the decoder forms), R
  * checks per variable and L variables per check: *eps0 = the largest power of two in [2^-20, 2^-8] with

@@ -80,6 +80,10 @@ int launch_decode_sparse(void* plan, const SparseDecode& d, hipStream_t stream);
 const void* select_wave_minsum(const Code& c);
 std::string wave_minsum_name(const Code& c);
 int launch_wave_minsum(const void* shape, const Code& c, const SparseDecode& d, hipStream_t stream);
+// bp_wave_relay.hip
+const void* select_wave_relay(const Code& c);
+std::string wave_relay_name(const Code& c);
+int launch_wave_relay(const void* shape, const Code& c, const SparseDecode& d, hipStream_t stream);
 int launch_sample_pauli(uint64_t seed, uint64_t start, long long B, int n, const uint64_t* thr, uint8_t* x, uint8_t* z,
                         hipStream_t st);
 int launch_sample_independent(uint64_t seed, uint64_t start, long long B, int n, const float* prior, uint8_t* x,
@@ -185,6 +189,9 @@ struct qec_decoder {
     // QEC_OPT_MINSUM_WAVE: a sparse-engine handle's plain min-sum decodes run the wave kernels (bp_wave_minsum.hip);
     // data like minsum_scale, in effect while bp_method = 1 and no relay tables are set
     int minsum_wave = 0;
+    // QEC_OPT_RELAY_WAVE: a sparse-engine handle's relay decodes run the wave kernels (bp_wave_relay.hip); data like
+    // minsum_wave, in effect while bp_method = 1 and relay tables are set, whatever minsum_wave says
+    int relay_wave = 0;
     const float* llr_host() const { return has_priors ? mllr.data() : nullptr; }
     const float* llr_dev() const { return has_priors ? dmllr.data() : nullptr; }
     // qec_decoder_set_relay ("The relay form"): L legs of per-variable memory strengths, [leg][sector][n],
@@ -686,10 +693,12 @@ int qec_decoder_destroy(qec_decoder* d)
 int qec_decoder_describe(const qec_decoder* d, char* buf, size_t len)
 {
     if (!d || !buf || !len) return fail(QEC_ERR_ARG, "qec_decoder_describe: bad argument");
+    std::string text = d->variant_name;
     if (d->minsum_wave)  // the kernels of the handle's plain min-sum decodes
-        std::snprintf(buf, len, "%s [min-sum: %s]", d->variant_name.c_str(), wave_minsum_name(*d->code).c_str());
-    else
-        std::snprintf(buf, len, "%s", d->variant_name.c_str());
+        text += " [min-sum: " + wave_minsum_name(*d->code) + "]";
+    if (d->relay_wave)   // ... and of its relay decodes
+        text += " [relay: " + wave_relay_name(*d->code) + "]";
+    std::snprintf(buf, len, "%s", text.c_str());
     return QEC_OK;
 }
 
@@ -839,6 +848,27 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
                                 "(J,K,L) of the runtime-shift table");
         }
         d->minsum_wave = value;
+        return QEC_OK;
+    case QEC_OPT_RELAY_WAVE:
+        if (value != 0 && value != 1)
+            return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_RELAY_WAVE is 0 (the sparse-graph kernels) or 1 (the "
+                                     "wave kernels)");
+        if (value && d->parts.empty()) {
+            if (d->cpu)
+                return fail(QEC_ERR_UNSUPPORTED,
+                            "qec_decoder_set_option: QEC_OPT_RELAY_WAVE = 1 chooses GPU kernels; the CPU engine has one "
+                            "relay implementation");
+            if (d->engine != QEC_ENGINE_SPARSE)
+                return fail(QEC_ERR_UNSUPPORTED,
+                            "qec_decoder_set_option: QEC_OPT_RELAY_WAVE = 1 is a kernel choice of a sparse-engine handle, "
+                            "which alone runs the relay; create the decoder with QEC_ENGINE_SPARSE (engine \"sparse\")");
+            if (!select_wave_relay(*d->code))
+                return fail(QEC_ERR_UNSUPPORTED,
+                            "qec_decoder_set_option: QEC_OPT_RELAY_WAVE = 1: no wave relay kernel for this code (" +
+                                d->code->describe() + "): needs circulant-permutation blocks, P <= 64 and a block shape "
+                                "(J,K,L) of the runtime-shift table");
+        }
+        d->relay_wave = value;
         return QEC_OK;
     case QEC_OPT_OSD_CS_SECTORS:
         return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD_CS_SECTORS is read only");
@@ -1158,6 +1188,7 @@ int qec_decoder_get_option(const qec_decoder* d, int option, int* value)
     case QEC_OPT_BP_METHOD: *value = d->bp_method; return QEC_OK;
     case QEC_OPT_MINSUM_SCALE: *value = d->minsum_scale; return QEC_OK;
     case QEC_OPT_MINSUM_WAVE: *value = d->minsum_wave; return QEC_OK;
+    case QEC_OPT_RELAY_WAVE: *value = d->relay_wave; return QEC_OK;
     case QEC_OPT_OSD_CS_SECTORS: {
         unsigned long long t = d->osd_cs_sectors;
         for (const qec_decoder* p : d->parts) t += p->osd_cs_sectors;
@@ -1264,6 +1295,10 @@ int dispatch_decode(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, long l
         if (sd.minsum && sd.gamma == nullptr && d->minsum_wave) {
             d->last_path |= QEC_PATH_WAVE;
             rc = launch_wave_minsum(select_wave_minsum(c), c, sd, st);
+        } else if (sd.minsum && sd.gamma != nullptr && d->relay_wave) {
+            // QEC_OPT_RELAY_WAVE, read at the call: the relay in the wave layout (set_option has checked the code)
+            d->last_path |= QEC_PATH_WAVE;
+            rc = launch_wave_relay(select_wave_relay(c), c, sd, st);
         } else {
             rc = launch_decode_sparse(d->sparse, sd, st);
         }

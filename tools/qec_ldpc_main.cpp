@@ -50,6 +50,8 @@
 //                      of the L legs of sector X, then of the L legs of sector Z (each |gamma| <= 1); needs
 //                      --bp-method minsum
 //   --relay-solutions S   the relay stops at the lightest of its first S solutions (1 .. 64, default 1); needs --relay
+//   --relay-wave 0|1   the kernels of relay decodes (QEC_OPT_RELAY_WAVE): 1 = the register-resident wave relay kernels
+//                      (the codes of --minsum-wave); needs --engine sparse, --bp-method minsum and --relay FILE
 //   --pauli FILE       per-qubit Pauli channel (qec_decoder_set_pauli_channel): FILE holds three lines of n decimal
 //                      floats, pX, pY and pZ.  BP decodes under its marginals (and --correlated under its conditional
 //                      tables), the init file's p is not used, and --rng philox draws its errors from the channel.
@@ -103,7 +105,7 @@ int usage(const std::string& why)
                  " [--stop ref|fixed|syndrome] [--batch B] [--seed S] [--logical file|reference|degenerate]"
                  " [--osd 0 [--osd-order L] [--osd-iterations K] [--osd-score hamming|priors]] [--priors FILE]"
                  " [--correlated xz|zx] [--bp-schedule flooding|serial] [--bp-method product|minsum [--minsum-scale K] [--minsum-wave 0|1]"
-                 " [--relay FILE [--relay-solutions S]]] [--pauli FILE] initFile"
+                 " [--relay FILE [--relay-solutions S] [--relay-wave 0|1]]] [--pauli FILE] initFile"
               << std::endl;
     return 2;
 }
@@ -183,7 +185,8 @@ int main(int argc, char** argv)
     bool relaySolutionsFlag = false;
     int correlated = 0, bpSchedule = 0, bpMethod = 0, minsumScale = 160;
     bool minsumScaleFlag = false;
-    int minsumWave = 0;
+    int minsumWave = 0, relayWave = 0;
+    bool relayWaveFlag = false;
     bool deviceFlag = false, stopFlag = false, batchFlag = false, seedFlag = false, osd = false, osdIterFlag = false;
     bool osdOrderFlag = false, osdScoreFlag = false;
     int osdScore = 0;
@@ -260,6 +263,10 @@ int main(int argc, char** argv)
             } else if (flag == "--minsum-wave") {
                 if (val != "0" && val != "1") return usage("--minsum-wave: 0 or 1");
                 minsumWave = val == "1" ? 1 : 0;
+            } else if (flag == "--relay-wave") {
+                if (val != "0" && val != "1") return usage("--relay-wave: 0 or 1");
+                relayWave = val == "1" ? 1 : 0;
+                relayWaveFlag = true;
             } else if (flag == "--relay") {
                 relayFile = val;
             } else if (flag == "--relay-solutions") {
@@ -291,6 +298,8 @@ int main(int argc, char** argv)
     if (bpMethod && bpSchedule) return usage("--bp-method minsum and --bp-schedule serial exclude each other");
     if (!relayFile.empty() && !bpMethod) return usage("--relay needs --bp-method minsum");
     if (relaySolutionsFlag && relayFile.empty()) return usage("--relay-solutions needs --relay FILE");
+    if (relayWaveFlag && (!bpMethod || engine != "sparse" || relayFile.empty()))
+        return usage("--relay-wave needs --engine sparse, --bp-method minsum and --relay FILE");
     if (!pauliFile.empty() && !priorsFile.empty()) return usage("--pauli and --priors exclude each other");
     if (osdScore == 1 && priorsFile.empty()) return usage("--osd-score priors needs --priors FILE");
     if (argc - a != 1 || devices.empty()) {
@@ -342,6 +351,7 @@ int main(int argc, char** argv)
             if (bpMethod) decoder.SetBpMethod(bpMethod, minsumScale);
             if (minsumWave) decoder.SetMinSumWave(minsumWave);
             if (relayLegs) decoder.SetRelay(gammaX, gammaZ, relayLegs, relaySolutions);
+            if (relayWave) decoder.SetRelayWave(relayWave);
             std::cout << "Engine: " << decoder.Describe() << std::endl;
             const int stop = stopName == "ref" ? QEC_STOP_REF : stopName == "fixed" ? QEC_STOP_FIXED : QEC_STOP_SYNDROME;
             std::stringstream fileName;
@@ -384,6 +394,7 @@ int main(int argc, char** argv)
             if (bpMethod) g->SetBpMethod(bpMethod, minsumScale);
             if (minsumWave) g->SetMinSumWave(minsumWave);
             if (relayLegs) g->SetRelay(gammaX, gammaZ, relayLegs, relaySolutions);
+            if (relayWave) g->SetRelayWave(relayWave);
             std::cout << "Engine: " << g->Describe() << std::endl;
         }
         for (; w <= W; ++w) {
