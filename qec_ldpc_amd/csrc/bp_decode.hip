@@ -42,6 +42,7 @@
 #include "qec_internal.h"
 #include "qec_launch.h"
 #include "qec_near.h"
+#include "qec_wave.h"
 
 #pragma clang fp contract(off)
 
@@ -80,7 +81,7 @@ struct Tune {
     static constexpr bool kMaskSelect = MASKSEL_;  // rotation base chosen by a constant lane mask (rot_addr)
     static constexpr int kPipeline = PIPE_;  // D: the gathers of the next D columns in flight during a column
     static constexpr bool kSplit = SPLIT_;  // QEC_OPT_SECTOR_SPLIT = 1 (auto) splits sectors for this variant
-    static constexpr bool kRelabel = RELABEL_;  // spanning-tree lane relabelling (relabel below)
+    static constexpr bool kRelabel = RELABEL_;  // spanning-tree lane relabelling (relabel, qec_wave.h)
     static constexpr bool kZeroSkip = ZEROSKIP_;  // a column of +0 numerators skips its divisions
     static constexpr bool kFastDiv = FASTDIV_;  // the short division (div_short)
     static constexpr bool kSaturate = SATURATE_;  // the hard-message forms (check_pass_hard, var_pass)
@@ -210,7 +211,7 @@ struct BpArgs {
     // near-hard jump (qec_near.h), per sector: the compare value T of this launch's
     // eps0; 0 = off (option off, final messages requested, syndrome stop, or no eps0 for this p')
     uint32_t nearT[2];
-    // lane-relabelled circulant tables (see relabel() below)
+    // lane-relabelled circulant tables (relabel(), qec_wave.h)
     // iteration-0 tables of both sectors computed on the host (launch_decode: the same operations,
     // so the same bits, as table0_entry on the device; each workgroup copies them to LDS, four entries
     // per load)
@@ -222,27 +223,6 @@ struct BpArgs {
     int DX[kMaxR], DZ[kMaxR];    // check-view lane lambda holds check (r, (lambda + D[r]) mod P)
     int CX[kMaxL], CZ[kMaxL];    // var-view lane mu holds variable (l, (mu + C[l]) mod P)
 };
-
-// ---- lane relabelling ------------------------------------------------------
-// Block (r, l) of a sector is the circulant "check (r, i) <-> variable (l, (E[r][l] + i) mod P)".
-// Storing check (r, i) in lane (i - D[r]) mod P and variable (l, j) in lane (j - C[l]) mod P
-// turns the block's check->variable lane rotation into S[r][l] = (E[r][l] + D[r] - C[l]) mod P.
-// With C[l] = E[0][l] and D[r] = (C[0] - E[r][0]) mod P the R + L - 1 blocks of row 0 and
-// column 0 need no rotation at all (a spanning tree of the block graph), so those edges skip
-// the ds_bpermute in both directions.  Arithmetic (and so every output bit) is unchanged.
-inline void relabel(const int* E, int R, int L, int P, bool on, int* S, int* D, int* C)
-{
-    if (!on) {
-        for (int k = 0; k < R * L; ++k) S[k] = E[k];
-        for (int r = 0; r < R; ++r) D[r] = 0;
-        for (int l = 0; l < L; ++l) C[l] = 0;
-        return;
-    }
-    for (int l = 0; l < L; ++l) C[l] = E[l];
-    for (int r = 0; r < R; ++r) D[r] = ((C[0] - E[r * L]) % P + P) % P;
-    for (int r = 0; r < R; ++r)
-        for (int l = 0; l < L; ++l) S[r * L + l] = ((E[r * L + l] + D[r] - C[l]) % P + P) % P;
-}
 
 // ---- shift providers -------------------------------------------------------
 // Runtime: exponents read from the kernel-argument block.  table() launders the
@@ -292,7 +272,7 @@ struct GeneratedShifts {
             for (int l = 0; l < L_; ++l) t.EX[j][l] = e.EX[j][l];
         for (int k = 0; k < K_; ++k)
             for (int l = 0; l < L_; ++l) t.EZ[k][l] = e.EZ[k][l];
-        // relabel() on the 2-D tables (same rule, written out for constant evaluation)
+        // relabel() of qec_wave.h on the 2-D tables (same rule, written out for constant evaluation)
         for (int l = 0; l < L_; ++l) { t.CX[l] = RL_ ? t.EX[0][l] : 0; t.CZ[l] = RL_ ? t.EZ[0][l] : 0; }
         for (int r = 0; r < J_; ++r) t.DX[r] = RL_ ? ((t.CX[0] - t.EX[r][0]) % P_ + P_) % P_ : 0;
         for (int r = 0; r < K_; ++r) t.DZ[r] = RL_ ? ((t.CZ[0] - t.EZ[r][0]) % P_ + P_) % P_ : 0;

@@ -711,6 +711,32 @@ int qec_near_hard_threshold(float pPrime, int R, int L, float* eps0, uint32_t* T
     return QEC_OK;
 }
 
+// QEC_OPT_MINSUM_WAVE and QEC_OPT_RELAY_WAVE (`name`): 0 or 1 into `field`; 1 on a single handle needs the sparse engine
+// and a code with wave kernels (`select`).  `what` names the rule ("min-sum", "relay"), `alone` what only the sparse
+// engine does with it.
+static int set_wave_option(qec_decoder* d, int value, int& field, const std::string& name, const char* what,
+                           const char* alone, const void* (*select)(const Code&))
+{
+    const std::string who = "qec_decoder_set_option: " + name;
+    if (value != 0 && value != 1) return fail(QEC_ERR_ARG, who + " is 0 (the sparse-graph kernels) or 1 (the wave kernels)");
+    if (value && d->parts.empty()) {
+        if (d->cpu)
+            return fail(QEC_ERR_UNSUPPORTED,
+                        who + " = 1 chooses GPU kernels; the CPU engine has one " + what + " implementation");
+        if (d->engine != QEC_ENGINE_SPARSE)
+            return fail(QEC_ERR_UNSUPPORTED,
+                        who + " = 1 is a kernel choice of a sparse-engine handle, which alone " + alone +
+                            "; create the decoder with QEC_ENGINE_SPARSE (engine \"sparse\")");
+        if (!select(*d->code))
+            return fail(QEC_ERR_UNSUPPORTED,
+                        who + " = 1: no wave " + what + " kernel for this code (" + d->code->describe() +
+                            "): needs circulant-permutation blocks, P <= 64 and a block shape (J,K,L) of the "
+                            "runtime-shift table");
+    }
+    field = value;
+    return QEC_OK;
+}
+
 int qec_decoder_set_option(qec_decoder* d, int option, int value)
 {
     if (!d) return fail(QEC_ERR_ARG, "qec_decoder_set_option: null decoder");
@@ -829,47 +855,11 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
         d->minsum_scale = value;
         return QEC_OK;
     case QEC_OPT_MINSUM_WAVE:
-        if (value != 0 && value != 1)
-            return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_MINSUM_WAVE is 0 (the sparse-graph kernels) or 1 (the "
-                                     "wave kernels)");
-        if (value && d->parts.empty()) {
-            if (d->cpu)
-                return fail(QEC_ERR_UNSUPPORTED,
-                            "qec_decoder_set_option: QEC_OPT_MINSUM_WAVE = 1 chooses GPU kernels; the CPU engine has one "
-                            "min-sum implementation");
-            if (d->engine != QEC_ENGINE_SPARSE)
-                return fail(QEC_ERR_UNSUPPORTED,
-                            "qec_decoder_set_option: QEC_OPT_MINSUM_WAVE = 1 is a kernel choice of a sparse-engine handle, "
-                            "which alone decodes by min-sum; create the decoder with QEC_ENGINE_SPARSE (engine \"sparse\")");
-            if (!select_wave_minsum(*d->code))
-                return fail(QEC_ERR_UNSUPPORTED,
-                            "qec_decoder_set_option: QEC_OPT_MINSUM_WAVE = 1: no wave min-sum kernel for this code (" +
-                                d->code->describe() + "): needs circulant-permutation blocks, P <= 64 and a block shape "
-                                "(J,K,L) of the runtime-shift table");
-        }
-        d->minsum_wave = value;
-        return QEC_OK;
+        return set_wave_option(d, value, d->minsum_wave, "QEC_OPT_MINSUM_WAVE", "min-sum", "decodes by min-sum",
+                               select_wave_minsum);
     case QEC_OPT_RELAY_WAVE:
-        if (value != 0 && value != 1)
-            return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_RELAY_WAVE is 0 (the sparse-graph kernels) or 1 (the "
-                                     "wave kernels)");
-        if (value && d->parts.empty()) {
-            if (d->cpu)
-                return fail(QEC_ERR_UNSUPPORTED,
-                            "qec_decoder_set_option: QEC_OPT_RELAY_WAVE = 1 chooses GPU kernels; the CPU engine has one "
-                            "relay implementation");
-            if (d->engine != QEC_ENGINE_SPARSE)
-                return fail(QEC_ERR_UNSUPPORTED,
-                            "qec_decoder_set_option: QEC_OPT_RELAY_WAVE = 1 is a kernel choice of a sparse-engine handle, "
-                            "which alone runs the relay; create the decoder with QEC_ENGINE_SPARSE (engine \"sparse\")");
-            if (!select_wave_relay(*d->code))
-                return fail(QEC_ERR_UNSUPPORTED,
-                            "qec_decoder_set_option: QEC_OPT_RELAY_WAVE = 1: no wave relay kernel for this code (" +
-                                d->code->describe() + "): needs circulant-permutation blocks, P <= 64 and a block shape "
-                                "(J,K,L) of the runtime-shift table");
-        }
-        d->relay_wave = value;
-        return QEC_OK;
+        return set_wave_option(d, value, d->relay_wave, "QEC_OPT_RELAY_WAVE", "relay", "runs the relay",
+                               select_wave_relay);
     case QEC_OPT_OSD_CS_SECTORS:
         return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD_CS_SECTORS is read only");
     case QEC_OPT_LAST_PATH: return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_LAST_PATH is read only");
