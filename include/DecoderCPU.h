@@ -96,6 +96,10 @@ public:
         check(qec_decoder_set_option(dec_, QEC_OPT_MINSUM_SCALE, scale));
         check(qec_decoder_set_option(dec_, QEC_OPT_BP_METHOD, method));
     }
+    // The order of min-sum's updates (QEC_OPT_MINSUM_SCHEDULE): 0 = flooding (the default), 1 = layered (check-sequential)
+    // min-sum.  In effect while SetBpMethod(1) is and no relay is set; independent of
+    // SetBpSchedule, the product rule's serial schedule.  Any other value throws the library's message.
+    void SetMinSumSchedule(int schedule) { check(qec_decoder_set_option(dec_, QEC_OPT_MINSUM_SCHEDULE, schedule)); }
     // Relay-BP (qec_decoder_set_relay): `legs` legs of memory min-sum under SetBpMethod(1), gammaX / gammaZ the memory
     // strengths [legs][n] (|gamma| <= 1), stopping at the first solution or at the lightest of the first `solutions`.
     void SetRelay(const std::vector<float>& gammaX, const std::vector<float>& gammaZ, int legs, int solutions = 1)

@@ -176,6 +176,10 @@ public:
         check(qec_decoder_set_option(dec_, QEC_OPT_MINSUM_SCALE, scale));
         check(qec_decoder_set_option(dec_, QEC_OPT_BP_METHOD, method));
     }
+    // The order of min-sum's updates (QEC_OPT_MINSUM_SCHEDULE): 0 = flooding (the default), 1 = layered (check-sequential)
+    // min-sum on the sparse-graph engine.  In effect while SetBpMethod(1) is and no relay is set; independent of
+    // SetBpSchedule, the product rule's serial schedule.  Any other value and 1 on a wave-circulant decoder throws the library's message.
+    void SetMinSumSchedule(int schedule) { check(qec_decoder_set_option(dec_, QEC_OPT_MINSUM_SCHEDULE, schedule)); }
     // The kernels of plain min-sum decodes (QEC_OPT_MINSUM_WAVE): 0 = the sparse-graph MINSUM kernels (the default),
     // 1 = the register-resident wave kernels, bit-identical, for circulant codes with P <= 64 and a block shape of the
     // runtime-shift table (qec_code_has_wave_minsum).  A kernel choice of a sparse-engine decoder: 1 on any other

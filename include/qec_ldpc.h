@@ -411,13 +411,40 @@ int qec_decoder_device(const qec_decoder* dec);         /* HIP device ordinal (o
  *     the option at 0 a relay decode never sets it.  The _dev entry points read it at the call and allocate nothing.
  *     1 is refused with QEC_ERR_UNSUPPORTED (the handle stays as it was, the text names the reason) on a sparse
  *     handle whose code has no wave kernel (qec_code_has_wave_minsum answers for both options), on a wave-circulant
- *     handle and on a CPU handle.  A group applies the value to every part. */
+ *     handle and on a CPU handle.  A group applies the value to every part.
+ *   QEC_OPT_MINSUM_SCHEDULE (default 0; 0 or 1, other values QEC_ERR_ARG): the order of min-sum's updates.  0 = flooding,
+ *     as ever (the same kernels).  1 = layered (check-sequential) min-sum, DESIGN.md section 2, "The layered min-sum
+ *     form": the state is one fp32 check->variable LLR R per real edge, +0.0f at the start (an unused slot of a general
+ *     code reads +0.0f in q_final).  An iteration takes the sector's checks in the order of qec_code_layers, sorted by
+ *     (colour, index); check c forms, for each of its slots in ascending order, the left fold lambda_v + R of v's OTHER
+ *     checks as they stand, in ascending check order, and then its own R by the check update of QEC_OPT_BP_METHOD = 1
+ *     (a check of degree 1 sends alpha * 2^20).  The posterior of v is the same fold over ALL its checks; its decision
+ *     is posterior < 0.0f; a variable in no check decides 0 and enters no test.  Stop rules over the posteriors: FIXED N
+ *     iterations; SYNDROME after the first iteration whose decisions satisfy the syndrome; REF after an iteration with
+ *     index % 10 == 0 that leaves no posterior inside (fabsf < 4.5951198f).  There is no special last iteration.
+ *     CONVERGENCE_FAIL: a posterior of the final state inside; SYNDROME_FAIL from the final decisions; q_final: every
+ *     real slot of v holds v's final posterior; N = 0 gives lambda_v.  The value is data, like QEC_OPT_MINSUM_SCALE: it
+ *     is read at every decode call and takes effect while QEC_OPT_BP_METHOD = 1 and no relay tables are set; under the
+ *     product rule it does nothing, and a relay runs its flooding legs as before.  QEC_OPT_BP_SCHEDULE is the product
+ *     rule's serial schedule and stays what it was: it and QEC_OPT_BP_METHOD = 1 still refuse each other.  Sparse-graph
+ *     engine (the LAYERED kernels of bp_sparse.hip; plan, workspace, grid and describe string unchanged; the layer
+ *     tables are uploaded when the plan is created, so setting the option allocates nothing) and CPU engine; a
+ *     wave-circulant handle refuses 1 with QEC_ERR_UNSUPPORTED and the text says to create the decoder with
+ *     QEC_ENGINE_SPARSE.  With QEC_OPT_MINSUM_WAVE = 1 a layered decode runs the layered wave kernels of
+ *     bp_wave_minsum.hip ("The layered min-sum form in the wave layout": the messages in the
+ *     variable view, a layer = a block row = one lane-local check pass; no LDS, no barrier, no scratch), bit for bit
+ *     the LAYERED kernels' outputs.  QEC_OPT_LAST_PATH carries QEC_PATH_MINSUM | QEC_PATH_SERIAL when the layered rule
+ *     ran, and QEC_PATH_WAVE beside them when the wave kernels ran it.  Every decode entry point
+ *     honours it, the _dev ones read it at the call and allocate nothing (a captured graph keeps the kernels it
+ *     captured); the OSD stage's soft decode runs the same schedule (its column key reads q_final, here the
+ *     posterior).  The near-hard jump never fires.  A schedule for the QC codes: on the hypergraph product hgp_ham it
+ *     leaves more syndromes unsatisfied than flooding min-sum does (README).  A group applies the value to every part. */
 enum { QEC_OPT_HARD_PATHS = 1, QEC_OPT_CYCLE_JUMP = 2, QEC_OPT_SCHEDULE = 3, QEC_OPT_SECTOR_SPLIT = 4,
        QEC_OPT_PHASE_STATS = 5, QEC_OPT_TRIAGE = 6, QEC_OPT_LAST_PATH = 7, QEC_OPT_MC_DECODE_TIME = 8,
        QEC_OPT_OSD = 9, QEC_OPT_OSD_ITERATIONS = 10, QEC_OPT_OSD_SECTORS = 11, QEC_OPT_OSD_SWEEP = 12,
        QEC_OPT_OSD_ORDER = 13, QEC_OPT_OSD_CS_SECTORS = 14, QEC_OPT_NEAR_HARD_JUMP = 15, QEC_OPT_OSD_SCORE = 16,
        QEC_OPT_CORRELATED = 17, QEC_OPT_BP_SCHEDULE = 18, QEC_OPT_BP_METHOD = 19, QEC_OPT_MINSUM_SCALE = 20,
-       QEC_OPT_MINSUM_WAVE = 21, QEC_OPT_RELAY_WAVE = 22 };
+       QEC_OPT_MINSUM_WAVE = 21, QEC_OPT_RELAY_WAVE = 22, QEC_OPT_MINSUM_SCHEDULE = 23 };
 enum {
     QEC_PATH_ORDERED = 1,          /* dispatch order pass (schedule.hip) */
     QEC_PATH_SECTOR_ORDER = 2,     /* ... in the per-sector form (each sector's waves by its own weight) */
@@ -429,7 +456,8 @@ enum {
     QEC_PATH_RECORDS = 128,        /* packed decision records out */
     QEC_PATH_OSD = 256,            /* the call ran the OSD stage (QEC_OPT_OSD) */
     QEC_PATH_CORRELATED = 512,     /* one sector decoded under priors conditioned on the other's estimate */
-    QEC_PATH_SERIAL = 1024,        /* BP under the serial schedule (QEC_OPT_BP_SCHEDULE = 1) */
+    QEC_PATH_SERIAL = 1024,        /* BP under the serial schedule (QEC_OPT_BP_SCHEDULE = 1), or layered min-sum
+                                      (QEC_OPT_MINSUM_SCHEDULE = 1, then beside QEC_PATH_MINSUM) */
     QEC_PATH_MINSUM = 2048,        /* scaled min-sum BP (QEC_OPT_BP_METHOD = 1) */
     QEC_PATH_RELAY = 4096,         /* ... as a relay of memory min-sum legs (qec_decoder_set_relay) */
     QEC_PATH_WAVE = 8192           /* ... by the register-resident wave kernels (QEC_OPT_MINSUM_WAVE = 1, or

@@ -30,12 +30,14 @@ OPTION = {"hard_paths": 1, "cycle_jump": 2, "schedule": 3, "sector_split": 4, "p
           "last_path": 7, "mc_decode_time": 8, "osd": 9, "osd_iterations": 10, "osd_sectors": 11,
           "osd_sweep": 12, "osd_order": 13, "osd_cs_sectors": 14, "near_hard": 15, "osd_score": 16,
           "correlated": 17, "bp_schedule": 18, "bp_method": 19, "minsum_scale": 20,
-          "minsum_wave": 21, "relay_wave": 22}
+          "minsum_wave": 21, "relay_wave": 22, "minsum_schedule": 23}
 OPTIONS = OPTION
 # values of the "bp_schedule" option (QEC_OPT_BP_SCHEDULE)
 BP_SCHEDULE = {"flooding": 0, "serial": 1}
 # values of the "bp_method" option (QEC_OPT_BP_METHOD)
 BP_METHOD = {"product": 0, "minsum": 1}
+# values of the "minsum_schedule" option (QEC_OPT_MINSUM_SCHEDULE)
+MINSUM_SCHEDULE = {"flooding": 0, "layered": 1}
 # QEC_PATH_* bits of QEC_OPT_LAST_PATH (include/qec_ldpc.h): the launch sequence of the last decode call
 PATH = {"ordered": 1, "sector_order": 2, "split_waves": 4, "sector_launches": 8, "triage": 16, "bit_rows": 32,
         "sparse": 64, "records": 128, "osd": 256, "correlated": 512, "serial": 1024,

@@ -960,6 +960,144 @@ __device__ __forceinline__ void sp_minsum_decode(const SparseArgs& a, const uint
     }
 }
 
+// ---- LAYERED: layered min-sum (QEC_OPT_MINSUM_SCHEDULE = 1; DESIGN.md section 2, "The layered min-sum form") -----
+// The SERIAL body's layer intervals and two steps with min-sum's arithmetic.  The message array holds R, the
+// check->variable LLR of every edge: +0.0f at the start; an unused slot of a general code holds the float K throughout,
+// as in the MINSUM body (it changes neither a minimum nor the parity, sp_minsum_check stores it back as K, no fold reads
+// it -- the folds walk the variable's real edges only -- and the export writes +0.0f for it).  Per layer interval:
+//   * a thread per slot of the layer's checks forms the slot's input, the left fold of the variable's channel LLR and
+//     the R of its other checks in ascending check order, and parks it in its own slot (the checks of one colour share
+//     no variable, so nobody else reads that slot in this interval); barrier;
+//   * a thread per check turns its row into the check's R in place by sp_minsum_check; barrier.
+// The posterior pass (thread per variable, the fold over all of the variable's checks) writes the decision bytes and
+// folds the inside test into its ballot; it runs where a stop rule looks and once on the final state.  The argument
+// block is read as the MINSUM kernels read it (errorProbability = the scalar channel LLR, prior = null or the 2n channel
+// LLRs, c0 = alpha) together with the SERIAL kernels' layer tables.  Workspace, grid and workgroup are the scalar plan's.
+template <bool GENERAL>
+__device__ __forceinline__ float sp_layered_fold(const float* __restrict__ msg, const int32_t* __restrict__ ve, int dv,
+                                                 int self, float lam)
+{
+    float t = lam;
+    for (int j = 0; j < dv; ++j) {
+        const int ed = ve[j];
+        if (GENERAL && ed < 0) break;  // the real entries come first
+        if (ed == self) continue;
+        t = t + msg[ed];
+    }
+    return t;
+}
+
+template <int STOP, int MAXDC, int MAXDV, bool GENERAL>
+__device__ __forceinline__ void sp_layered_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws)
+{
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
+    const int EX = mX * dc, E = m * dc;
+    float* msg = reinterpret_cast<float*>(ws);            // E floats
+    uint8_t* syn = ws + (size_t)E * sizeof(float);        // m bytes: sX then sZ
+    uint8_t* hd = syn + m;                                // 2n bytes: X then Z decisions
+
+    const float lam0 = a.errorProbability, alpha = a.c0;
+    const float* llr = a.prior;
+    const bool tab = llr != nullptr;  // workgroup-uniform: per-variable channel LLRs or the scalar one
+    const int N = a.maxIter < 0 ? 0 : a.maxIter;
+    const int LX = a.LX, LZ = a.LZ;
+    const int32_t* offX = a.layOff;
+    const int32_t* offZ = a.layOff + LX + 1;
+
+    // the posterior pass over the sectors doX / doZ: decision bytes, and whether a posterior is inside the band
+    auto posterior = [&](bool doX, bool doZ, bool& bx, bool& bz) {
+        for (int v = tid; v < 2 * n; v += nt) {
+            const bool z = v >= n;
+            if (z ? !doZ : !doX) continue;
+            int dv;
+            const int32_t* ve = sp_var_edges(a, v, dv);
+            if (GENERAL && ve[0] < 0) { hd[v] = 0; continue; }  // a variable in no check decides 0, enters no test
+            const float post = sp_layered_fold<GENERAL>(msg, ve, dv, -1, tab ? llr[v] : lam0);
+            hd[v] = post < 0.0f;
+            if (sp_minsum_inside(post)) { if (z) bz = true; else bx = true; }
+        }
+    };
+
+    for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
+        sp_load_syndromes<GENERAL>(a, chkDeg, b, syn);
+        for (int e = tid; e < E; e += nt)
+            msg[e] = (!GENERAL || a.chkVar[e] >= 0) ? 0.0f : __uint_as_float(kMinSumCap);
+        __syncthreads();
+
+        bool actX = true, actZ = true;  // workgroup-uniform
+        int itX = 0, itZ = 0;
+        for (int it = 0; it < N && (actX || actZ); ++it) {
+            itX += actX;
+            itZ += actZ;
+            const int layers = max(actX ? LX : 0, actZ ? LZ : 0);
+            for (int l = 0; l < layers; ++l) {
+                const int x0 = actX && l < LX ? offX[l] : 0, nx = actX && l < LX ? offX[l + 1] - x0 : 0;
+                const int z0 = actZ && l < LZ ? offZ[l] : 0, nz = actZ && l < LZ ? offZ[l + 1] - z0 : 0;
+                // the slots of the layer's checks, a thread per slot: the input from the slot's variable
+                for (int i = tid; i < (nx + nz) * dc; i += nt) {
+                    const int j = i / dc, k = i - j * dc;
+                    const int c = a.layOrder[j < nx ? x0 + j : z0 + (j - nx)];
+                    const int e = c * dc + k, v = a.chkVar[e];
+                    if (GENERAL && v < 0) continue;  // an unused slot keeps K
+                    const bool z = c >= mX;
+                    const int dv = z ? a.dvZ : a.dvX;
+                    const int32_t* ve = a.varEdge + (z ? (size_t)n * a.dvX : 0) + (size_t)v * dv;
+                    msg[e] = sp_layered_fold<GENERAL>(msg, ve, dv, e, tab ? llr[(z ? n : 0) + v] : lam0);
+                }
+                __syncthreads();
+                // the layer's checks, a thread per check: the row becomes the check's R
+                for (int i = tid; i < nx + nz; i += nt) {
+                    const int c = a.layOrder[i < nx ? x0 + i : z0 + (i - nx)];
+                    sp_minsum_check<GENERAL>(msg + (size_t)c * dc, dc, syn[c], alpha);
+                }
+                __syncthreads();
+            }
+            if (STOP == QEC_STOP_REF && it % 10 == 0) {
+                bool bx = false, bz = false;
+                posterior(actX, actZ, bx, bz);
+                const bool anyx = __syncthreads_or(bx), anyz = __syncthreads_or(bz);
+                if (actX && !anyx) actX = false;
+                if (actZ && !anyz) actZ = false;
+            } else if (STOP == QEC_STOP_SYNDROME) {
+                bool bx = false, bz = false;
+                posterior(actX, actZ, bx, bz);
+                __syncthreads();
+                bx = bz = false;
+                sp_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
+                const bool badx = __syncthreads_or(bx), badz = __syncthreads_or(bz);
+                if (actX && !badx) actX = false;
+                if (actZ && !badz) actZ = false;
+            }
+        }
+
+        // ---- the final state: decisions, flags, q_final ----
+        bool bx = false, bz = false;
+        posterior(true, true, bx, bz);
+        const bool convFailX = __syncthreads_or(bx), convFailZ = __syncthreads_or(bz);
+        for (int v = tid; v < 2 * n; v += nt) {
+            if (v >= n) a.eZ[b * n + (v - n)] = hd[v]; else a.eX[b * n + v] = hd[v];
+        }
+        bool sx = false, sz = false;
+        sp_syndrome_fails<GENERAL>(a, syn, hd, sx, sz);
+        const bool synFailX = __syncthreads_or(sx), synFailZ = __syncthreads_or(sz);
+        if (a.q != nullptr)
+            for (int e = tid; e < E; e += nt) {
+                const int v = a.chkVar[e];
+                float post = 0.0f;  // an unused slot of a general code
+                if (!GENERAL || v >= 0) {
+                    const int gv = (e < EX ? 0 : n) + v;
+                    int dv;
+                    const int32_t* ve = sp_var_edges(a, gv, dv);
+                    post = sp_layered_fold<GENERAL>(msg, ve, dv, -1, tab ? llr[gv] : lam0);
+                }
+                a.q[b * E + e] = post;
+            }
+        sp_store_status(a, b, sp_fail_flags(synFailX, synFailZ, convFailX, convFailZ), itX, itZ);
+        __syncthreads();  // the workspace is reused by the next syndrome pair
+    }
+}
+
 // ---- RELAY: chained memory min-sum legs (qec_decoder_set_relay; DESIGN.md section 2, "The relay form") -----
 // The min-sum body with one fp32 memory M_v per variable and a chain of legs: each leg starts from channel-LLR slots and
 // the previous leg's posteriors in M, runs under the call's stop rule counted within the leg, and a leg whose final
@@ -1235,9 +1373,18 @@ __global__ __launch_bounds__(kSparseThreads) void bp_relay_kernel(const RelayArg
     sp_relay_decode<STOP, MAXDC, MAXDV, GENERAL>(ra, ws);
 }
 
+// Layered min-sum's one entry for both routes (a regular code brings no degree bytes)
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL>
+__global__ __launch_bounds__(kSparseThreads) void bp_layered_kernel(const GeneralArgs ga)
+{
+    uint8_t* ws = LDS ? sp_lds : ga.s.scratch + (long long)blockIdx.x * ga.s.ws_bytes;
+    sp_layered_decode<STOP, MAXDC, MAXDV, GENERAL>(ga.s, ga.chkDeg, ws);
+}
+
 // ---- plan ------------------------------------------------------------------
-// The kernels of one shape, by variant and stop rule.  SERIAL takes priors as a runtime branch, CORR, MINSUM and RELAY too.
-enum { kScalar = 0, kPriors = 1, kCorr = 2, kSerial = 3, kMinSum = 4, kRelay = 5, kVariants = 6 };
+// The kernels of one shape, by variant and stop rule.  SERIAL takes priors as a runtime branch, CORR, MINSUM, RELAY and
+// LAYERED too.
+enum { kScalar = 0, kPriors = 1, kCorr = 2, kSerial = 3, kMinSum = 4, kRelay = 5, kLayered = 6, kVariants = 7 };
 using SparseKernels = const void* [kVariants][3];
 
 template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL, bool PRIORS, bool CORR, bool SERIAL, bool MINSUM = false>
@@ -1257,6 +1404,7 @@ static void sparse_kernels_of_stop(SparseKernels& fn)
     fn[kSerial][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, false, true>();
     fn[kMinSum][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, false, false, true>();
     fn[kRelay][STOP] = reinterpret_cast<const void*>(&bp_relay_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL>);
+    fn[kLayered][STOP] = reinterpret_cast<const void*>(&bp_layered_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL>);
 }
 
 template <int MAXDC, int MAXDV, bool LDS, bool GENERAL>
@@ -1515,6 +1663,10 @@ int launch_decode_sparse(void* plan, const SparseDecode& d, hipStream_t stream)
         ra.solutions = d.solutions;
         args[0] = &ra;
         variant = kRelay;
+    }
+    if (d.minsum && d.gamma == nullptr && d.layered) {  // plain min-sum under QEC_OPT_MINSUM_SCHEDULE = 1: the LAYERED kernels
+        args[0] = &ga;
+        variant = kLayered;
     }
     const unsigned grid = (unsigned)std::min<long long>(d.B, p->grid);
     (void)hipLaunchKernel(p->fn[variant][d.stop], dim3(grid), dim3(p->threads), args, p->lds ? (size_t)p->ws_bytes : 0, stream);

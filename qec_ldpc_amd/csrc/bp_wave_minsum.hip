@@ -2,7 +2,8 @@
 // "The min-sum form in the wave layout").  The rule is sp_minsum_decode's (bp_sparse.hip) in every bit; the layout,
 // the lane helpers, the check pass, the syndrome test and the host-side shape table, argument filling and launch are
 // qec_wave.h's.  This file holds what is min-sum's own: the argument struct, sp_minsum_var's folds from lambda (with
-// the LAST form of the cap's last iteration), the sector function and the kernel.
+// the LAST form of the cap's last iteration), the sector function and the kernel -- and, behind them, the same for
+// layered min-sum (QEC_OPT_MINSUM_SCHEDULE = 1): wl_sector and wave_layered_kernel over the same argument struct.
 // No LDS beyond the permutes' crossbar, no atomics, no barriers, no scratch.  Every loop is bounded by maxIter.
 //
 // Groups of one wave stop on their own (G > 1, reference and syndrome stop): control flow stays wave-uniform, every
@@ -180,7 +181,160 @@ __global__ __launch_bounds__(64) void wave_minsum_kernel(const WaveMinsumArgs a)
     wave_store_flags(a, ln, b, f, itX, itZ);
 }
 
+// ---- layered min-sum (QEC_OPT_MINSUM_SCHEDULE = 1; DESIGN.md section 2, "The layered min-sum form in the wave layout") ----
+// The rule is sp_layered_decode's (bp_sparse.hip) in every bit.  The layers of a circulant-permutation code are its
+// block rows, and a block row's checks sit one per lane, so a layer is one lane-local check pass.  The messages live in
+// the VARIABLE view, Rv[r][l] = the message of row block r into the lane's variable of column l: the fold of a layer's
+// inputs (the channel LLR and the R of the other row blocks, ascending) and the posterior are then lane-local adds,
+// and a layer rotates its L inputs to the check view and its L outputs back -- per iteration the 2 (R - 1)(L - 1)
+// permutes of a flooding iteration.  The stop tests and the flags read the posteriors; q_final is the posterior rotated
+// to each check's slots, only when requested.  Frozen groups, full EXEC at every permute and the loop bound as above.
+template <int R, int L>
+__device__ __forceinline__ uint32_t wl_posterior(float (&post)[L], const float (&Rv)[R][L], const float (&lamv)[L], bool& in)
+{
+    uint32_t hd = 0;
+    in = false;
+#pragma unroll
+    for (int l = 0; l < L; ++l) {
+        float t = lamv[l];
+#pragma unroll
+        for (int r = 0; r < R; ++r) t = t + Rv[r][l];
+        post[l] = t;
+        hd |= (uint32_t)(t < 0.0f) << l;
+        in |= wave_inside(t);
+    }
+    return hd;
+}
+
+template <int R, int L, int SEC, int STOP, bool FREEZE>
+__device__ __forceinline__ uint32_t wl_sector(const WaveMinsumArgs& a, const WaveLane& ln, long long b, int& itn)
+{
+    const int P = a.P, n = a.n, N = a.maxIter;
+    const int* D = SEC ? a.DZ : a.DX;
+    const int* C = SEC ? a.CZ : a.CX;
+    const float alpha = a.alpha;
+
+    const uint32_t sb = wave_load_syndrome<R, SEC>(a, ln, b);
+    // channel LLRs of the lane's variables (l, (i + C[l]) mod P)
+    float lamv[L];
+#pragma unroll
+    for (int l = 0; l < L; ++l) lamv[l] = a.lam;
+    if (a.llr != nullptr && ln.live) {
+        const float* t = a.llr + (size_t)SEC * n;
+#pragma unroll
+        for (int l = 0; l < L; ++l) lamv[l] = t[l * P + wave_wrap(ln.i + C[l], P)];
+    }
+    float Rv[R][L];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int l = 0; l < L; ++l) Rv[r][l] = 0.0f;
+
+    bool act = ln.live;  // the same on every lane of a group
+    bool syn_ok = false; // syndrome stop: the last test of the group's own decisions
+    itn = 0;
+    for (int it = 0; it < N; ++it) {
+        if (__builtin_amdgcn_ballot_w64(act) == 0ull) break;
+        itn += act ? 1 : 0;
+        {
+            const WaveTable S = wave_table<WaveMinsumArgs, SEC>();
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                float qc[L];
+#pragma unroll
+                for (int l = 0; l < L; ++l) {
+                    float t = lamv[l];
+#pragma unroll
+                    for (int k = 0; k < R; ++k)
+                        if (k != r) t = t + Rv[k][l];
+                    qc[l] = (r == 0 || l == 0) ? t : wave_rot(t, ln, P - S[r * L + l]);
+                }
+                wave_check_row<L>(qc, ((sb >> (2 * r)) & 3u) != 0u, alpha);
+#pragma unroll
+                for (int l = 0; l < L; ++l) {
+                    const float back = (r == 0 || l == 0) ? qc[l] : wave_rot(qc[l], ln, S[r * L + l]);
+                    Rv[r][l] = FREEZE && !act ? Rv[r][l] : back;
+                }
+            }
+        }
+        if (STOP == QEC_STOP_REF && it % 10 == 0) {
+            float post[L];
+            bool in;
+            (void)wl_posterior<R, L>(post, Rv, lamv, in);
+            if (wave_group_all<true>(!in, ln)) act = false;
+        } else if (STOP == QEC_STOP_SYNDROME) {
+            float post[L];
+            bool in;
+            const uint32_t hd = wl_posterior<R, L>(post, Rv, lamv, in);
+            const bool ok = wave_group_all<true>(wave_lane_syndrome_ok<R, L, SEC>(a, hd, sb, ln), ln);
+            syn_ok = act ? ok : syn_ok;
+            if (ok) act = false;
+        }
+    }
+
+    // ---- the final state: posteriors, decisions, flags, the outputs ----
+    float post[L];
+    bool in;
+    const uint32_t hd = wl_posterior<R, L>(post, Rv, lamv, in);
+    const bool convFail = !wave_group_all<true>(!in, ln);
+    if (STOP != QEC_STOP_SYNDROME || N == 0)
+        syn_ok = wave_group_all<true>(wave_lane_syndrome_ok<R, L, SEC>(a, hd, sb, ln), ln);
+    if (ln.live) {
+        uint8_t* e = (SEC ? a.eZ : a.eX) + b * n;
+#pragma unroll
+        for (int l = 0; l < L; ++l) e[l * P + wave_wrap(ln.i + C[l], P)] = (uint8_t)((hd >> l) & 1u);
+    }
+    if (a.q != nullptr) {  // wave-uniform: every lane takes part in the rotations, a live lane stores
+        const WaveTable S = wave_table<WaveMinsumArgs, SEC>();
+        float* q = a.q + b * ((long long)(a.mX + a.mZ) * L) + (SEC ? (long long)a.mX * L : 0);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float* row = q + (size_t)(r * P + wave_wrap(ln.i + D[r], P)) * L;
+#pragma unroll
+            for (int l = 0; l < L; ++l) {
+                const float v = (r == 0 || l == 0) ? post[l] : wave_rot(post[l], ln, P - S[r * L + l]);
+                if (ln.live) row[l] = v;
+            }
+        }
+    }
+    uint32_t f = 0;
+    if (!syn_ok) f |= SEC ? QEC_SYNDROME_FAIL_Z : QEC_SYNDROME_FAIL_X;
+    if (convFail) f |= SEC ? QEC_CONVERGENCE_FAIL_Z : QEC_CONVERGENCE_FAIL_X;
+    return f;
+}
+
+template <int J, int K, int L, int STOP>
+__global__ __launch_bounds__(64) void wave_layered_kernel(const WaveMinsumArgs a)
+{
+    long long b;
+    WaveLane ln;
+    wave_lane(a, ln, b);
+
+    uint32_t f;
+    int itX, itZ;
+    if (STOP != QEC_STOP_FIXED && a.G > 1) {  // wave-uniform: groups that stop on their own
+        f = wl_sector<J, L, 0, STOP, true>(a, ln, b, itX);
+        f |= wl_sector<K, L, 1, STOP, true>(a, ln, b, itZ);
+    } else {
+        f = wl_sector<J, L, 0, STOP, false>(a, ln, b, itX);
+        f |= wl_sector<K, L, 1, STOP, false>(a, ln, b, itZ);
+    }
+    wave_store_flags(a, ln, b, f, itX, itZ);
+}
+
 // ---- host side ---------------------------------------------------------------
+template <int J, int K, int L>
+static WaveShape wl_shape()
+{
+    WaveShape s{J, K, L, {nullptr, nullptr, nullptr}};
+    s.fn[QEC_STOP_REF] = reinterpret_cast<const void*>(&wave_layered_kernel<J, K, L, QEC_STOP_REF>);
+    s.fn[QEC_STOP_FIXED] = reinterpret_cast<const void*>(&wave_layered_kernel<J, K, L, QEC_STOP_FIXED>);
+    s.fn[QEC_STOP_SYNDROME] = reinterpret_cast<const void*>(&wave_layered_kernel<J, K, L, QEC_STOP_SYNDROME>);
+    return s;
+}
+
+static const WaveShape kWaveLayeredShapes[] = {QEC_WAVE_SHAPE_TABLE(wl_shape)};
+
 template <int J, int K, int L>
 static WaveShape wm_shape()
 {
@@ -199,7 +353,7 @@ const void* select_wave_minsum(const Code& c) { return wave_find_shape(kWaveMins
 std::string wave_minsum_name(const Code& c) { return wave_name("minsum", c); }
 
 // One min-sum decode launch in the wave layout: d as launch_decode_sparse's MINSUM kernels read it (minsum = the
-// scale, lam, and with prior set llr), no relay tables.
+// scale, lam, and with prior set llr), no relay tables; d.layered picks the layered kernels of the same shape.
 int launch_wave_minsum(const void* shape, const Code& c, const SparseDecode& d, hipStream_t stream)
 {
     const char* who = "wave min-sum launch";
@@ -210,7 +364,9 @@ int launch_wave_minsum(const void* shape, const Code& c, const SparseDecode& d, 
         return fail(QEC_ERR_ARG, "wave min-sum launch: plain min-sum only (no correlated form, serial schedule or relay)");
     WaveMinsumArgs a{};
     const int rc = wave_fill_args(who, a, c, d);
-    return rc != QEC_OK ? rc : wave_launch(who, s->fn[d.stop], a, stream);
+    if (rc != QEC_OK) return rc;
+    if (d.layered) s = wave_find_shape(kWaveLayeredShapes, c);  // the same row of the other table
+    return wave_launch(who, s->fn[d.stop], a, stream);
 }
 
 }  // namespace qec

@@ -94,7 +94,7 @@ int cpu_threads();
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
                      bool near_hard, const float* prior, int corr, const float* cond, int serial, int minsum,
-                     const float* llr, const float* gamma, int legs, int solutions, const int32_t* weight);
+                     const float* llr, const float* gamma, int legs, int solutions, const int32_t* weight, int layered);
 int sparse_plan_relay_reserve(void* plan);
 void correlated_priors(float p, float* c0, float* c1);
 int launch_pack_decisions(const uint8_t* eX, const uint8_t* eZ, const uint8_t* flags, long long B, int n, uint8_t* out,
@@ -192,6 +192,9 @@ struct qec_decoder {
     // QEC_OPT_RELAY_WAVE: a sparse-engine handle's relay decodes run the wave kernels (bp_wave_relay.hip); data like
     // minsum_wave, in effect while bp_method = 1 and relay tables are set, whatever minsum_wave says
     int relay_wave = 0;
+    // QEC_OPT_MINSUM_SCHEDULE: 0 flooding, 1 layered min-sum ("The layered min-sum form"); data like
+    // minsum_scale, in effect while bp_method = 1 and no relay tables are set
+    int minsum_schedule = 0;
     const float* llr_host() const { return has_priors ? mllr.data() : nullptr; }
     const float* llr_dev() const { return has_priors ? dmllr.data() : nullptr; }
     // qec_decoder_set_relay ("The relay form"): L legs of per-variable memory strengths, [leg][sector][n],
@@ -206,6 +209,7 @@ struct qec_decoder {
     bool relay_on() const { return relay_legs > 0 && bp_method == 1 && !relay_hold; }
     const float* relay_host() const { return relay_on() ? relay.data() : nullptr; }
     const float* relay_dev() const { return relay_on() ? drelay.data() : nullptr; }
+    bool layered_on() const { return bp_method == 1 && minsum_schedule == 1 && !relay_on(); }
     // the weights of a relay solution: the integer tables of the priors (as qec_decoder_get_osd_weights), or none
     const int32_t* relay_w_host() const { return has_priors ? osw.data() : nullptr; }
     const int32_t* relay_w_dev() const { return has_priors ? dosw.data() : nullptr; }
@@ -854,6 +858,15 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
             return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_MINSUM_SCALE is 1 .. 256 (alpha = value / 256)");
         d->minsum_scale = value;
         return QEC_OK;
+    case QEC_OPT_MINSUM_SCHEDULE:
+        if (value != 0 && value != 1)
+            return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_MINSUM_SCHEDULE is 0 (flooding) or 1 (layered)");
+        if (value && d->parts.empty() && !d->cpu && d->engine != QEC_ENGINE_SPARSE)
+            return fail(QEC_ERR_UNSUPPORTED,
+                        "qec_decoder_set_option: QEC_OPT_MINSUM_SCHEDULE = 1 (layered) is a schedule of min-sum, which the "
+                        "wave-circulant engine does not run; create the decoder with QEC_ENGINE_SPARSE (engine \"sparse\")");
+        d->minsum_schedule = value;
+        return QEC_OK;
     case QEC_OPT_MINSUM_WAVE:
         return set_wave_option(d, value, d->minsum_wave, "QEC_OPT_MINSUM_WAVE", "min-sum", "decodes by min-sum",
                                select_wave_minsum);
@@ -1178,6 +1191,7 @@ int qec_decoder_get_option(const qec_decoder* d, int option, int* value)
     case QEC_OPT_BP_METHOD: *value = d->bp_method; return QEC_OK;
     case QEC_OPT_MINSUM_SCALE: *value = d->minsum_scale; return QEC_OK;
     case QEC_OPT_MINSUM_WAVE: *value = d->minsum_wave; return QEC_OK;
+    case QEC_OPT_MINSUM_SCHEDULE: *value = d->minsum_schedule; return QEC_OK;
     case QEC_OPT_RELAY_WAVE: *value = d->relay_wave; return QEC_OK;
     case QEC_OPT_OSD_CS_SECTORS: {
         unsigned long long t = d->osd_cs_sectors;
@@ -1280,6 +1294,9 @@ int dispatch_decode(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, long l
                 sd.relay_weight = d->relay_w_dev();
                 d->last_path |= QEC_PATH_RELAY;
             }
+            // QEC_OPT_MINSUM_SCHEDULE, read at the call: the LAYERED kernels (plain min-sum only: the relay's legs flood)
+            sd.layered = d->layered_on();
+            if (sd.layered) d->last_path |= QEC_PATH_SERIAL;
         }
         // QEC_OPT_MINSUM_WAVE, read at the call: plain min-sum in the wave layout (set_option has checked the code)
         if (sd.minsum && sd.gamma == nullptr && d->minsum_wave) {
@@ -1470,7 +1487,8 @@ int osd_repair_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t
             const int rc = cpu_decode_batch(d->cpu, cX.data(), cZ.data(), (long long)cnt, p, d->osd_iters, QEC_STOP_FIXED,
                                             cEX.data(), cEZ.data(), cFs.data(), nullptr, nullptr, cq.data(), 0,
                                             false, d->prior_host(), d->correlated, d->cond_host(), d->bp_schedule,
-                                            d->minsum(), d->llr_host(), nullptr, 0, 0, nullptr);  // never the relay
+                                            d->minsum(), d->llr_host(), nullptr, 0, 0, nullptr,  // never the relay
+                                            d->bp_method == 1 && d->minsum_schedule == 1);
             if (rc) return rc;
             long long swept = 0;
             osd_host_batch(*d->oplan, cX.data(), cZ.data(), (long long)cnt, cq.data(), cEX.data(), cEZ.data(), cF.data(), 0,
@@ -1590,8 +1608,8 @@ int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
         const int rc = cpu_decode_batch(d->cpu, sX, sZ, (long long)B, p, maxIter, stop, eX, eZ, flags, rec, iters, q, 0,
                                         d->hard_paths && d->near_hard, d->prior_host(), d->correlated, d->cond_host(),
                                         d->bp_schedule, d->minsum(), d->llr_host(), d->relay_host(), d->relay_legs,
-                                        d->relay_solutions, d->relay_w_host());
-        d->last_path = (d->correlated ? QEC_PATH_CORRELATED : 0) | (d->bp_schedule ? QEC_PATH_SERIAL : 0) |
+                                        d->relay_solutions, d->relay_w_host(), d->layered_on());
+        d->last_path = (d->correlated ? QEC_PATH_CORRELATED : 0) | (d->bp_schedule || d->layered_on() ? QEC_PATH_SERIAL : 0) |
                        (d->bp_method ? QEC_PATH_MINSUM : 0) | (d->relay_on() ? QEC_PATH_RELAY : 0);
         return rc || !d->osd ? rc : osd_repair_host(d, sX, sZ, B, p, eX, eZ, flags, rec);
     }
@@ -1946,7 +1964,8 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
         const int rc = cpu_decode_batch(d->cpu, sx.data(), sz.data(), cnt, p, maxIter, QEC_STOP_REF, ex.data(), ez.data(),
                                         fl.data(), nullptr, nullptr, nullptr, 0, d->hard_paths && d->near_hard,
                                         d->prior_host(), d->correlated, d->cond_host(), d->bp_schedule, d->minsum(),
-                                        d->llr_host(), d->relay_host(), d->relay_legs, d->relay_solutions, d->relay_w_host());
+                                        d->llr_host(), d->relay_host(), d->relay_legs, d->relay_solutions, d->relay_w_host(),
+                                        d->layered_on());
         if (rc) return rc;
         if (d->osd) {  // the counters describe the repaired estimates
             d->osd_sectors = 0;
@@ -1981,7 +2000,7 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
     d->osd_sectors = repaired;
     d->osd_cs_sectors = swept;
     d->last_path = (d->osd ? QEC_PATH_OSD : 0) | (d->correlated ? QEC_PATH_CORRELATED : 0) |
-                   (d->bp_schedule ? QEC_PATH_SERIAL : 0) | (d->bp_method ? QEC_PATH_MINSUM : 0) |
+                   (d->bp_schedule || d->layered_on() ? QEC_PATH_SERIAL : 0) | (d->bp_method ? QEC_PATH_MINSUM : 0) |
                    (d->relay_on() ? QEC_PATH_RELAY : 0);
     std::memset(out, 0, sizeof *out);
     out->randSeed = seed;

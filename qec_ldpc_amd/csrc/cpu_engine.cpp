@@ -487,6 +487,102 @@ int decode_sector_minsum(const CpuSector& S, int n, bool general, const uint8_t*
     return it;
 }
 
+// One sector under layered min-sum (QEC_OPT_MINSUM_SCHEDULE = 1; DESIGN.md section 2, "The layered min-sum form"),
+// regular and general codes.  r[e] is the check->variable message R of edge e as an LLR, +0.0f at the start (an unused
+// slot +0.0f throughout).  An iteration takes the checks in S.order; check c first forms the input of each of its slots
+// -- the left fold of the variable's channel LLR and the R of its other checks as they stand -- and then its own R by
+// decode_sector_minsum's check update.  The posterior of a variable is the same fold over all its checks; decisions,
+// both stop tests, the flags and q_out are stated over the posteriors, and a variable in no check decides 0 and enters
+// no test.  There is no special last iteration.
+int decode_sector_minsum_layered(const CpuSector& S, int n, bool general, const uint8_t* syn, float lam0, const float* llr,
+                                 int scale, int N, int stop, Work& w, bool& conv_out, bool& syn_ok, float* q_out)
+{
+    const int m = S.m, D = S.dc, dvs = S.dv;
+    float* q = w.q.data();  // the current check's inputs
+    float* r = w.r.data();
+    uint8_t* e = w.e.data();
+    const float alpha = (float)scale / 256.0f;
+    auto cdeg = [&](int c) { return general ? (int)S.chk_deg[c] : D; };
+    auto vdeg = [&](int v) { return general ? (int)S.var_deg[v] : dvs; };
+    auto lam = [&](int v) { return llr ? llr[v] : lam0; };
+    std::fill(r, r + (size_t)m * D, 0.0f);
+    std::vector<float>& post = w.post;
+    post.resize(n);
+    bool inside = false;
+    auto posterior = [&]() {
+        inside = false;
+        for (int v = 0; v < n; ++v) {
+            const int dv = vdeg(v);
+            if (dv == 0) { e[v] = 0; post[v] = 0.0f; continue; }
+            const int32_t* ve = S.var_edge.data() + (size_t)v * dvs;
+            float t = lam(v);
+            for (int j = 0; j < dv; ++j) t = t + r[ve[j]];
+            post[v] = t;
+            e[v] = t < 0.0f;
+            inside |= minsum_inside(t);
+        }
+    };
+    auto syndrome_ok = [&]() {
+        for (int c = 0; c < m; ++c) {
+            uint32_t x = 0;
+            for (int k = 0; k < cdeg(c); ++k) x ^= e[S.chk_var[(size_t)c * D + k]];
+            if ((x & 1u) != syn[c]) return false;
+        }
+        return true;
+    };
+    int it = 0;
+    for (int iter = 0; iter < N; ++iter) {
+        ++it;
+        for (int o = 0; o < m; ++o) {
+            const int c = S.order[o], dc = cdeg(c);
+            float* rc = r + (size_t)c * D;
+            uint32_t min1 = kMinSumCap, min2 = kMinSumCap, par = syn[c] != 0;
+            int arg = -1;
+            for (int k = 0; k < dc; ++k) {
+                const int v = S.chk_var[(size_t)c * D + k], self = c * D + k;
+                const int32_t* ve = S.var_edge.data() + (size_t)v * dvs;
+                float t = lam(v);
+                for (int j = 0; j < vdeg(v); ++j)
+                    if (ve[j] != self) t = t + r[ve[j]];
+                q[k] = t;
+                uint32_t b;
+                std::memcpy(&b, &t, sizeof b);
+                const uint32_t a = b & 0x7FFFFFFFu;
+                par ^= b >> 31;
+                if (a < min1) { min2 = min1; min1 = a; arg = k; }
+                else if (a < min2) min2 = a;
+            }
+            for (int i = 0; i < dc; ++i) {
+                uint32_t b, o2;
+                std::memcpy(&b, q + i, sizeof b);
+                const uint32_t mag = i == arg ? min2 : min1;
+                float f;
+                std::memcpy(&f, &mag, sizeof f);
+                f = alpha * f;
+                std::memcpy(&o2, &f, sizeof o2);
+                o2 |= (par ^ (b >> 31)) << 31;
+                std::memcpy(rc + i, &o2, sizeof o2);
+            }
+        }
+        if (stop == QEC_STOP_REF && iter % 10 == 0) {
+            posterior();
+            if (!inside) break;
+        }
+        if (stop == QEC_STOP_SYNDROME) {
+            posterior();
+            if (syndrome_ok()) break;
+        }
+    }
+    posterior();
+    conv_out = !inside;
+    syn_ok = syndrome_ok();
+    if (q_out)
+        for (int c = 0; c < m; ++c)
+            for (int k = 0; k < D; ++k)
+                q_out[(size_t)c * D + k] = k < cdeg(c) ? post[S.chk_var[(size_t)c * D + k]] : 0.0f;
+    return it;
+}
+
 // One sector under the relay form (qec_decoder_set_relay; DESIGN.md section 2, "The relay form"): min-sum legs chained
 // through one fp32 memory per variable.  gam: the sector's rows of the tables, leg l at gam + l * gstride; wt: nullptr
 // (w_v = 1) or the sector's integer weights.  Leg l starts from channel-LLR slots and the memory of leg l - 1 (leg 0:
@@ -680,10 +776,11 @@ void correlated_priors(float p, float* c0, float* c1)
 // without prior the scalar minsum_llr(p').
 // gamma (with minsum; qec_decoder_set_relay): nullptr, or the relay tables [legs][sector][n] for decode_sector_relay, with
 // solutions = S and weight = nullptr (w_v = 1) or the integer weights of the priors, sector X [n] then Z [n].
+// layered (QEC_OPT_MINSUM_SCHEDULE; with minsum and without gamma): 1 = layered min-sum (decode_sector_minsum_layered).
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
                      bool near_hard, const float* prior, int corr, const float* cond, int serial, int minsum,
-                     const float* llr, const float* gamma, int legs, int solutions, const int32_t* weight)
+                     const float* llr, const float* gamma, int legs, int solutions, const int32_t* weight, int layered)
 {
     const CpuPlan& P = *static_cast<const CpuPlan*>(plan);
     const int n = P.n, nb = (n + 7) / 8;
@@ -730,6 +827,9 @@ int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long
                                                                      minsum, maxIter, stop, gamma + (size_t)sec * n, 2 * (size_t)n, legs,
                                                                      solutions, weight ? weight + (size_t)sec * n : nullptr, w, conv,
                                                                      ok, qo)
+                               : minsum && layered ? decode_sector_minsum_layered(S, n, P.general, syn, lam0,
+                                                                                  prior ? llr + (size_t)sec * n : nullptr, minsum,
+                                                                                  maxIter, stop, w, conv, ok, qo)
                                : minsum ? decode_sector_minsum(S, n, P.general, syn, lam0, prior ? llr + (size_t)sec * n : nullptr,
                                                              minsum, maxIter, stop, w, conv, ok, qo)
                                : serial ? decode_sector_serial(S, n, P.general, syn, p, pri, maxIter, stop, w, conv, ok, qo)

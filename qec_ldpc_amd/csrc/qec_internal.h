@@ -151,6 +151,8 @@ struct SparseDecode {
     const float* gamma = nullptr;
     int legs = 0, solutions = 0;
     const int32_t* relay_weight = nullptr;
+    // QEC_OPT_MINSUM_SCHEDULE = 1 (with minsum, gamma = nullptr): the LAYERED kernels, layered min-sum
+    int layered = 0;
 };
 
 // The relay form: the limits of qec_decoder_set_relay

@@ -149,6 +149,34 @@ __device__ __forceinline__ void wave_check_pass(float (&m)[R][L], uint32_t sb, f
     }
 }
 
+// wave_check_pass for one row of the lane's checks (the layered kernels: a layer is a block row): m holds the row's L
+// inputs and receives its L outputs; t = the syndrome entry is non-zero
+template <int L>
+__device__ __forceinline__ void wave_check_row(float (&m)[L], bool t, float alpha)
+{
+    uint32_t min1 = kMinSumCap, min2 = kMinSumCap;
+    uint32_t sgn = t ? 0x80000000u : 0u;  // the parity, kept in the sign position
+    int arg = -1;
+#pragma unroll
+    for (int l = 0; l < L; ++l) {
+        const uint32_t b = __float_as_uint(m[l]);
+        const uint32_t x = b & 0x7FFFFFFFu;
+        sgn ^= b;
+        const bool lt1 = x < min1;
+        min2 = lt1 ? min1 : (x < min2 ? x : min2);
+        arg = lt1 ? l : arg;
+        min1 = lt1 ? x : min1;
+    }
+    sgn &= 0x80000000u;
+    const uint32_t o1 = __float_as_uint(alpha * __uint_as_float(min1));
+    const uint32_t o2 = __float_as_uint(alpha * __uint_as_float(min2));
+#pragma unroll
+    for (int l = 0; l < L; ++l) {
+        const uint32_t b = __float_as_uint(m[l]);
+        m[l] = __uint_as_float((l == arg ? o2 : o1) | ((sgn ^ b) & 0x80000000u));
+    }
+}
+
 // Whether the parities of the lane's R checks over the decisions hd (variable view, bit l) equal their syndrome
 // entries; an entry other than 0 / 1 equals no parity
 template <int R, int L, int SEC, class A>

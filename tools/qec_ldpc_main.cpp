@@ -43,6 +43,8 @@
 //                      in the LLR domain.  Sparse-graph and CPU engines; not with --correlated or --bp-schedule serial
 //   --minsum-scale K   min-sum's factor alpha = K / 256 (QEC_OPT_MINSUM_SCALE, 1 .. 256, default 160); needs
 //                      --bp-method minsum
+//   --minsum-schedule flooding|serial   the order of min-sum's updates (QEC_OPT_MINSUM_SCHEDULE): flooding (default), or
+//                      layered (check-sequential) min-sum.  Sparse-graph and CPU engines; needs --bp-method minsum
 //   --minsum-wave 0|1  the kernels of plain min-sum decodes (QEC_OPT_MINSUM_WAVE): 1 = the register-resident wave
 //                      kernels (circulant codes, P <= 64, a block shape of the runtime-shift table); needs
 //                      --engine sparse and --bp-method minsum
@@ -185,7 +187,8 @@ int main(int argc, char** argv)
     bool relaySolutionsFlag = false;
     int correlated = 0, bpSchedule = 0, bpMethod = 0, minsumScale = 160;
     bool minsumScaleFlag = false;
-    int minsumWave = 0, relayWave = 0;
+    int minsumWave = 0, relayWave = 0, minsumSchedule = 0;
+    bool minsumScheduleFlag = false;
     bool relayWaveFlag = false;
     bool deviceFlag = false, stopFlag = false, batchFlag = false, seedFlag = false, osd = false, osdIterFlag = false;
     bool osdOrderFlag = false, osdScoreFlag = false;
@@ -260,6 +263,10 @@ int main(int argc, char** argv)
                 minsumScale = std::stoi(val);
                 if (minsumScale < 1 || minsumScale > 256) return usage("--minsum-scale: 1 .. 256");
                 minsumScaleFlag = true;
+            } else if (flag == "--minsum-schedule") {
+                if (val != "flooding" && val != "serial") return usage("--minsum-schedule: flooding or serial");
+                minsumSchedule = val == "serial" ? 1 : 0;
+                minsumScheduleFlag = true;
             } else if (flag == "--minsum-wave") {
                 if (val != "0" && val != "1") return usage("--minsum-wave: 0 or 1");
                 minsumWave = val == "1" ? 1 : 0;
@@ -293,6 +300,7 @@ int main(int argc, char** argv)
     if (osdScoreFlag && !osd) return usage("--osd-score needs --osd 0");
     if (bpSchedule && correlated) return usage("--bp-schedule serial and --correlated exclude each other");
     if (minsumScaleFlag && !bpMethod) return usage("--minsum-scale needs --bp-method minsum");
+    if (minsumScheduleFlag && !bpMethod) return usage("--minsum-schedule needs --bp-method minsum");
     if (minsumWave && (!bpMethod || engine != "sparse")) return usage("--minsum-wave 1 needs --engine sparse and --bp-method minsum");
     if (bpMethod && correlated) return usage("--bp-method minsum and --correlated exclude each other");
     if (bpMethod && bpSchedule) return usage("--bp-method minsum and --bp-schedule serial exclude each other");
@@ -349,6 +357,7 @@ int main(int argc, char** argv)
             if (correlated) decoder.SetCorrelated(correlated);
             if (bpSchedule) decoder.SetBpSchedule(bpSchedule);
             if (bpMethod) decoder.SetBpMethod(bpMethod, minsumScale);
+            if (minsumSchedule) decoder.SetMinSumSchedule(minsumSchedule);
             if (minsumWave) decoder.SetMinSumWave(minsumWave);
             if (relayLegs) decoder.SetRelay(gammaX, gammaZ, relayLegs, relaySolutions);
             if (relayWave) decoder.SetRelayWave(relayWave);
@@ -380,6 +389,7 @@ int main(int argc, char** argv)
             if (correlated) c->SetCorrelated(correlated);
             if (bpSchedule) c->SetBpSchedule(bpSchedule);
             if (bpMethod) c->SetBpMethod(bpMethod, minsumScale);
+            if (minsumSchedule) c->SetMinSumSchedule(minsumSchedule);
             if (relayLegs) c->SetRelay(gammaX, gammaZ, relayLegs, relaySolutions);
             std::cout << "Engine: CPU (" << std::thread::hardware_concurrency() << " threads)" << std::endl;
         } else {
@@ -392,6 +402,7 @@ int main(int argc, char** argv)
             if (correlated) g->SetCorrelated(correlated);
             if (bpSchedule) g->SetBpSchedule(bpSchedule);
             if (bpMethod) g->SetBpMethod(bpMethod, minsumScale);
+            if (minsumSchedule) g->SetMinSumSchedule(minsumSchedule);
             if (minsumWave) g->SetMinSumWave(minsumWave);
             if (relayLegs) g->SetRelay(gammaX, gammaZ, relayLegs, relaySolutions);
             if (relayWave) g->SetRelayWave(relayWave);
