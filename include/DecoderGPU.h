@@ -200,6 +200,16 @@ public:
         check(qec_decoder_set_relay(dec_, gammaX.data(), gammaZ.data(), legs, solutions));
     }
     void ClearRelay() { check(qec_decoder_set_relay(dec_, nullptr, nullptr, 0, 0)); }
+    // Noisy syndromes (qec_decoder_set_syndrome_priors): qX [numEqsX], qZ [numEqsZ] = the probability that each check's
+    // measured bit is flipped.  Under SetBpMethod(1) every decode then treats the syndrome bits as soft; not together
+    // with SetRelay or SetOsd, which throw the library's message (as this call does after them).
+    void SetSyndromePriors(const std::vector<float>& qX, const std::vector<float>& qZ)
+    {
+        if (qX.size() != (size_t)_code.numEqsX || qZ.size() != (size_t)_code.numEqsZ)
+            throw std::string("SetSyndromePriors: qX needs numEqsX and qZ numEqsZ entries");
+        check(qec_decoder_set_syndrome_priors(dec_, qX.data(), qZ.data()));
+    }
+    void ClearSyndromePriors() { check(qec_decoder_set_syndrome_priors(dec_, nullptr, nullptr)); }
     // Per-qubit Pauli channel (qec_decoder_set_pauli_channel): qubit v suffers X, Y or Z with probabilities pX[v],
     // pY[v], pZ[v] (n entries each; Y sets both bits).  Installs the marginal priors, the conditional tables of
     // SetCorrelated and the noise of the device Monte-Carlo run; a later SetPriors or ClearPriors drops it.

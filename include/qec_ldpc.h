@@ -460,6 +460,7 @@ enum {
                                       (QEC_OPT_MINSUM_SCHEDULE = 1, then beside QEC_PATH_MINSUM) */
     QEC_PATH_MINSUM = 2048,        /* scaled min-sum BP (QEC_OPT_BP_METHOD = 1) */
     QEC_PATH_RELAY = 4096,         /* ... as a relay of memory min-sum legs (qec_decoder_set_relay) */
+    QEC_PATH_SOFT = 16384,         /* ... under syndrome priors (qec_decoder_set_syndrome_priors) */
     QEC_PATH_WAVE = 8192           /* ... by the register-resident wave kernels (QEC_OPT_MINSUM_WAVE = 1, or
                                       QEC_OPT_RELAY_WAVE = 1 on a relay decode) */
 };
@@ -552,6 +553,31 @@ int qec_decoder_get_minsum_llr(const qec_decoder* dec, float* llrX, float* llrZ)
 int qec_decoder_set_relay(qec_decoder* dec, const float* gammaX, const float* gammaZ, int legs, int solutions);
 /* *legs and *solutions (0 and 0 without tables; a NULL pointer is skipped) and, where given, the tables ([legs][n]). */
 int qec_decoder_get_relay(const qec_decoder* dec, float* gammaX, float* gammaZ, int* legs, int* solutions);
+/* Noisy syndromes ("The soft-syndrome form"): qX [numEqsX], qZ [numEqsZ] are HOST arrays, q_c = the
+ * probability that the measured bit of check c is flipped.  Every entry in [0, 1] (NaN is not): QEC_ERR_ARG otherwise,
+ * and for exactly one NULL pointer; the handle is then unchanged.  (NULL, NULL) clears: the handle behaves as one that
+ * never had them.
+ *   - Decoding (H, s) under syndrome priors is decoding the extended code [H | I] whose variable n + c sits in check c
+ *     only, with channel LLR mu_c = qec_minsum_llr(q_c); the outputs are those of the first n variables and the real
+ *     slots of H.  Natively: check c has one virtual input mu_c in every check pass, the virtual slot's output rho_c gives
+ *     the measurement decision f_c = (mu_c + rho_c < 0.0f) (before the first check pass f_c = mu_c < 0.0f), and the
+ *     syndrome test (the syndrome stop and SYNDROME_FAIL) compares (parity of the row's decisions) ^ f_c with the entry.
+ *     The inside tests (the reference stop, CONVERGENCE_FAIL) look at the data slots / data posteriors only.  With every
+ *     q_c = 0 every output bit equals the call without syndrome priors.
+ *   - They are a form of plain min-sum, flooding or layered (QEC_OPT_MINSUM_SCHEDULE), on the sparse-graph engine (the
+ *     SOFT kernels of bp_sparse.hip, or with QEC_OPT_MINSUM_WAVE = 1 those of bp_wave_minsum.hip) and the CPU engine.  Every decode entry point of such a handle decodes under them
+ *     (qec_decode_batch*, the _dev and packed forms, qec_get_statistics, qec_monte_carlo) with unchanged output layouts,
+ *     and QEC_PATH_SOFT is then set in QEC_OPT_LAST_PATH; qec_decoder_describe appends " [soft syndrome]".
+ *   - Refusals, QEC_ERR_UNSUPPORTED with the handle unchanged, whichever call comes second: they need
+ *     QEC_OPT_BP_METHOD = 1 and that option refuses 0 while they are set; they and relay tables (qec_decoder_set_relay)
+ *     refuse each other; they and QEC_OPT_OSD = 1 refuse each other (OSD solves H e = s exactly; qec_osd and qec_osd_dev
+ *     as separate calls are untouched); a wave-circulant handle refuses them.
+ *   - Synchronous.  The first set allocates the device copy, later sets rewrite it in place; the _dev entry points
+ *     allocate nothing, and a captured graph replayed after a later set decodes with the new values.  A group passes
+ *     the tables to every part. */
+int qec_decoder_set_syndrome_priors(qec_decoder* dec, const float* qX, const float* qZ);
+/* 1 and the arrays filled (a NULL array is skipped) if syndrome priors are set, 0 if not. */
+int qec_decoder_get_syndrome_priors(const qec_decoder* dec, float* qX, float* qZ);
 /* The scalar tables of QEC_OPT_CORRELATED for depolarising noise of strength p: *c1 = P(other bit | this bit
  * set) = 0.5f and *c0 = P(other bit | this bit clear) = (p / 3.0f) / (1.0f - 2.0f / 3.0f * p), every operation
  * in fp32.  Both engines decode with exactly these values. */
@@ -605,6 +631,28 @@ int qec_decode_batch_dev(qec_decoder* dec, const uint8_t* sX, const uint8_t* sZ,
                          float errorProbability, int maxIterations, int stop,
                          uint8_t* eX, uint8_t* eZ, uint8_t* flags, int32_t* iters, float* q_final,
                          void* stream);
+/* qec_decode_batch and qec_decode_batch_dev with the measurement decisions of a handle with syndrome priors
+ * (qec_decoder_set_syndrome_priors) as two further nullable outputs: fX [B x numEqsX] and fZ [B x numEqsZ] bytes,
+ * f = 1 where the decoder takes the measured syndrome bit as flipped.  Any min-sum handle (QEC_OPT_BP_METHOD = 1;
+ * QEC_ERR_UNSUPPORTED otherwise); without syndrome priors f is all zero.  Every other output equals the plain call's.
+ * The _dev form allocates nothing and is graph-capturable. */
+int qec_decode_batch_soft(qec_decoder* dec, const uint8_t* sX, const uint8_t* sZ, size_t B,
+                          float errorProbability, int maxIterations, int stop,
+                          uint8_t* eX, uint8_t* eZ, uint8_t* fX, uint8_t* fZ, uint8_t* flags, int32_t* iters,
+                          float* q_final);
+int qec_decode_batch_soft_dev(qec_decoder* dec, const uint8_t* sX, const uint8_t* sZ, size_t B,
+                              float errorProbability, int maxIterations, int stop,
+                              uint8_t* eX, uint8_t* eZ, uint8_t* fX, uint8_t* fZ, uint8_t* flags, int32_t* iters,
+                              float* q_final, void* stream);
+/* The measurement-error channel of a handle with syndrome priors, in place on DEVICE byte syndromes sX [B x numEqsX],
+ * sZ [B x numEqsZ]; fX / fZ (nullable, same shapes) receive the flips.  Sample b (index start + b) makes Philox4x32-10
+ * calls k = 0, 1, ... with counter (b lo, b hi, k, 0xA54FF53A) and key (seed lo, seed hi); word 4k + j is output j of
+ * call k; X check c reads word c, Z check c word numEqsX + c; the bit is flipped iff word < floor(q 2^32), evaluated in
+ * double from the float as a 64-bit value (q = 1 always flips, q = 0 never).  Any shard of the index space can be drawn
+ * alone.  QEC_ERR_ARG without syndrome priors.  On such a handle qec_sample_syndrome_dev and qec_monte_carlo apply
+ * these flips after the syndrome, with the same seed and sample index (errp stays the data error). */
+int qec_flip_syndrome_dev(qec_decoder* dec, uint64_t seed, uint64_t start, size_t B, uint8_t* sX, uint8_t* sZ,
+                          uint8_t* fX, uint8_t* fZ, void* stream);
 /* Bit-packed output (SURVEY.md 8(d)'s I/O model): the decode kernel writes one decision record
  * per syndrome instead of eX / eZ / flags: records is B x QEC_RECORD_BYTES(n) bytes, per syndrome
  * eX packed (ceil(n/8) bytes, bit j of byte k = qubit 8k + j, padding bits 0), then eZ packed,

@@ -41,7 +41,7 @@ MINSUM_SCHEDULE = {"flooding": 0, "layered": 1}
 # QEC_PATH_* bits of QEC_OPT_LAST_PATH (include/qec_ldpc.h): the launch sequence of the last decode call
 PATH = {"ordered": 1, "sector_order": 2, "split_waves": 4, "sector_launches": 8, "triage": 16, "bit_rows": 32,
         "sparse": 64, "records": 128, "osd": 256, "correlated": 512, "serial": 1024,
-        "minsum": 2048, "relay": 4096, "wave": 8192}
+        "minsum": 2048, "relay": 4096, "wave": 8192, "soft": 16384}
 
 # every symbol include/qec_ldpc.h declares
 EXPORTS = (
@@ -59,6 +59,8 @@ EXPORTS = (
     "qec_decoder_set_priors", "qec_decoder_get_priors", "qec_decoder_get_osd_weights", "qec_sample_independent_dev",
     "qec_correlated_priors", "qec_minsum_llr", "qec_decoder_get_minsum_llr", "qec_decoder_set_pauli_channel", "qec_decoder_get_pauli_channel",
     "qec_decoder_set_relay", "qec_decoder_get_relay",
+    "qec_decoder_set_syndrome_priors", "qec_decoder_get_syndrome_priors",
+    "qec_decode_batch_soft", "qec_decode_batch_soft_dev", "qec_flip_syndrome_dev",
     "qec_decoder_get_conditional_priors", "qec_sample_pauli_dev",
     "qec_decode_batch", "qec_decode_batch_dev", "qec_decode_batch_packed", "qec_decode_batch_packed_dev",
     "qec_decode_bits_packed_dev",
@@ -169,6 +171,11 @@ def lib():
             "qec_decoder_get_minsum_llr": (i, [vp, vp, vp]),
             "qec_decoder_set_relay": (i, [vp, vp, vp, i, i]),
             "qec_decoder_get_relay": (i, [vp, vp, vp, vp, vp]),
+            "qec_decoder_set_syndrome_priors": (i, [vp, vp, vp]),
+            "qec_decoder_get_syndrome_priors": (i, [vp, vp, vp]),
+            "qec_decode_batch_soft": (i, [vp, vp, vp, sz, f, i, i, vp, vp, vp, vp, vp, vp, vp]),
+            "qec_decode_batch_soft_dev": (i, [vp, vp, vp, sz, f, i, i, vp, vp, vp, vp, vp, vp, vp, vp]),
+            "qec_flip_syndrome_dev": (i, [vp, ctypes.c_uint64, ctypes.c_uint64, sz, vp, vp, vp, vp, vp]),
             "qec_decoder_set_pauli_channel": (i, [vp, vp, vp, vp]),
             "qec_decoder_get_pauli_channel": (i, [vp, vp, vp, vp]),
             "qec_decoder_get_conditional_priors": (i, [vp, vp, vp, vp, vp]),
@@ -650,6 +657,37 @@ class DecoderGPU:
         _check(lib().qec_decoder_get_relay(self._h, _ptr(gX), _ptr(gZ), None, None), "qec_decoder_get_relay")
         return gX, gZ, sol.value
 
+    def set_syndrome_priors(self, qX, qZ):
+        """Noisy syndromes (qec_decoder_set_syndrome_priors): qX [numEqsX], qZ [numEqsZ] = the probability that each
+        check's measured bit is flipped (arrays, or a scalar for every check); (None, None) clears.  Every min-sum decode
+        of the handle then treats the syndrome bits as soft: decode_batch(..., want_flips=True) also returns which
+        measured bits the decoder took as flipped.  Needs set_option("bp_method", 1); refused beside relay tables
+        and "osd" = 1, and by a wave-circulant decoder."""
+        if (qX is None) != (qZ is None):
+            raise QecError("set_syndrome_priors: qX and qZ must both be given, or both be None (clear)")
+        if qX is None:
+            _check(lib().qec_decoder_set_syndrome_priors(self._h, None, None), "qec_decoder_set_syndrome_priors")
+            return
+        arrs = []
+        for name, q, m in (("qX", qX, self.code.numEqsX), ("qZ", qZ, self.code.numEqsZ)):
+            a = np.asarray(q, dtype=np.float32)
+            if a.ndim == 0:
+                a = np.full(m, a, dtype=np.float32)
+            if a.shape != (m,):
+                raise QecError("set_syndrome_priors: %s must be a scalar or have shape [%d], has shape %s" % (name, m, a.shape))
+            arrs.append(np.ascontiguousarray(a))
+        _check(lib().qec_decoder_set_syndrome_priors(self._h, _ptr(arrs[0]), _ptr(arrs[1])),
+               "qec_decoder_set_syndrome_priors")
+
+    def get_syndrome_priors(self):
+        """(qX, qZ) as float32 arrays (qec_decoder_get_syndrome_priors), or None when none are set."""
+        qX = np.empty(self.code.numEqsX, dtype=np.float32)
+        qZ = np.empty(self.code.numEqsZ, dtype=np.float32)
+        rc = lib().qec_decoder_get_syndrome_priors(self._h, _ptr(qX), _ptr(qZ))
+        if rc < 0:
+            raise QecError("qec_decoder_get_syndrome_priors failed (%d): %s" % (rc, last_error()))
+        return (qX, qZ) if rc == 1 else None
+
     def last_path(self):
         """The launch sequence of this handle's last decode call (QEC_OPT_LAST_PATH) as a set of
         PATH names, e.g. {"bit_rows", "records", "ordered", "sector_order", "sector_launches"}."""
@@ -661,9 +699,11 @@ class DecoderGPU:
         return record_bytes(self.code.n)
 
     # ---- host buffers ------------------------------------------------------------------
-    def decode_batch(self, sX, sZ, p, max_iter, stop="ref", want_iters=False, want_q=False):
+    def decode_batch(self, sX, sZ, p, max_iter, stop="ref", want_iters=False, want_q=False, want_flips=False):
         """Host-buffer batch decode -> (eX, eZ, flags, iters|None, q|None).  With priors set (set_priors)
-        BP uses them and p is not used, here and in every other decode call."""
+        BP uses them and p is not used, here and in every other decode call.  want_flips (a min-sum handle;
+        qec_decode_batch_soft): two further items fX [B, numEqsX], fZ [B, numEqsZ], the measured syndrome bits the
+        decoder took as flipped (all zero without set_syndrome_priors)."""
         c = self.code
         sX = np.atleast_2d(sX)
         B = sX.shape[0]
@@ -674,6 +714,13 @@ class DecoderGPU:
         flags = np.empty(B, dtype=np.uint8)
         iters = np.empty((B, 2), dtype=np.int32) if want_iters else None
         q = np.empty((B, (c.numEqsX + c.numEqsZ) * c.stride), dtype=np.float32) if want_q else None
+        if want_flips:
+            fX = np.empty((B, c.numEqsX), dtype=np.uint8)
+            fZ = np.empty((B, c.numEqsZ), dtype=np.uint8)
+            _check(lib().qec_decode_batch_soft(self._h, _ptr(sX), _ptr(sZ), B, float(p), int(max_iter), STOP[stop],
+                                               _ptr(eX), _ptr(eZ), _ptr(fX), _ptr(fZ), _ptr(flags), _ptr(iters), _ptr(q)),
+                   "qec_decode_batch_soft")
+            return eX, eZ, flags, iters, q, fX, fZ
         _check(lib().qec_decode_batch(self._h, _ptr(sX), _ptr(sZ), B, float(p), int(max_iter), STOP[stop],
                                       _ptr(eX), _ptr(eZ), _ptr(flags), _ptr(iters), _ptr(q)), "qec_decode_batch")
         return eX, eZ, flags, iters, q
@@ -781,6 +828,40 @@ class DecoderGPU:
                 self._t(iters, "iters", torch.int32, (B, 2), True),
                 self._t(q, "q", torch.float32, (B, (c.numEqsX + c.numEqsZ) * c.stride), True))
         return self._issue("qec_decode_batch_dev", (self._h, *args, ctypes.c_void_p(self._stream(stream))))
+
+    def decode_batch_soft_dev(self, sX, sZ, p, max_iter, stop, eX, eZ, flags, fX=None, fZ=None, iters=None, q=None,
+                              stream=None):
+        """decode_batch_dev of a min-sum handle with the measurement decisions of set_syndrome_priors as optional
+        outputs fX [B, numEqsX], fZ [B, numEqsZ] (uint8; all zero without syndrome priors).  No allocation
+        (graph-capturable)."""
+        import torch
+        self._single("decode_batch_soft_dev")
+        c = self.code
+        B = sX.shape[0]
+        u8 = torch.uint8
+        args = (self._t(sX, "sX", u8, (B, c.numEqsX)), self._t(sZ, "sZ", u8, (B, c.numEqsZ)),
+                B, float(p), int(max_iter), STOP[stop],
+                self._t(eX, "eX", u8, (B, c.n)), self._t(eZ, "eZ", u8, (B, c.n)),
+                self._t(fX, "fX", u8, (B, c.numEqsX), True), self._t(fZ, "fZ", u8, (B, c.numEqsZ), True),
+                self._t(flags, "flags", u8, (B,)),
+                self._t(iters, "iters", torch.int32, (B, 2), True),
+                self._t(q, "q", torch.float32, (B, (c.numEqsX + c.numEqsZ) * c.stride), True))
+        return self._issue("qec_decode_batch_soft_dev", (self._h, *args, ctypes.c_void_p(self._stream(stream))))
+
+    def flip_syndrome_dev(self, seed, start, sX, sZ, fX=None, fZ=None, stream=None):
+        """The measurement-error channel of set_syndrome_priors, in place on device byte syndromes of samples
+        [start, start + B) (qec_flip_syndrome_dev): X check c is flipped iff word c of sample b's Philox stream
+        < floor(qX[c] 2^32), Z check c from word numEqsX + c; fX / fZ (optional) receive the flips."""
+        import torch
+        self._single("flip_syndrome_dev")
+        c = self.code
+        B = sX.shape[0]
+        u8 = torch.uint8
+        _check(lib().qec_flip_syndrome_dev(self._h, seed & (2 ** 64 - 1), start, B,
+                                           self._t(sX, "sX", u8, (B, c.numEqsX)), self._t(sZ, "sZ", u8, (B, c.numEqsZ)),
+                                           self._t(fX, "fX", u8, (B, c.numEqsX), True),
+                                           self._t(fZ, "fZ", u8, (B, c.numEqsZ), True),
+                                           ctypes.c_void_p(self._stream(stream))), "qec_flip_syndrome_dev")
 
     def decode_batch_packed_dev(self, sX, sZ, p, max_iter, stop, records, iters=None, q=None, stream=None):
         """Device-buffer batch decode into packed decision records [B, record_bytes()] (uint8)."""

@@ -827,6 +827,96 @@ __device__ __forceinline__ void sp_minsum_check(float* __restrict__ m, int dc, u
     }
 }
 
+// ---- SOFT: min-sum under syndrome priors (qec_decoder_set_syndrome_priors; DESIGN.md section 2, "The soft-syndrome
+// form").  The SOFT instantiations of the MINSUM and LAYERED bodies; the others do not change.  Check c has one virtual
+// input mu[c], the channel LLR of its measurement-error variable, read from the handle's table (mX + mZ floats that every
+// workgroup shares).  The syndrome byte of the workspace holds the entry as 0, 1 or 2 = any other value in bits 0-1 and
+// the measurement decision f_c in bit 2 (a general code's degree is read from chkDeg instead): the thread that updates
+// check c rewrites the byte, the syndrome tests XOR the bit into the row's parity.  No further workspace.
+struct SoftArgs {
+    GeneralArgs g;           // chkDeg = nullptr for a regular code
+    const float* mu;         // mX + mZ channel LLRs of the measurement-error variables
+    uint8_t* fX;             // nullable: [B][mX] measurement decisions out
+    uint8_t* fZ;             // nullable: [B][mZ]
+};
+
+__device__ __forceinline__ void sp_soft_load_syndromes(const SparseArgs& a, const float* __restrict__ mu, long long b,
+                                                       uint8_t* syn)
+{
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int mX = a.mX, mZ = a.mZ, m = mX + mZ;
+    for (int c = tid; c < m; c += nt) {
+        const uint32_t s = c < mX ? a.sX[b * mX + c] : a.sZ[b * mZ + (c - mX)];
+        syn[c] = (uint8_t)((s > 1u ? 2u : s) | (mu[c] < 0.0f ? 4u : 0u));  // f of N = 0 (layered: of R = +0.0f)
+    }
+}
+
+// sp_minsum_check with the virtual input: it enters the minima and the sign XOR ahead of the row (the outputs do not
+// depend on an input's position); returns f = mu + rho < 0, rho the virtual slot's own output
+template <bool GENERAL>
+__device__ __forceinline__ bool sp_soft_check(float* __restrict__ m, int dc, int deg, uint32_t sd, float mu, float alpha)
+{
+    const uint32_t mb = __float_as_uint(mu), ma = mb & 0x7FFFFFFFu;
+    const bool virt = ma < kMinSumCap;
+    uint32_t min1 = virt ? ma : kMinSumCap, min2 = kMinSumCap;
+    uint32_t par = ((sd & 3u) != 0u) ^ (mb >> 31);
+    int arg = virt ? -2 : -1;
+    for (int k = 0; k < dc; ++k) {
+        const uint32_t b = __float_as_uint(m[k]);
+        const uint32_t a = b & 0x7FFFFFFFu;
+        par ^= b >> 31;
+        const bool lt1 = a < min1, lt2 = a < min2;
+        min2 = lt1 ? min1 : lt2 ? a : min2;
+        arg = lt1 ? k : arg;
+        min1 = lt1 ? a : min1;
+    }
+    const uint32_t o1 = __float_as_uint(alpha * __uint_as_float(min1));
+    const uint32_t o2 = __float_as_uint(alpha * __uint_as_float(min2));
+    for (int i = 0; i < dc; ++i) {
+        const uint32_t b = __float_as_uint(m[i]);
+        const uint32_t o = (i == arg ? o2 : o1) | ((par ^ (b >> 31)) << 31);
+        m[i] = __uint_as_float(!GENERAL || i < deg ? o : kMinSumCap);  // an unused slot keeps K
+    }
+    const float rho = __uint_as_float((arg == -2 ? o2 : o1) | ((par ^ (mb >> 31)) << 31));
+    const float postm = mu + rho;
+    return postm < 0.0f;
+}
+
+// sp_syndrome_fails under SOFT: check c is satisfied iff (the row's parity) ^ f_c equals its syndrome entry exactly
+template <bool GENERAL>
+__device__ __forceinline__ void sp_soft_syndrome_fails(const SparseArgs& a, const uint8_t* syn, const uint8_t* hd, bool& bx,
+                                                       bool& bz)
+{
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int mX = a.mX, m = mX + a.mZ, dc = a.dc;
+    for (int c = tid; c < m; c += nt) {
+        const bool z = c >= mX;
+        const int32_t* row = a.chkVar + (size_t)c * dc;
+        const uint8_t* h = hd + (z ? a.n : 0);
+        const uint32_t sd = syn[c];
+        uint32_t x = (sd >> 2) & 1u;
+        for (int k = 0; k < dc; ++k) {
+            const int v = row[k];
+            x ^= (!GENERAL || v >= 0) ? (uint32_t)h[v < 0 ? 0 : v] : 0u;
+        }
+        if (x != (sd & 3u)) {
+            if (z) bz = true; else bx = true;
+        }
+    }
+}
+
+// The measurement decisions of syndrome pair b out, where requested
+__device__ __forceinline__ void sp_soft_store_flips(const SparseArgs& a, long long b, const uint8_t* syn, uint8_t* fX,
+                                                    uint8_t* fZ)
+{
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int mX = a.mX, mZ = a.mZ;
+    if (fX != nullptr)
+        for (int c = tid; c < mX; c += nt) fX[b * mX + c] = (syn[c] >> 2) & 1u;
+    if (fZ != nullptr)
+        for (int c = tid; c < mZ; c += nt) fZ[b * mZ + c] = (syn[mX + c] >> 2) & 1u;
+}
+
 // One variable's update from its channel LLR; returns its decision (posterior < 0; a variable in no check decides 0)
 template <int MAXDV, bool GENERAL>
 __device__ __forceinline__ bool sp_minsum_var(float* __restrict__ msg, const int32_t* __restrict__ ve, int dv, float lam,
@@ -873,8 +963,10 @@ __device__ __forceinline__ bool sp_minsum_var(float* __restrict__ msg, const int
     return idx[0] >= 0 && post < 0.0f;
 }
 
-template <int STOP, int MAXDC, int MAXDV, bool GENERAL>
-__device__ __forceinline__ void sp_minsum_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws)
+template <int STOP, int MAXDC, int MAXDV, bool GENERAL, bool SOFT = false>
+__device__ __forceinline__ void sp_minsum_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws,
+                                                 const float* __restrict__ mu = nullptr, uint8_t* fX = nullptr,
+                                                 uint8_t* fZ = nullptr)
 {
     const int tid = threadIdx.x, nt = blockDim.x;
     const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
@@ -896,7 +988,8 @@ __device__ __forceinline__ void sp_minsum_decode(const SparseArgs& a, const uint
     };
 
     for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
-        sp_load_syndromes<GENERAL>(a, chkDeg, b, syn);
+        if constexpr (SOFT) sp_soft_load_syndromes(a, mu, b, syn);
+        else sp_load_syndromes<GENERAL>(a, chkDeg, b, syn);
         for (int e = tid; e < E; e += nt) {
             const int v = (GENERAL || tab) ? a.chkVar[e] : 0;
             float x = __uint_as_float(kMinSumCap);  // an unused slot of a general code
@@ -918,7 +1011,13 @@ __device__ __forceinline__ void sp_minsum_decode(const SparseArgs& a, const uint
             itZ += actZ;
             for (int c = tid; c < m; c += nt) {
                 if (c < mX ? !actX : !actZ) continue;
-                sp_minsum_check<GENERAL>(msg + (size_t)c * dc, dc, syn[c], alpha);
+                if constexpr (SOFT) {
+                    const uint32_t sd = syn[c];
+                    const bool f = sp_soft_check<GENERAL>(msg + (size_t)c * dc, dc, GENERAL ? (int)chkDeg[c] : dc, sd, mu[c], alpha);
+                    syn[c] = (uint8_t)((sd & 3u) | (f ? 4u : 0u));
+                } else {
+                    sp_minsum_check<GENERAL>(msg + (size_t)c * dc, dc, syn[c], alpha);
+                }
             }
             __syncthreads();
             for (int v = tid; v < 2 * n; v += nt) {
@@ -936,7 +1035,8 @@ __device__ __forceinline__ void sp_minsum_decode(const SparseArgs& a, const uint
                 if (actZ && !anyz) actZ = false;
             } else if (STOP == QEC_STOP_SYNDROME) {
                 bool bx = false, bz = false;
-                sp_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
+                if constexpr (SOFT) sp_soft_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
+                else sp_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
                 const bool badx = __syncthreads_or(bx), badz = __syncthreads_or(bz);
                 if (actX && !badx) actX = false;
                 if (actZ && !badz) actZ = false;
@@ -951,7 +1051,12 @@ __device__ __forceinline__ void sp_minsum_decode(const SparseArgs& a, const uint
         }
         const bool convFailX = __syncthreads_or(bx), convFailZ = __syncthreads_or(bz);
         bool sx = false, sz = false;
-        sp_syndrome_fails<GENERAL>(a, syn, hd, sx, sz);
+        if constexpr (SOFT) {
+            sp_soft_syndrome_fails<GENERAL>(a, syn, hd, sx, sz);
+            sp_soft_store_flips(a, b, syn, fX, fZ);
+        } else {
+            sp_syndrome_fails<GENERAL>(a, syn, hd, sx, sz);
+        }
         const bool synFailX = __syncthreads_or(sx), synFailZ = __syncthreads_or(sz);
         if (a.q != nullptr)
             for (int e = tid; e < E; e += nt) a.q[b * E + e] = (!GENERAL || a.chkVar[e] >= 0) ? msg[e] : 0.0f;
@@ -987,8 +1092,10 @@ __device__ __forceinline__ float sp_layered_fold(const float* __restrict__ msg, 
     return t;
 }
 
-template <int STOP, int MAXDC, int MAXDV, bool GENERAL>
-__device__ __forceinline__ void sp_layered_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws)
+template <int STOP, int MAXDC, int MAXDV, bool GENERAL, bool SOFT = false>
+__device__ __forceinline__ void sp_layered_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws,
+                                                  const float* __restrict__ mu = nullptr, uint8_t* fX = nullptr,
+                                                  uint8_t* fZ = nullptr)
 {
     const int tid = threadIdx.x, nt = blockDim.x;
     const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
@@ -1020,7 +1127,8 @@ __device__ __forceinline__ void sp_layered_decode(const SparseArgs& a, const uin
     };
 
     for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
-        sp_load_syndromes<GENERAL>(a, chkDeg, b, syn);
+        if constexpr (SOFT) sp_soft_load_syndromes(a, mu, b, syn);
+        else sp_load_syndromes<GENERAL>(a, chkDeg, b, syn);
         for (int e = tid; e < E; e += nt)
             msg[e] = (!GENERAL || a.chkVar[e] >= 0) ? 0.0f : __uint_as_float(kMinSumCap);
         __syncthreads();
@@ -1049,7 +1157,13 @@ __device__ __forceinline__ void sp_layered_decode(const SparseArgs& a, const uin
                 // the layer's checks, a thread per check: the row becomes the check's R
                 for (int i = tid; i < nx + nz; i += nt) {
                     const int c = a.layOrder[i < nx ? x0 + i : z0 + (i - nx)];
-                    sp_minsum_check<GENERAL>(msg + (size_t)c * dc, dc, syn[c], alpha);
+                    if constexpr (SOFT) {
+                        const uint32_t sd = syn[c];
+                        const bool f = sp_soft_check<GENERAL>(msg + (size_t)c * dc, dc, GENERAL ? (int)chkDeg[c] : dc, sd, mu[c], alpha);
+                        syn[c] = (uint8_t)((sd & 3u) | (f ? 4u : 0u));
+                    } else {
+                        sp_minsum_check<GENERAL>(msg + (size_t)c * dc, dc, syn[c], alpha);
+                    }
                 }
                 __syncthreads();
             }
@@ -1064,7 +1178,8 @@ __device__ __forceinline__ void sp_layered_decode(const SparseArgs& a, const uin
                 posterior(actX, actZ, bx, bz);
                 __syncthreads();
                 bx = bz = false;
-                sp_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
+                if constexpr (SOFT) sp_soft_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
+                else sp_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
                 const bool badx = __syncthreads_or(bx), badz = __syncthreads_or(bz);
                 if (actX && !badx) actX = false;
                 if (actZ && !badz) actZ = false;
@@ -1079,7 +1194,12 @@ __device__ __forceinline__ void sp_layered_decode(const SparseArgs& a, const uin
             if (v >= n) a.eZ[b * n + (v - n)] = hd[v]; else a.eX[b * n + v] = hd[v];
         }
         bool sx = false, sz = false;
-        sp_syndrome_fails<GENERAL>(a, syn, hd, sx, sz);
+        if constexpr (SOFT) {
+            sp_soft_syndrome_fails<GENERAL>(a, syn, hd, sx, sz);
+            sp_soft_store_flips(a, b, syn, fX, fZ);
+        } else {
+            sp_syndrome_fails<GENERAL>(a, syn, hd, sx, sz);
+        }
         const bool synFailX = __syncthreads_or(sx), synFailZ = __syncthreads_or(sz);
         if (a.q != nullptr)
             for (int e = tid; e < E; e += nt) {
@@ -1381,10 +1501,21 @@ __global__ __launch_bounds__(kSparseThreads) void bp_layered_kernel(const Genera
     sp_layered_decode<STOP, MAXDC, MAXDV, GENERAL>(ga.s, ga.chkDeg, ws);
 }
 
+// Min-sum under syndrome priors: one entry for both routes and both schedules (SoftArgs)
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL, bool LAYERED>
+__global__ __launch_bounds__(kSparseThreads) void bp_soft_kernel(const SoftArgs sa)
+{
+    const SparseArgs& a = sa.g.s;
+    uint8_t* ws = LDS ? sp_lds : a.scratch + (long long)blockIdx.x * a.ws_bytes;
+    if constexpr (LAYERED) sp_layered_decode<STOP, MAXDC, MAXDV, GENERAL, true>(a, sa.g.chkDeg, ws, sa.mu, sa.fX, sa.fZ);
+    else sp_minsum_decode<STOP, MAXDC, MAXDV, GENERAL, true>(a, sa.g.chkDeg, ws, sa.mu, sa.fX, sa.fZ);
+}
+
 // ---- plan ------------------------------------------------------------------
 // The kernels of one shape, by variant and stop rule.  SERIAL takes priors as a runtime branch, CORR, MINSUM, RELAY and
 // LAYERED too.
-enum { kScalar = 0, kPriors = 1, kCorr = 2, kSerial = 3, kMinSum = 4, kRelay = 5, kLayered = 6, kVariants = 7 };
+enum { kScalar = 0, kPriors = 1, kCorr = 2, kSerial = 3, kMinSum = 4, kRelay = 5, kLayered = 6, kSoftMinSum = 7,
+       kSoftLayered = 8, kVariants = 9 };
 using SparseKernels = const void* [kVariants][3];
 
 template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL, bool PRIORS, bool CORR, bool SERIAL, bool MINSUM = false>
@@ -1405,6 +1536,8 @@ static void sparse_kernels_of_stop(SparseKernels& fn)
     fn[kMinSum][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, false, false, true>();
     fn[kRelay][STOP] = reinterpret_cast<const void*>(&bp_relay_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL>);
     fn[kLayered][STOP] = reinterpret_cast<const void*>(&bp_layered_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL>);
+    fn[kSoftMinSum][STOP] = reinterpret_cast<const void*>(&bp_soft_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false>);
+    fn[kSoftLayered][STOP] = reinterpret_cast<const void*>(&bp_soft_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, true>);
 }
 
 template <int MAXDC, int MAXDV, bool LDS, bool GENERAL>
@@ -1667,6 +1800,18 @@ int launch_decode_sparse(void* plan, const SparseDecode& d, hipStream_t stream)
     if (d.minsum && d.gamma == nullptr && d.layered) {  // plain min-sum under QEC_OPT_MINSUM_SCHEDULE = 1: the LAYERED kernels
         args[0] = &ga;
         variant = kLayered;
+    }
+    SoftArgs sa{};
+    if (d.mu != nullptr) {  // syndrome priors (qec_decoder_set_syndrome_priors): the SOFT kernels of plain min-sum
+        if (!d.minsum || d.gamma != nullptr)
+            return fail(QEC_ERR_UNSUPPORTED, "bp_sparse launch: syndrome priors are built for plain min-sum");
+        sa.g = ga;
+        if (!p->general) sa.g.chkDeg = nullptr;
+        sa.mu = d.mu;
+        sa.fX = d.fX;
+        sa.fZ = d.fZ;
+        args[0] = &sa;
+        variant = d.layered ? kSoftLayered : kSoftMinSum;
     }
     const unsigned grid = (unsigned)std::min<long long>(d.B, p->grid);
     (void)hipLaunchKernel(p->fn[variant][d.stop], dim3(grid), dim3(p->threads), args, p->lds ? (size_t)p->ws_bytes : 0, stream);

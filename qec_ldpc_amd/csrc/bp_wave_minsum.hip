@@ -42,6 +42,15 @@ struct WaveMinsumArgs {
     int CX[kWaveMaxL], CZ[kWaveMaxL];    // var-view lane mu holds variable (l, (mu + C[l]) mod P)
 };
 
+// The argument of the SOFT kernels (syndrome priors; DESIGN.md section 2, "The soft-syndrome form"): the plain kernels'
+// block at offset 0, so that wave_table and every helper read it as they stand, and behind it the table and the outputs
+struct WaveSoftArgs {
+    WaveMinsumArgs w;
+    const float* mu;     // the channel LLRs of the measurement-error variables, sector X [mX] then Z [mZ]
+    uint8_t* fX;         // nullable: [B][mX] measurement decisions out
+    uint8_t* fZ;         // nullable: [B][mZ]
+};
+
 // sp_minsum_var for the lane's L variables: gathers, the folds from lambda, the inverse rotations.  Returns the
 // decisions (bit l: the posterior of variable l is < 0).
 template <int R, int L, int SEC, bool LAST, bool FREEZE>
@@ -322,7 +331,256 @@ __global__ __launch_bounds__(64) void wave_layered_kernel(const WaveMinsumArgs a
     wave_store_flags(a, ln, b, f, itX, itZ);
 }
 
+// ---- the soft-syndrome form (qec_decoder_set_syndrome_priors) ----
+// wm_sector and wl_sector with the virtual inputs, as bodies of their own: a shared body behind a template parameter
+// changed the instruction streams of the kernels above.  mu = the sector's table, fo = its nullable output: every check
+// has the virtual input mu_c; the lane keeps the decisions f of its R checks in fb, frozen with its group, and the
+// syndrome tests XOR them into the parities.  The inside tests read the data slots / data posteriors as above.
+template <int R, int L, int SEC, int STOP, bool FREEZE>
+__device__ __forceinline__ uint32_t wm_sector_soft(const WaveMinsumArgs& a, const WaveLane& ln, long long b, int& itn,
+                                                   const float* __restrict__ mu, uint8_t* __restrict__ fo)
+{
+    const int P = a.P, n = a.n, N = a.maxIter;
+    const int* D = SEC ? a.DZ : a.DX;
+    const int* C = SEC ? a.CZ : a.CX;
+    const float alpha = a.alpha;
+
+    const uint32_t sb = wave_load_syndrome<R, SEC>(a, ln, b);
+    // channel LLRs of the lane's variables (l, (i + C[l]) mod P)
+    float lamv[L];
+#pragma unroll
+    for (int l = 0; l < L; ++l) lamv[l] = a.lam;
+    if (a.llr != nullptr && ln.live) {
+        const float* t = a.llr + (size_t)SEC * n;
+#pragma unroll
+        for (int l = 0; l < L; ++l) lamv[l] = t[l * P + wave_wrap(ln.i + C[l], P)];
+    }
+    // every slot starts at its variable's channel LLR; the decisions of N = 0
+    float m[R][L];
+    uint32_t hd = 0;
+    {
+        const WaveTable S = wave_table<WaveMinsumArgs, SEC>();
+#pragma unroll
+        for (int l = 0; l < L; ++l) {
+            hd |= (uint32_t)(lamv[l] < 0.0f) << l;
+#pragma unroll
+            for (int r = 0; r < R; ++r) m[r][l] = lamv[l];
+        }
+        if (a.llr != nullptr) {  // wave-uniform
+#pragma unroll
+            for (int l = 1; l < L; ++l)
+#pragma unroll
+                for (int r = 1; r < R; ++r) m[r][l] = wave_rot(lamv[l], ln, P - S[r * L + l]);
+        }
+    }
+
+    float muv[R];
+    uint32_t fb = 0;
+    wave_load_mu<R, SEC>(muv, a, mu, ln);
+#pragma unroll
+    for (int r = 0; r < R; ++r) fb |= (uint32_t)(muv[r] < 0.0f) << r;  // N = 0
+    auto lane_ok = [&]() { return wave_lane_syndrome_ok_soft<R, L, SEC>(a, hd, sb, fb, ln); };
+
+    bool act = ln.live;  // the same on every lane of a group
+    bool syn_ok = false; // syndrome stop: the last test of the group's own decisions
+    itn = 0;
+    for (int it = 0; it < N; ++it) {
+        if (__builtin_amdgcn_ballot_w64(act) == 0ull) break;
+        itn += act ? 1 : 0;
+        fb = wave_check_pass_soft<R, L, FREEZE>(m, sb, muv, alpha, act, fb);
+        if (it == N - 1) hd = wm_var_pass<R, L, SEC, true, FREEZE>(a, m, lamv, ln, act, hd);
+        else hd = wm_var_pass<R, L, SEC, false, FREEZE>(a, m, lamv, ln, act, hd);
+        if (STOP == QEC_STOP_REF && it % 10 == 0) {
+            if (wave_group_all<true>(!wave_lane_any_inside<R, L>(m), ln)) act = false;
+        } else if (STOP == QEC_STOP_SYNDROME) {
+            const bool ok = wave_group_all<true>(lane_ok(), ln);
+            syn_ok = act ? ok : syn_ok;
+            if (ok) act = false;
+        }
+    }
+
+    // ---- the final state: flags from the slots and from the decisions, the outputs ----
+    const bool convFail = !wave_group_all<true>(!wave_lane_any_inside<R, L>(m), ln);
+    if (STOP != QEC_STOP_SYNDROME || N == 0)
+        syn_ok = wave_group_all<true>(lane_ok(), ln);
+    if (fo != nullptr) wave_store_flips<R, SEC>(a, fo, ln, b, fb);  // wave-uniform
+    if (ln.live) {
+        uint8_t* e = (SEC ? a.eZ : a.eX) + b * n;
+#pragma unroll
+        for (int l = 0; l < L; ++l) e[l * P + wave_wrap(ln.i + C[l], P)] = (uint8_t)((hd >> l) & 1u);
+        if (a.q != nullptr) {
+            float* q = a.q + b * ((long long)(a.mX + a.mZ) * L) + (SEC ? (long long)a.mX * L : 0);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                float* row = q + (size_t)(r * P + wave_wrap(ln.i + D[r], P)) * L;
+#pragma unroll
+                for (int l = 0; l < L; ++l) row[l] = m[r][l];
+            }
+        }
+    }
+    uint32_t f = 0;
+    if (!syn_ok) f |= SEC ? QEC_SYNDROME_FAIL_Z : QEC_SYNDROME_FAIL_X;
+    if (convFail) f |= SEC ? QEC_CONVERGENCE_FAIL_Z : QEC_CONVERGENCE_FAIL_X;
+    return f;
+}
+
+template <int R, int L, int SEC, int STOP, bool FREEZE>
+__device__ __forceinline__ uint32_t wl_sector_soft(const WaveMinsumArgs& a, const WaveLane& ln, long long b, int& itn,
+                                                   const float* __restrict__ mu, uint8_t* __restrict__ fo)
+{
+    const int P = a.P, n = a.n, N = a.maxIter;
+    const int* D = SEC ? a.DZ : a.DX;
+    const int* C = SEC ? a.CZ : a.CX;
+    const float alpha = a.alpha;
+
+    const uint32_t sb = wave_load_syndrome<R, SEC>(a, ln, b);
+    // channel LLRs of the lane's variables (l, (i + C[l]) mod P)
+    float lamv[L];
+#pragma unroll
+    for (int l = 0; l < L; ++l) lamv[l] = a.lam;
+    if (a.llr != nullptr && ln.live) {
+        const float* t = a.llr + (size_t)SEC * n;
+#pragma unroll
+        for (int l = 0; l < L; ++l) lamv[l] = t[l * P + wave_wrap(ln.i + C[l], P)];
+    }
+    float Rv[R][L];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int l = 0; l < L; ++l) Rv[r][l] = 0.0f;
+    float muv[R];
+    uint32_t fb = 0;  // the decisions f of the lane's checks: R[c, virtual] = +0.0f at the start
+    wave_load_mu<R, SEC>(muv, a, mu, ln);
+#pragma unroll
+    for (int r = 0; r < R; ++r) fb |= (uint32_t)(muv[r] < 0.0f) << r;
+    auto lane_ok = [&](uint32_t hd) { return wave_lane_syndrome_ok_soft<R, L, SEC>(a, hd, sb, fb, ln); };
+
+    bool act = ln.live;  // the same on every lane of a group
+    bool syn_ok = false; // syndrome stop: the last test of the group's own decisions
+    itn = 0;
+    for (int it = 0; it < N; ++it) {
+        if (__builtin_amdgcn_ballot_w64(act) == 0ull) break;
+        itn += act ? 1 : 0;
+        {
+            const WaveTable S = wave_table<WaveMinsumArgs, SEC>();
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                float qc[L];
+#pragma unroll
+                for (int l = 0; l < L; ++l) {
+                    float t = lamv[l];
+#pragma unroll
+                    for (int k = 0; k < R; ++k)
+                        if (k != r) t = t + Rv[k][l];
+                    qc[l] = (r == 0 || l == 0) ? t : wave_rot(t, ln, P - S[r * L + l]);
+                }
+                const uint32_t f = (uint32_t)wave_check_row_soft<L>(qc, ((sb >> (2 * r)) & 3u) != 0u, muv[r], alpha) << r;
+                fb = FREEZE && !act ? fb : ((fb & ~(1u << r)) | f);
+#pragma unroll
+                for (int l = 0; l < L; ++l) {
+                    const float back = (r == 0 || l == 0) ? qc[l] : wave_rot(qc[l], ln, S[r * L + l]);
+                    Rv[r][l] = FREEZE && !act ? Rv[r][l] : back;
+                }
+            }
+        }
+        if (STOP == QEC_STOP_REF && it % 10 == 0) {
+            float post[L];
+            bool in;
+            (void)wl_posterior<R, L>(post, Rv, lamv, in);
+            if (wave_group_all<true>(!in, ln)) act = false;
+        } else if (STOP == QEC_STOP_SYNDROME) {
+            float post[L];
+            bool in;
+            const uint32_t hd = wl_posterior<R, L>(post, Rv, lamv, in);
+            const bool ok = wave_group_all<true>(lane_ok(hd), ln);
+            syn_ok = act ? ok : syn_ok;
+            if (ok) act = false;
+        }
+    }
+
+    // ---- the final state: posteriors, decisions, flags, the outputs ----
+    float post[L];
+    bool in;
+    const uint32_t hd = wl_posterior<R, L>(post, Rv, lamv, in);
+    const bool convFail = !wave_group_all<true>(!in, ln);
+    if (STOP != QEC_STOP_SYNDROME || N == 0)
+        syn_ok = wave_group_all<true>(lane_ok(hd), ln);
+    if (fo != nullptr) wave_store_flips<R, SEC>(a, fo, ln, b, fb);  // wave-uniform
+    if (ln.live) {
+        uint8_t* e = (SEC ? a.eZ : a.eX) + b * n;
+#pragma unroll
+        for (int l = 0; l < L; ++l) e[l * P + wave_wrap(ln.i + C[l], P)] = (uint8_t)((hd >> l) & 1u);
+    }
+    if (a.q != nullptr) {  // wave-uniform: every lane takes part in the rotations, a live lane stores
+        const WaveTable S = wave_table<WaveMinsumArgs, SEC>();
+        float* q = a.q + b * ((long long)(a.mX + a.mZ) * L) + (SEC ? (long long)a.mX * L : 0);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float* row = q + (size_t)(r * P + wave_wrap(ln.i + D[r], P)) * L;
+#pragma unroll
+            for (int l = 0; l < L; ++l) {
+                const float v = (r == 0 || l == 0) ? post[l] : wave_rot(post[l], ln, P - S[r * L + l]);
+                if (ln.live) row[l] = v;
+            }
+        }
+    }
+    uint32_t f = 0;
+    if (!syn_ok) f |= SEC ? QEC_SYNDROME_FAIL_Z : QEC_SYNDROME_FAIL_X;
+    if (convFail) f |= SEC ? QEC_CONVERGENCE_FAIL_Z : QEC_CONVERGENCE_FAIL_X;
+    return f;
+}
+
+// The SOFT kernels: flooding and layered min-sum under syndrome priors, over the same shape table
+template <int J, int K, int L, int STOP, bool LAYERED>
+__global__ __launch_bounds__(64) void wave_soft_kernel(const WaveSoftArgs sa)
+{
+    const WaveMinsumArgs& a = sa.w;
+    long long b;
+    WaveLane ln;
+    wave_lane(a, ln, b);
+
+    const float* muX = sa.mu;
+    const float* muZ = sa.mu + a.mX;
+    uint32_t f;
+    int itX, itZ;
+    if (STOP != QEC_STOP_FIXED && a.G > 1) {  // wave-uniform: groups that stop on their own
+        if constexpr (LAYERED) {
+            f = wl_sector_soft<J, L, 0, STOP, true>(a, ln, b, itX, muX, sa.fX);
+            f |= wl_sector_soft<K, L, 1, STOP, true>(a, ln, b, itZ, muZ, sa.fZ);
+        } else {
+            f = wm_sector_soft<J, L, 0, STOP, true>(a, ln, b, itX, muX, sa.fX);
+            f |= wm_sector_soft<K, L, 1, STOP, true>(a, ln, b, itZ, muZ, sa.fZ);
+        }
+    } else {
+        if constexpr (LAYERED) {
+            f = wl_sector_soft<J, L, 0, STOP, false>(a, ln, b, itX, muX, sa.fX);
+            f |= wl_sector_soft<K, L, 1, STOP, false>(a, ln, b, itZ, muZ, sa.fZ);
+        } else {
+            f = wm_sector_soft<J, L, 0, STOP, false>(a, ln, b, itX, muX, sa.fX);
+            f |= wm_sector_soft<K, L, 1, STOP, false>(a, ln, b, itZ, muZ, sa.fZ);
+        }
+    }
+    wave_store_flags(a, ln, b, f, itX, itZ);
+}
+
 // ---- host side ---------------------------------------------------------------
+template <int J, int K, int L, bool LAYERED>
+static WaveShape ws_shape_of()
+{
+    WaveShape s{J, K, L, {nullptr, nullptr, nullptr}};
+    s.fn[QEC_STOP_REF] = reinterpret_cast<const void*>(&wave_soft_kernel<J, K, L, QEC_STOP_REF, LAYERED>);
+    s.fn[QEC_STOP_FIXED] = reinterpret_cast<const void*>(&wave_soft_kernel<J, K, L, QEC_STOP_FIXED, LAYERED>);
+    s.fn[QEC_STOP_SYNDROME] = reinterpret_cast<const void*>(&wave_soft_kernel<J, K, L, QEC_STOP_SYNDROME, LAYERED>);
+    return s;
+}
+template <int J, int K, int L>
+static WaveShape wsm_shape() { return ws_shape_of<J, K, L, false>(); }
+template <int J, int K, int L>
+static WaveShape wsl_shape() { return ws_shape_of<J, K, L, true>(); }
+
+static const WaveShape kWaveSoftMinsumShapes[] = {QEC_WAVE_SHAPE_TABLE(wsm_shape)};
+static const WaveShape kWaveSoftLayeredShapes[] = {QEC_WAVE_SHAPE_TABLE(wsl_shape)};
+
 template <int J, int K, int L>
 static WaveShape wl_shape()
 {
@@ -365,6 +623,11 @@ int launch_wave_minsum(const void* shape, const Code& c, const SparseDecode& d, 
     WaveMinsumArgs a{};
     const int rc = wave_fill_args(who, a, c, d);
     if (rc != QEC_OK) return rc;
+    if (d.mu != nullptr) {  // syndrome priors: the SOFT kernels of the same shape
+        s = d.layered ? wave_find_shape(kWaveSoftLayeredShapes, c) : wave_find_shape(kWaveSoftMinsumShapes, c);
+        WaveSoftArgs sa{a, d.mu, d.fX, d.fZ};
+        return wave_launch_as(who, s->fn[d.stop], sa, a.B, a.G, stream);
+    }
     if (d.layered) s = wave_find_shape(kWaveLayeredShapes, c);  // the same row of the other table
     return wave_launch(who, s->fn[d.stop], a, stream);
 }

@@ -94,7 +94,10 @@ int cpu_threads();
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
                      bool near_hard, const float* prior, int corr, const float* cond, int serial, int minsum,
-                     const float* llr, const float* gamma, int legs, int solutions, const int32_t* weight, int layered);
+                     const float* llr, const float* gamma, int legs, int solutions, const int32_t* weight, int layered,
+                     const float* mu = nullptr, uint8_t* fX = nullptr, uint8_t* fZ = nullptr);
+int launch_flip_syndrome(uint64_t seed, uint64_t start, long long B, int mX, int mZ, const float* q, uint8_t* sX,
+                         uint8_t* sZ, uint8_t* fX, uint8_t* fZ, hipStream_t st);
 int sparse_plan_relay_reserve(void* plan);
 void correlated_priors(float p, float* c0, float* c1);
 int launch_pack_decisions(const uint8_t* eX, const uint8_t* eZ, const uint8_t* flags, long long B, int n, uint8_t* out,
@@ -213,6 +216,19 @@ struct qec_decoder {
     // the weights of a relay solution: the integer tables of the priors (as qec_decoder_get_osd_weights), or none
     const int32_t* relay_w_host() const { return has_priors ? osw.data() : nullptr; }
     const int32_t* relay_w_dev() const { return has_priors ? dosw.data() : nullptr; }
+    // qec_decoder_set_syndrome_priors ("The soft-syndrome form"): the probability that each check's
+    // measured bit is flipped, sector X [mX] then Z [mZ], and their channel LLRs mu; the device copy (the LLRs, then the
+    // priors for the flip sampler) is allocated by the first set and rewritten in place afterwards, as dpri is.  Set only
+    // while bp_method = 1 and no relay tables are set (the calls refuse each other), so every min-sum decode of the
+    // handle then runs under them.
+    bool has_syn = false;
+    std::vector<float> synq, synmu;
+    DeviceArray<float> dsyn;
+    bool soft_on() const { return has_syn && bp_method == 1 && !relay_on(); }
+    const float* mu_host() const { return soft_on() ? synmu.data() : nullptr; }
+    const float* mu_dev() const { return soft_on() ? dsyn.data() : nullptr; }
+    const float* synq_dev() const { return dsyn.data() + synq.size(); }
+    DeviceArray<uint8_t> fX, fZ;    // staging of the measurement decisions for qec_decode_batch_soft
     std::vector<float> cond;
     DeviceArray<float> dcond;
     const float* cond_host() const { return has_priors ? cond.data() : nullptr; }
@@ -702,6 +718,7 @@ int qec_decoder_describe(const qec_decoder* d, char* buf, size_t len)
         text += " [min-sum: " + wave_minsum_name(*d->code) + "]";
     if (d->relay_wave)   // ... and of its relay decodes
         text += " [relay: " + wave_relay_name(*d->code) + "]";
+    if (d->has_syn) text += " [soft syndrome]";
     std::snprintf(buf, len, "%s", text.c_str());
     return QEC_OK;
 }
@@ -773,6 +790,10 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
     case QEC_OPT_OSD:
         if (value != 0 && value != 1) return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_OSD is 0 (off) or 1 (OSD-0)");
         if (value && d->parts.empty() && !d->cpu && !d->odev) return fail(QEC_ERR_UNSUPPORTED, d->osd_why);
+        if (value && d->has_syn)
+            return fail(QEC_ERR_UNSUPPORTED,
+                        "qec_decoder_set_option: QEC_OPT_OSD = 1 solves H e = s exactly, which is not the problem under "
+                        "syndrome priors; clear them (qec_decoder_set_syndrome_priors(dec, NULL, NULL)) first");
         d->osd = value;
         return QEC_OK;
     case QEC_OPT_OSD_ITERATIONS:
@@ -851,6 +872,10 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
             return fail(QEC_ERR_UNSUPPORTED,
                         "qec_decoder_set_option: min-sum is built for the flooding schedule; set QEC_OPT_BP_SCHEDULE to 0 "
                         "(flooding) first");
+        if (!value && d->has_syn)
+            return fail(QEC_ERR_UNSUPPORTED,
+                        "qec_decoder_set_option: syndrome priors are built for min-sum; clear them "
+                        "(qec_decoder_set_syndrome_priors(dec, NULL, NULL)) before QEC_OPT_BP_METHOD = 0");
         d->bp_method = value;
         return QEC_OK;
     case QEC_OPT_MINSUM_SCALE:
@@ -1125,6 +1150,10 @@ int qec_decoder_set_relay(qec_decoder* d, const float* gammaX, const float* gamm
                 return fail(QEC_ERR_ARG, std::string("qec_decoder_set_relay: gamma") + (sec ? "Z[" : "X[") + std::to_string(i / n) +
                                              "][" + std::to_string(i % n) + "] = " + std::to_string(g[i]) + " is not in [-1, 1]");
     }
+    if (d->has_syn)
+        return fail(QEC_ERR_UNSUPPORTED,
+                    "qec_decoder_set_relay: the relay's legs have no form under syndrome priors; clear them "
+                    "(qec_decoder_set_syndrome_priors(dec, NULL, NULL)) first");
     bool sparse = true;
     for (const qec_decoder* p : parts_of(d)) sparse = sparse && (p->cpu || p->engine == QEC_ENGINE_SPARSE);
     if (!sparse)
@@ -1150,6 +1179,80 @@ int qec_decoder_get_relay(const qec_decoder* d, float* gammaX, float* gammaZ, in
         if (gammaZ) std::memcpy(gammaZ + (size_t)l * n, d->relay.data() + (2 * (size_t)l + 1) * n, n * sizeof(float));
     }
     return QEC_OK;
+}
+
+// Installs validated syndrome priors (q and their LLRs, sector X [mX] then Z [mZ]) on a handle and on every part of a group
+static int install_syndrome_priors(qec_decoder* d, const std::vector<float>& q, const std::vector<float>& mu)
+{
+    for (qec_decoder* p : d->parts) {
+        const int rc = install_syndrome_priors(p, q, mu);
+        if (rc) return rc;
+    }
+    if (d->parts.empty() && !d->cpu) {
+        QEC_DEVICE_SCOPE(d->device);
+        // synchronous: the handle's last launch may still read the buffer this call rewrites
+        QEC_HIP_CHECK(hipStreamSynchronize(d->stream));
+        if (d->ws_used) QEC_HIP_CHECK(hipEventSynchronize(d->ws_ev));
+        try {
+            d->dsyn.reserve(2 * q.size());
+        } catch (const std::exception& ex) {
+            return fail(QEC_ERR_NOMEM, std::string("qec_decoder_set_syndrome_priors: ") + ex.what());
+        }
+        QEC_HIP_CHECK(hipMemcpy(d->dsyn.data(), mu.data(), mu.size() * sizeof(float), hipMemcpyHostToDevice));
+        QEC_HIP_CHECK(hipMemcpy(d->dsyn.data() + mu.size(), q.data(), q.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    d->synq = q;
+    d->synmu = mu;
+    d->has_syn = true;
+    return QEC_OK;
+}
+
+int qec_decoder_set_syndrome_priors(qec_decoder* d, const float* qX, const float* qZ)
+{
+    const std::string who = "qec_decoder_set_syndrome_priors: ";
+    if (!d) return fail(QEC_ERR_ARG, who + "null decoder");
+    if (!qX && !qZ) {  // clear: the handle behaves as one that never had them (the device buffer is kept)
+        for (qec_decoder* p : d->parts) p->has_syn = false;
+        d->has_syn = false;
+        return QEC_OK;
+    }
+    if (!qX || !qZ) return fail(QEC_ERR_ARG, who + "qX and qZ must both be given, or both be NULL (clear)");
+    const int mX = d->code->mX, mZ = d->code->mZ;
+    for (int sec = 0; sec < 2; ++sec) {
+        const float* q = sec ? qZ : qX;
+        for (int c = 0; c < (sec ? mZ : mX); ++c)
+            if (!(q[c] >= 0.0f && q[c] <= 1.0f))  // a NaN fails both comparisons
+                return fail(QEC_ERR_ARG, who + "q" + (sec ? "Z[" : "X[") + std::to_string(c) + "] = " + std::to_string(q[c]) +
+                                             " is not in [0, 1]");
+    }
+    bool sparse = true;
+    for (const qec_decoder* p : parts_of(d)) sparse = sparse && (p->cpu || p->engine == QEC_ENGINE_SPARSE);
+    if (!sparse)
+        return fail(QEC_ERR_UNSUPPORTED, who + "syndrome priors are a form of min-sum, which is not built for the wave-circulant "
+                                               "engine; create the decoder with QEC_ENGINE_SPARSE (engine \"sparse\")");
+    if (d->bp_method != 1)
+        return fail(QEC_ERR_UNSUPPORTED, who + "syndrome priors are built for min-sum; set QEC_OPT_BP_METHOD to 1 first");
+    if (d->relay_legs > 0)
+        return fail(QEC_ERR_UNSUPPORTED, who + "the relay's legs have no form under syndrome priors; clear the relay tables "
+                                               "(qec_decoder_set_relay(dec, NULL, NULL, 0, 0)) first");
+    if (d->osd)
+        return fail(QEC_ERR_UNSUPPORTED, who + "the OSD stage solves H e = s exactly, which is not the problem under syndrome "
+                                               "priors; set QEC_OPT_OSD to 0 first");
+    std::vector<float> q((size_t)mX + mZ), mu(q.size());
+    std::memcpy(q.data(), qX, mX * sizeof(float));
+    std::memcpy(q.data() + mX, qZ, mZ * sizeof(float));
+    for (size_t i = 0; i < q.size(); ++i) mu[i] = minsum_llr(q[i]);
+    return install_syndrome_priors(d, q, mu);
+}
+
+int qec_decoder_get_syndrome_priors(const qec_decoder* d, float* qX, float* qZ)
+{
+    if (!d) return fail(QEC_ERR_ARG, "qec_decoder_get_syndrome_priors: null decoder");
+    if (!d->has_syn) return 0;
+    const int mX = d->code->mX, mZ = d->code->mZ;
+    if (qX) std::memcpy(qX, d->synq.data(), mX * sizeof(float));
+    if (qZ) std::memcpy(qZ, d->synq.data() + mX, mZ * sizeof(float));
+    return 1;
 }
 
 int qec_decoder_get_osd_weights(const qec_decoder* d, int32_t* wX, int32_t* wZ)
@@ -1247,12 +1350,16 @@ bool triage_on(const qec_decoder* d, float p)
 // whole words for its statistics kernel; wave-circulant engine only)
 int dispatch_decode(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
                     uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* q, hipStream_t st,
-                    bool sbits = false, int rec_stride = 0)
+                    bool sbits = false, int rec_stride = 0, uint8_t* fX = nullptr, uint8_t* fZ = nullptr)
 {
     if (B <= 0) return QEC_OK;
     const Code& c = *d->code;
     int rc = ws_acquire(d, st);
     if (rc) return rc;
+    if (!d->soft_on()) {  // qec_decode_batch_soft on a handle without syndrome priors: no measurement bit is flipped
+        if (fX) QEC_HIP_CHECK(hipMemsetAsync(fX, 0, (size_t)B * c.mX, st));
+        if (fZ) QEC_HIP_CHECK(hipMemsetAsync(fZ, 0, (size_t)B * c.mZ, st));
+    }
     d->last_path = (sbits ? QEC_PATH_BIT_ROWS : 0) | (rec != nullptr ? QEC_PATH_RECORDS : 0);
     if (d->engine == QEC_ENGINE_SPARSE) {
         d->last_path |= QEC_PATH_SPARSE;
@@ -1297,6 +1404,13 @@ int dispatch_decode(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, long l
             // QEC_OPT_MINSUM_SCHEDULE, read at the call: the LAYERED kernels (plain min-sum only: the relay's legs flood)
             sd.layered = d->layered_on();
             if (sd.layered) d->last_path |= QEC_PATH_SERIAL;
+            // qec_decoder_set_syndrome_priors, read at the call: the SOFT kernels under the handle's table
+            sd.mu = d->mu_dev();
+            if (sd.mu) {
+                sd.fX = fX;
+                sd.fZ = fZ;
+                d->last_path |= QEC_PATH_SOFT;
+            }
         }
         // QEC_OPT_MINSUM_WAVE, read at the call: plain min-sum in the wave layout (set_option has checked the code)
         if (sd.minsum && sd.gamma == nullptr && d->minsum_wave) {
@@ -1599,7 +1713,8 @@ int osd_count_end(qec_decoder* d)
 
 // Host-buffer decode of one single-device handle (synchronous): stage, decode, copy back.
 int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, float p, int maxIter, int stop,
-                uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* q)
+                uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* q, uint8_t* fX = nullptr,
+                uint8_t* fZ = nullptr)
 {
     d->osd_sectors = 0;
     d->osd_cs_sectors = 0;
@@ -1608,9 +1723,10 @@ int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
         const int rc = cpu_decode_batch(d->cpu, sX, sZ, (long long)B, p, maxIter, stop, eX, eZ, flags, rec, iters, q, 0,
                                         d->hard_paths && d->near_hard, d->prior_host(), d->correlated, d->cond_host(),
                                         d->bp_schedule, d->minsum(), d->llr_host(), d->relay_host(), d->relay_legs,
-                                        d->relay_solutions, d->relay_w_host(), d->layered_on());
+                                        d->relay_solutions, d->relay_w_host(), d->layered_on(), d->mu_host(), fX, fZ);
         d->last_path = (d->correlated ? QEC_PATH_CORRELATED : 0) | (d->bp_schedule || d->layered_on() ? QEC_PATH_SERIAL : 0) |
-                       (d->bp_method ? QEC_PATH_MINSUM : 0) | (d->relay_on() ? QEC_PATH_RELAY : 0);
+                       (d->bp_method ? QEC_PATH_MINSUM : 0) | (d->relay_on() ? QEC_PATH_RELAY : 0) |
+                       (d->soft_on() ? QEC_PATH_SOFT : 0);
         return rc || !d->osd ? rc : osd_repair_host(d, sX, sZ, B, p, eX, eZ, flags, rec);
     }
     QEC_DEVICE_SCOPE(d->device);
@@ -1624,6 +1740,8 @@ int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
         else { d->eX.reserve(B * c.n); d->eZ.reserve(B * c.n); d->flags.reserve(B); }
         if (iters) d->iters.reserve(2 * B);
         if (q) d->q.reserve(B * qn);
+        if (fX) d->fX.reserve(B * c.mX);
+        if (fZ) d->fZ.reserve(B * c.mZ);
     } catch (const std::exception& ex) {
         return fail(QEC_ERR_HIP, std::string("device staging allocation: ") + ex.what());
     }
@@ -1632,8 +1750,11 @@ int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
     // the sparse engine's packed path stages its byte outputs in eX/eZ/flags (dispatch_decode)
     int rc = dispatch_decode(d, d->sX.data(), d->sZ.data(), (long long)B, p, maxIter, stop, rec ? nullptr : d->eX.data(),
                              rec ? nullptr : d->eZ.data(), rec ? nullptr : d->flags.data(), rec ? d->rec.data() : nullptr,
-                             iters ? d->iters.data() : nullptr, q ? d->q.data() : nullptr, st);
+                             iters ? d->iters.data() : nullptr, q ? d->q.data() : nullptr, st, false, 0,
+                             fX ? d->fX.data() : nullptr, fZ ? d->fZ.data() : nullptr);
     if (rc) return rc;
+    if (fX) QEC_HIP_CHECK(hipMemcpyAsync(fX, d->fX.data(), B * c.mX, hipMemcpyDeviceToHost, st));
+    if (fZ) QEC_HIP_CHECK(hipMemcpyAsync(fZ, d->fZ.data(), B * c.mZ, hipMemcpyDeviceToHost, st));
     if (rec) {
         QEC_HIP_CHECK(hipMemcpyAsync(rec, d->rec.data(), B * recB, hipMemcpyDeviceToHost, st));
     } else {
@@ -1650,11 +1771,12 @@ int decode_host(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, 
 // Host-buffer decode on every part of a handle: contiguous shards, one host thread per part
 // (the reference's sample-parallel loop, DecoderCPU.h:419-438, across devices).
 int decode_host_parts(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, float p, int maxIter, int stop,
-                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* q)
+                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* q,
+                      uint8_t* fX = nullptr, uint8_t* fZ = nullptr)
 {
     const std::vector<qec_decoder*> parts = parts_of(d);
     if (parts.size() == 1)
-        return decode_host(parts[0], sX, sZ, B, p, maxIter, stop, eX, eZ, flags, rec, iters, q);
+        return decode_host(parts[0], sX, sZ, B, p, maxIter, stop, eX, eZ, flags, rec, iters, q, fX, fZ);
     const Code& c = *d->code;
     const size_t qn = (size_t)(c.mX + c.mZ) * c.stride();
     const size_t recB = 2 * (size_t)((c.n + 7) / 8) + 1;
@@ -1667,7 +1789,8 @@ int decode_host_parts(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size
         th.emplace_back([&, k, lo, hi] {
             rcs[k] = decode_host(parts[k], sX + lo * c.mX, sZ + lo * c.mZ, hi - lo, p, maxIter, stop,
                                  eX ? eX + lo * c.n : nullptr, eZ ? eZ + lo * c.n : nullptr, flags ? flags + lo : nullptr,
-                                 rec ? rec + lo * recB : nullptr, iters ? iters + 2 * lo : nullptr, q ? q + lo * qn : nullptr);
+                                 rec ? rec + lo * recB : nullptr, iters ? iters + 2 * lo : nullptr, q ? q + lo * qn : nullptr,
+                                 fX ? fX + lo * c.mX : nullptr, fZ ? fZ + lo * c.mZ : nullptr);
             if (rcs[k]) errs[k] = last_error_cstr();
         });
     }
@@ -1724,6 +1847,43 @@ int qec_decode_batch(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_
     if (rc) return rc;
     if (B && (!eX || !eZ || !flags)) return fail(QEC_ERR_ARG, "decode: null output buffer");
     return decode_host_parts(d, sX, sZ, B, p, maxIter, stop, eX, eZ, flags, nullptr, iters, q);
+}
+
+int qec_decode_batch_soft(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, float p, int maxIter, int stop,
+                          uint8_t* eX, uint8_t* eZ, uint8_t* fX, uint8_t* fZ, uint8_t* flags, int32_t* iters, float* q)
+{
+    int rc = check_decode_args(d, sX, sZ, B, stop);
+    if (rc) return rc;
+    if (B && (!eX || !eZ || !flags)) return fail(QEC_ERR_ARG, "decode: null output buffer");
+    if (d->bp_method != 1) return fail(QEC_ERR_UNSUPPORTED, "qec_decode_batch_soft: a min-sum call; set QEC_OPT_BP_METHOD to 1");
+    return decode_host_parts(d, sX, sZ, B, p, maxIter, stop, eX, eZ, flags, nullptr, iters, q, fX, fZ);
+}
+
+int qec_decode_batch_soft_dev(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, float p, int maxIter,
+                              int stop, uint8_t* eX, uint8_t* eZ, uint8_t* fX, uint8_t* fZ, uint8_t* flags, int32_t* iters,
+                              float* q, void* stream)
+{
+    int rc = check_decode_args(d, sX, sZ, B, stop);
+    if (rc || (rc = single_device_only(d, "qec_decode_batch_soft_dev"))) return rc;
+    if (B && (!eX || !eZ || !flags)) return fail(QEC_ERR_ARG, "decode: null output buffer");
+    if (d->bp_method != 1)
+        return fail(QEC_ERR_UNSUPPORTED, "qec_decode_batch_soft_dev: a min-sum call; set QEC_OPT_BP_METHOD to 1");
+    QEC_DEVICE_SCOPE(d->device);
+    return dispatch_decode(d, sX, sZ, (long long)B, p, maxIter, stop, eX, eZ, flags, nullptr, iters, q,
+                           static_cast<hipStream_t>(stream), false, 0, fX, fZ);
+}
+
+int qec_flip_syndrome_dev(qec_decoder* d, uint64_t seed, uint64_t start, size_t B, uint8_t* sX, uint8_t* sZ, uint8_t* fX,
+                          uint8_t* fZ, void* stream)
+{
+    if (!d || (B && (!sX || !sZ))) return fail(QEC_ERR_ARG, "qec_flip_syndrome_dev: bad argument");
+    int rc = single_device_only(d, "qec_flip_syndrome_dev");
+    if (rc) return rc;
+    if (!d->has_syn)
+        return fail(QEC_ERR_ARG, "qec_flip_syndrome_dev: the decoder has no syndrome priors (qec_decoder_set_syndrome_priors)");
+    QEC_DEVICE_SCOPE(d->device);
+    return launch_flip_syndrome(seed, start, (long long)B, d->code->mX, d->code->mZ, d->synq_dev(), sX, sZ, fX, fZ,
+                                static_cast<hipStream_t>(stream));
 }
 
 int qec_decode_batch_packed(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, size_t B, float p, int maxIter,
@@ -1843,6 +2003,12 @@ int mc_batch(qec_decoder* d, McArgsHost h, int src, float p, int maxIter, int st
     if (zero_counters) QEC_HIP_CHECK(hipMemsetAsync(d->mcount.data(), 0, QEC_MC_NCOUNTERS_ALL * sizeof(unsigned long long), st));
     int rc = launch_mc_errors_syndrome(src, h, st);
     if (rc) return rc;
+    // syndrome priors: the measurement-error channel on the sampled syndromes (qec_monte_carlo; GetStatistics' draws have
+    // no seeded index space and stay as they are)
+    if (d->soft_on() && src != MC_SRC_DRAWS &&
+        (rc = launch_flip_syndrome(h.seed, h.start, h.B, c.mX, c.mZ, d->synq_dev(), d->msX.data(), d->msZ.data(), nullptr,
+                                   nullptr, st)))
+        return rc;
     if (ev0) QEC_HIP_CHECK(hipEventRecord(ev0, st));
     // records at word-aligned rows (156 instead of 155 B for P61) on the bit-row path where the lane
     // statistics kernel has that row shape (rstride above: it then reads both arrays a word at a time);
@@ -1965,7 +2131,7 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
                                         fl.data(), nullptr, nullptr, nullptr, 0, d->hard_paths && d->near_hard,
                                         d->prior_host(), d->correlated, d->cond_host(), d->bp_schedule, d->minsum(),
                                         d->llr_host(), d->relay_host(), d->relay_legs, d->relay_solutions, d->relay_w_host(),
-                                        d->layered_on());
+                                        d->layered_on(), d->mu_host());
         if (rc) return rc;
         if (d->osd) {  // the counters describe the repaired estimates
             d->osd_sectors = 0;
@@ -2001,7 +2167,7 @@ int cpu_statistics(qec_decoder* d, int W, long tested, float p, int maxIter, uin
     d->osd_cs_sectors = swept;
     d->last_path = (d->osd ? QEC_PATH_OSD : 0) | (d->correlated ? QEC_PATH_CORRELATED : 0) |
                    (d->bp_schedule || d->layered_on() ? QEC_PATH_SERIAL : 0) | (d->bp_method ? QEC_PATH_MINSUM : 0) |
-                   (d->relay_on() ? QEC_PATH_RELAY : 0);
+                   (d->relay_on() ? QEC_PATH_RELAY : 0) | (d->soft_on() ? QEC_PATH_SOFT : 0);
     std::memset(out, 0, sizeof *out);
     out->randSeed = seed;
     out->numErrorsTested = (uint32_t)tested;
@@ -2217,8 +2383,12 @@ int qec_sample_syndrome_dev(qec_decoder* d, uint64_t seed, uint64_t start, size_
     h.B = (long long)B;
     h.prior = d->prior_dev();
     h.pauli_thr = d->has_channel ? d->dpth.data() : nullptr;
-    return launch_mc_errors_syndrome(d->has_channel ? MC_SRC_PAULI : d->has_priors ? MC_SRC_INDEPENDENT : MC_SRC_PHILOX, h,
-                                     static_cast<hipStream_t>(stream));
+    rc = launch_mc_errors_syndrome(d->has_channel ? MC_SRC_PAULI : d->has_priors ? MC_SRC_INDEPENDENT : MC_SRC_PHILOX, h,
+                                   static_cast<hipStream_t>(stream));
+    if (rc || !d->soft_on()) return rc;
+    // syndrome priors: the measurement-error channel of qec_flip_syndrome_dev, same seed and sample index
+    return launch_flip_syndrome(seed, start, (long long)B, d->code->mX, d->code->mZ, d->synq_dev(), sX, sZ, nullptr, nullptr,
+                                static_cast<hipStream_t>(stream));
 }
 
 int qec_syndrome_dev(qec_decoder* d, const uint8_t* x, const uint8_t* z, size_t B, uint8_t* sX, uint8_t* sZ,

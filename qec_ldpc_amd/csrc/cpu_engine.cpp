@@ -95,7 +95,38 @@ inline bool minsum_inside(float x) { return std::fabs(x) < kMinSumInside; }  // 
 struct Work {
     std::vector<float> q, r, post;
     std::vector<uint8_t> e;
+    std::vector<uint8_t> f;  // the soft-syndrome form: the measurement decisions of the sector's checks
 };
+
+constexpr int kSoftArg = -2;  // the argmin of a check pass when the virtual input holds the first minimum
+
+// The soft-syndrome form: the virtual input mu of a check enters the running minima and the sign
+// XOR ahead of the real slots (the outputs do not depend on the position of an input) ...
+inline void soft_input(float mu, uint32_t& min1, uint32_t& min2, uint32_t& par, int& arg)
+{
+    uint32_t b;
+    std::memcpy(&b, &mu, sizeof b);
+    const uint32_t a = b & 0x7FFFFFFFu;
+    par ^= b >> 31;
+    if (a < min1) { min2 = min1; min1 = a; arg = kSoftArg; }
+    else if (a < min2) min2 = a;
+}
+// ... and the virtual slot's own output rho = alpha * (the minimum over the real inputs, under the cap) with the sign
+// t ^ (the real inputs' signs); returns f = mu + rho < 0
+inline bool soft_decision(float mu, uint32_t min1, uint32_t min2, uint32_t par, int arg, float alpha)
+{
+    uint32_t b, o;
+    std::memcpy(&b, &mu, sizeof b);
+    const uint32_t mag = arg == kSoftArg ? min2 : min1;
+    float rho;
+    std::memcpy(&rho, &mag, sizeof rho);
+    rho = alpha * rho;
+    std::memcpy(&o, &rho, sizeof o);
+    o |= (par ^ (b >> 31)) << 31;
+    std::memcpy(&rho, &o, sizeof rho);
+    const float postm = mu + rho;
+    return postm < 0.0f;
+}
 
 // The near-hard criterion C(eps0) (qec_near.h) on the messages q after a var pass:
 // every message within eps0 of 0 or 1 (nearT: the compare value of eps0), each variable's messages on one
@@ -397,8 +428,11 @@ int decode_sector_serial(const CpuSector& S, int n, bool general, const uint8_t*
 // regular and general codes, flooding.  q[e] is the variable->check message of edge e as an LLR (> 0: the bit is 0),
 // lam[v] = the channel LLR of variable v (llr, or the scalar lam0).  The loop holds fp32 adds, one fp32 multiply by
 // alpha = scale / 256 and integer operations on bit patterns only; every value is finite.
+// mu != nullptr (qec_decoder_set_syndrome_priors; DESIGN.md section 2, "The soft-syndrome form"): the channel LLR of each
+// check's measurement-error variable, one virtual input of the check; w.f then holds the measurement decisions f_c, which
+// enter the syndrome test.  The inside tests stay on the data slots.
 int decode_sector_minsum(const CpuSector& S, int n, bool general, const uint8_t* syn, float lam0, const float* llr,
-                         int scale, int N, int stop, Work& w, bool& conv_out, bool& syn_ok, float* q_out)
+                         int scale, int N, int stop, Work& w, bool& conv_out, bool& syn_ok, float* q_out, const float* mu)
 {
     const int m = S.m, D = S.dc, dvs = S.dv;
     const size_t E = (size_t)m * D;
@@ -412,9 +446,15 @@ int decode_sector_minsum(const CpuSector& S, int n, bool general, const uint8_t*
     for (int c = 0; c < m; ++c)
         for (int k = 0; k < D; ++k) q[(size_t)c * D + k] = k < cdeg(c) ? lam(S.chk_var[(size_t)c * D + k]) : 0.0f;
     for (int v = 0; v < n; ++v) e[v] = vdeg(v) > 0 && lam(v) < 0.0f;  // N = 0
+    uint8_t* f = nullptr;
+    if (mu) {
+        w.f.resize(m);
+        f = w.f.data();
+        for (int c = 0; c < m; ++c) f[c] = mu[c] < 0.0f;  // N = 0
+    }
     auto syndrome_ok = [&]() {
         for (int c = 0; c < m; ++c) {
-            uint32_t x = 0;
+            uint32_t x = f ? f[c] : 0u;
             for (int k = 0; k < cdeg(c); ++k) x ^= e[S.chk_var[(size_t)c * D + k]];
             if ((x & 1u) != syn[c]) return false;
         }
@@ -439,6 +479,7 @@ int decode_sector_minsum(const CpuSector& S, int n, bool general, const uint8_t*
             const int dc = cdeg(c);
             uint32_t min1 = kMinSumCap, min2 = kMinSumCap, par = syn[c] != 0;
             int arg = -1;
+            if (mu) soft_input(mu[c], min1, min2, par, arg);
             for (int k = 0; k < dc; ++k) {
                 uint32_t b;
                 std::memcpy(&b, qc + k, sizeof b);
@@ -458,6 +499,7 @@ int decode_sector_minsum(const CpuSector& S, int n, bool general, const uint8_t*
                 o |= (par ^ (b >> 31)) << 31;
                 std::memcpy(rc + i, &o, sizeof o);
             }
+            if (mu) f[c] = soft_decision(mu[c], min1, min2, par, arg, alpha);
         }
         // variable update: left folds from the channel LLR in ascending check order; the last iteration of the cap
         // writes the posterior to every slot
@@ -493,9 +535,11 @@ int decode_sector_minsum(const CpuSector& S, int n, bool general, const uint8_t*
 // -- the left fold of the variable's channel LLR and the R of its other checks as they stand -- and then its own R by
 // decode_sector_minsum's check update.  The posterior of a variable is the same fold over all its checks; decisions,
 // both stop tests, the flags and q_out are stated over the posteriors, and a variable in no check decides 0 and enters
-// no test.  There is no special last iteration.
+// no test.  There is no special last iteration.  mu: as decode_sector_minsum's; R[c, virtual] is made when c is processed,
+// so f_c = mu_c + R[c, virtual] < 0 is kept in w.f from then on (before: mu_c < 0).
 int decode_sector_minsum_layered(const CpuSector& S, int n, bool general, const uint8_t* syn, float lam0, const float* llr,
-                                 int scale, int N, int stop, Work& w, bool& conv_out, bool& syn_ok, float* q_out)
+                                 int scale, int N, int stop, Work& w, bool& conv_out, bool& syn_ok, float* q_out,
+                                 const float* mu)
 {
     const int m = S.m, D = S.dc, dvs = S.dv;
     float* q = w.q.data();  // the current check's inputs
@@ -522,9 +566,15 @@ int decode_sector_minsum_layered(const CpuSector& S, int n, bool general, const 
             inside |= minsum_inside(t);
         }
     };
+    uint8_t* f = nullptr;
+    if (mu) {
+        w.f.resize(m);
+        f = w.f.data();
+        for (int c = 0; c < m; ++c) f[c] = mu[c] < 0.0f;  // R[c, virtual] = +0.0f
+    }
     auto syndrome_ok = [&]() {
         for (int c = 0; c < m; ++c) {
-            uint32_t x = 0;
+            uint32_t x = f ? f[c] : 0u;
             for (int k = 0; k < cdeg(c); ++k) x ^= e[S.chk_var[(size_t)c * D + k]];
             if ((x & 1u) != syn[c]) return false;
         }
@@ -538,6 +588,7 @@ int decode_sector_minsum_layered(const CpuSector& S, int n, bool general, const 
             float* rc = r + (size_t)c * D;
             uint32_t min1 = kMinSumCap, min2 = kMinSumCap, par = syn[c] != 0;
             int arg = -1;
+            if (mu) soft_input(mu[c], min1, min2, par, arg);
             for (int k = 0; k < dc; ++k) {
                 const int v = S.chk_var[(size_t)c * D + k], self = c * D + k;
                 const int32_t* ve = S.var_edge.data() + (size_t)v * dvs;
@@ -563,6 +614,7 @@ int decode_sector_minsum_layered(const CpuSector& S, int n, bool general, const 
                 o2 |= (par ^ (b >> 31)) << 31;
                 std::memcpy(rc + i, &o2, sizeof o2);
             }
+            if (mu) f[c] = soft_decision(mu[c], min1, min2, par, arg, alpha);
         }
         if (stop == QEC_STOP_REF && iter % 10 == 0) {
             posterior();
@@ -777,10 +829,13 @@ void correlated_priors(float p, float* c0, float* c1)
 // gamma (with minsum; qec_decoder_set_relay): nullptr, or the relay tables [legs][sector][n] for decode_sector_relay, with
 // solutions = S and weight = nullptr (w_v = 1) or the integer weights of the priors, sector X [n] then Z [n].
 // layered (QEC_OPT_MINSUM_SCHEDULE; with minsum and without gamma): 1 = layered min-sum (decode_sector_minsum_layered).
+// mu (with minsum and without gamma; qec_decoder_set_syndrome_priors): nullptr, or the measurement-error LLRs, sector X
+// [mX] then Z [mZ]; fX / fZ (nullable, [B][mX] / [B][mZ]) receive the measurement decisions, zeros without mu.
 int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long B, float p, int maxIter, int stop,
                      uint8_t* eX, uint8_t* eZ, uint8_t* flags, uint8_t* rec, int32_t* iters, float* qf, int threads,
                      bool near_hard, const float* prior, int corr, const float* cond, int serial, int minsum,
-                     const float* llr, const float* gamma, int legs, int solutions, const int32_t* weight, int layered)
+                     const float* llr, const float* gamma, int legs, int solutions, const int32_t* weight, int layered,
+                     const float* mu, uint8_t* fX, uint8_t* fZ)
 {
     const CpuPlan& P = *static_cast<const CpuPlan*>(plan);
     const int n = P.n, nb = (n + 7) / 8;
@@ -795,6 +850,8 @@ int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long
     if (minsum && (corr || serial))
         return fail(QEC_ERR_UNSUPPORTED, "CPU engine: min-sum has no correlated form and no serial schedule");
     if (minsum && prior && !llr) return fail(QEC_ERR_ARG, "CPU engine: min-sum under priors needs its LLR tables");
+    if (mu && (!minsum || gamma))
+        return fail(QEC_ERR_UNSUPPORTED, "CPU engine: syndrome priors are built for plain min-sum");
     const float lam0 = minsum_llr(2.0f / 3.0f * p);
     float sc0 = 0.0f, sc1 = 0.0f;
     if (corr) correlated_priors(p, &sc0, &sc1);
@@ -818,6 +875,7 @@ int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long
                 const uint8_t* syn = sec ? sZ + b * mZ : sX + b * mX;
                 const float* pri = prior ? prior + (size_t)sec * n : nullptr;
                 const bool second = corr && pass == 1;
+                const float* mus = mu ? mu + (sec ? mX : 0) : nullptr;
                 if (second) {
                     const float* t0 = cond ? cond + (size_t)sec * 2 * n : nullptr;
                     for (int v = 0; v < n; ++v) pi[v] = first[v] ? (cond ? t0[n + v] : sc1) : (cond ? t0[v] : sc0);
@@ -829,14 +887,18 @@ int cpu_decode_batch(void* plan, const uint8_t* sX, const uint8_t* sZ, long long
                                                                      ok, qo)
                                : minsum && layered ? decode_sector_minsum_layered(S, n, P.general, syn, lam0,
                                                                                   prior ? llr + (size_t)sec * n : nullptr, minsum,
-                                                                                  maxIter, stop, w, conv, ok, qo)
+                                                                                  maxIter, stop, w, conv, ok, qo, mus)
                                : minsum ? decode_sector_minsum(S, n, P.general, syn, lam0, prior ? llr + (size_t)sec * n : nullptr,
-                                                             minsum, maxIter, stop, w, conv, ok, qo)
+                                                             minsum, maxIter, stop, w, conv, ok, qo, mus)
                                : serial ? decode_sector_serial(S, n, P.general, syn, p, pri, maxIter, stop, w, conv, ok, qo)
                                : P.general ? decode_sector_general(S, n, syn, p, pri, maxIter, stop, w, conv, ok, qo)
                                            : decode_sector(S, n, syn, p, pri, maxIter, stop, w, conv, ok, qo,
                                                            second ? 0u : nearT[sec]);
                 if (corr && pass == 0) std::memcpy(first.data(), w.e.data(), n);
+                if (uint8_t* fo = sec ? fZ : fX) {
+                    if (mu) std::memcpy(fo + b * S.m, w.f.data(), S.m);
+                    else std::memset(fo + b * S.m, 0, S.m);
+                }
                 if (!ok) f |= sec ? QEC_SYNDROME_FAIL_Z : QEC_SYNDROME_FAIL_X;
                 if (!conv) f |= sec ? QEC_CONVERGENCE_FAIL_Z : QEC_CONVERGENCE_FAIL_X;
                 if (iters) iters[2 * b + sec] = it;

@@ -761,6 +761,35 @@ __global__ __launch_bounds__(64 * kIndepWaves) void sample_pauli_kernel(uint64_t
     }
 }
 
+// The measurement-error channel of a handle with syndrome priors (qec_flip_syndrome_dev), in place on byte syndromes:
+// one wave per sample at a time, lanes over its Philox calls (flip_call, qec_mc.h); word w < mX belongs to X check w,
+// word mX + c to Z check c.  q: the priors, mX floats then mZ.  fX / fZ (nullable) receive the flips.
+__global__ __launch_bounds__(64 * kIndepWaves) void flip_syndrome_kernel(uint64_t seed, uint64_t start, long long B, int mX,
+                                                                        int mZ, const float* __restrict__ q,
+                                                                        uint8_t* __restrict__ sX, uint8_t* __restrict__ sZ,
+                                                                        uint8_t* __restrict__ fX, uint8_t* __restrict__ fZ)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int m = mX + mZ, nc = (m + 3) / 4;
+    for (long long s = (long long)blockIdx.x * kIndepWaves + wv; s < B; s += (long long)gridDim.x * kIndepWaves) {
+        for (int k = lane; k < nc; k += 64) {
+            const uint32_t r = flip_call(seed, start + (uint64_t)s, k, m, q);
+            for (int j = 0; j < 4; ++j) {
+                const int w = 4 * k + j;
+                if (w >= m) break;
+                const uint8_t f = (uint8_t)((r >> j) & 1u);
+                if (w < mX) {
+                    sX[s * mX + w] ^= f;
+                    if (fX != nullptr) fX[s * mX + w] = f;
+                } else {
+                    sZ[s * mZ + (w - mX)] ^= f;
+                    if (fZ != nullptr) fZ[s * mZ + (w - mX)] = f;
+                }
+            }
+        }
+    }
+}
+
 // ---- launchers --------------------------------------------------------------
 static int launch_check(const char* what)
 {
@@ -788,6 +817,16 @@ int launch_sample_independent(uint64_t seed, uint64_t start, long long B, int n,
     hipLaunchKernelGGL(sample_independent_kernel, dim3((unsigned)blocks), dim3(64 * kIndepWaves), 0, st, seed, start, B, n,
                        prior, x, z);
     return launch_check("sample_independent");
+}
+
+int launch_flip_syndrome(uint64_t seed, uint64_t start, long long B, int mX, int mZ, const float* q, uint8_t* sX,
+                         uint8_t* sZ, uint8_t* fX, uint8_t* fZ, hipStream_t st)
+{
+    if (B <= 0) return QEC_OK;
+    const long long blocks = std::min<long long>((B + kIndepWaves - 1) / kIndepWaves, 1 << 16);
+    hipLaunchKernelGGL(flip_syndrome_kernel, dim3((unsigned)blocks), dim3(64 * kIndepWaves), 0, st, seed, start, B, mX, mZ, q,
+                       sX, sZ, fX, fZ);
+    return launch_check("flip_syndrome");
 }
 
 int launch_sample_pauli(uint64_t seed, uint64_t start, long long B, int n, const uint64_t* thr, uint8_t* x, uint8_t* z,

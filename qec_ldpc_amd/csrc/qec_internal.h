@@ -153,6 +153,11 @@ struct SparseDecode {
     const int32_t* relay_weight = nullptr;
     // QEC_OPT_MINSUM_SCHEDULE = 1 (with minsum, gamma = nullptr): the LAYERED kernels, layered min-sum
     int layered = 0;
+    // qec_decoder_set_syndrome_priors (with minsum, gamma = nullptr): the SOFT kernels under mu = the mX + mZ channel LLRs
+    // of the measurement-error variables; fX / fZ (nullable) receive the measurement decisions, [B][mX] and [B][mZ]
+    const float* mu = nullptr;
+    uint8_t* fX = nullptr;
+    uint8_t* fZ = nullptr;
 };
 
 // The relay form: the limits of qec_decoder_set_relay

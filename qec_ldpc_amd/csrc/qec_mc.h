@@ -143,6 +143,26 @@ __device__ __forceinline__ uint32_t indep_call(uint64_t seed, uint64_t b, int k,
     return r;
 }
 
+// Measurement-error sampler (qec_flip_syndrome_dev; a handle with syndrome priors).  Sample b makes Philox calls
+// k = 0, 1, ... with counter (b_lo, b_hi, k, kFlipSalt), key (seed_lo, seed_hi); word 4k + j = output word j of call k;
+// the check of word w (X check w, Z check w - mX) is flipped iff word w < floor(q 2^32) (indep_threshold).
+constexpr uint32_t kFlipSalt = 0xA54FF53Au;
+
+// Call k of sample b over the m = mX + mZ priors q: bits 0..3 = the flips of words 4k .. 4k + 3 (a word >= m gives 0)
+__device__ __forceinline__ uint32_t flip_call(uint64_t seed, uint64_t b, int k, int m, const float* __restrict__ q)
+{
+    const int w0 = 4 * k;
+    if (w0 >= m) return 0u;
+    const U4 o = philox4x32_10(U4{(uint32_t)b, (uint32_t)(b >> 32), (uint32_t)k, kFlipSalt}, (uint32_t)seed,
+                               (uint32_t)(seed >> 32));
+    const uint32_t u[4] = {o.x, o.y, o.z, o.w};
+    uint32_t r = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (w0 + j < m) r |= (uint32_t)((uint64_t)u[j] < indep_threshold(q[w0 + j])) << j;
+    return r;
+}
+
 // Pauli-channel sampler (qec_sample_pauli_dev; a handle with qec_decoder_set_pauli_channel).  Sample b makes
 // Philox calls k = 0, 1, ... with counter (b_lo, b_hi, k, kPauliSalt), key (seed_lo, seed_hi); output word j of
 // call k is the word u of qubit 4k + j: x = u < tXY, z = tX <= u < tXYZ (X below tX, Y up to tXY, Z up to tXYZ).

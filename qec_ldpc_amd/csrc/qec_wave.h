@@ -177,6 +177,147 @@ __device__ __forceinline__ void wave_check_row(float (&m)[L], bool t, float alph
     }
 }
 
+// ---- the soft-syndrome form (qec_decoder_set_syndrome_priors): SOFT siblings -----------------
+// The channel LLRs of the measurement-error variables of the lane's checks, at the index where wave_load_syndrome reads
+// the syndrome byte; mu = the sector's table.  An idle lane computes on +0.0f.
+template <int R, int SEC, class A>
+__device__ __forceinline__ void wave_load_mu(float (&muv)[R], const A& a, const float* __restrict__ mu, const WaveLane& ln)
+{
+    const int P = a.P;
+    const int* D = SEC ? a.DZ : a.DX;
+#pragma unroll
+    for (int r = 0; r < R; ++r) muv[r] = 0.0f;
+    if (ln.live) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) muv[r] = mu[r * P + wave_wrap(ln.i + D[r], P)];
+    }
+}
+
+// The virtual input of a row: it enters the minima and the parity ahead of the L registers (the outputs do not depend
+// on an input's position); virt = it holds the first minimum so far
+__device__ __forceinline__ void wave_soft_input(float mu, uint32_t& min1, uint32_t& sgn, bool& virt)
+{
+    const uint32_t b = __float_as_uint(mu);
+    const uint32_t x = b & 0x7FFFFFFFu;
+    sgn ^= b;
+    virt = x < kMinSumCap;
+    min1 = virt ? x : kMinSumCap;
+}
+// The row's measurement decision f = mu + rho < 0, rho = the virtual slot's own output: o2 where the virtual input is
+// the first minimum (arg never moved), else o1, under the parity without the input's own sign
+__device__ __forceinline__ bool wave_soft_decision(float mu, uint32_t o1, uint32_t o2, uint32_t sgn, bool virt, int arg)
+{
+    const uint32_t b = __float_as_uint(mu);
+    const float rho = __uint_as_float(((virt && arg < 0) ? o2 : o1) | ((sgn ^ b) & 0x80000000u));
+    const float postm = mu + rho;
+    return postm < 0.0f;
+}
+
+// wave_check_pass with the virtual inputs muv; returns the decisions f of the lane's R checks (bit r), a frozen
+// group's kept
+template <int R, int L, bool FREEZE>
+__device__ __forceinline__ uint32_t wave_check_pass_soft(float (&m)[R][L], uint32_t sb, const float (&muv)[R], float alpha,
+                                                         bool act, uint32_t fb_old)
+{
+    uint32_t fb = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        uint32_t min1, min2 = kMinSumCap;
+        uint32_t sgn = ((sb >> (2 * r)) & 3u) != 0u ? 0x80000000u : 0u;  // the parity, kept in the sign position
+        bool virt;
+        wave_soft_input(muv[r], min1, sgn, virt);
+        int arg = -1;
+#pragma unroll
+        for (int l = 0; l < L; ++l) {
+            const uint32_t b = __float_as_uint(m[r][l]);
+            const uint32_t x = b & 0x7FFFFFFFu;
+            sgn ^= b;
+            const bool lt1 = x < min1;
+            min2 = lt1 ? min1 : (x < min2 ? x : min2);
+            arg = lt1 ? l : arg;
+            min1 = lt1 ? x : min1;
+        }
+        sgn &= 0x80000000u;
+        const uint32_t o1 = __float_as_uint(alpha * __uint_as_float(min1));
+        const uint32_t o2 = __float_as_uint(alpha * __uint_as_float(min2));
+#pragma unroll
+        for (int l = 0; l < L; ++l) {
+            const uint32_t b = __float_as_uint(m[r][l]);
+            const uint32_t o = (l == arg ? o2 : o1) | ((sgn ^ b) & 0x80000000u);
+            m[r][l] = __uint_as_float(FREEZE && !act ? b : o);
+        }
+        fb |= (uint32_t)wave_soft_decision(muv[r], o1, o2, sgn, virt, arg) << r;
+    }
+    return FREEZE && !act ? fb_old : fb;
+}
+
+// wave_check_row with the virtual input mu; returns the row's decision f
+template <int L>
+__device__ __forceinline__ bool wave_check_row_soft(float (&m)[L], bool t, float mu, float alpha)
+{
+    uint32_t min1, min2 = kMinSumCap;
+    uint32_t sgn = t ? 0x80000000u : 0u;  // the parity, kept in the sign position
+    bool virt;
+    wave_soft_input(mu, min1, sgn, virt);
+    int arg = -1;
+#pragma unroll
+    for (int l = 0; l < L; ++l) {
+        const uint32_t b = __float_as_uint(m[l]);
+        const uint32_t x = b & 0x7FFFFFFFu;
+        sgn ^= b;
+        const bool lt1 = x < min1;
+        min2 = lt1 ? min1 : (x < min2 ? x : min2);
+        arg = lt1 ? l : arg;
+        min1 = lt1 ? x : min1;
+    }
+    sgn &= 0x80000000u;
+    const uint32_t o1 = __float_as_uint(alpha * __uint_as_float(min1));
+    const uint32_t o2 = __float_as_uint(alpha * __uint_as_float(min2));
+#pragma unroll
+    for (int l = 0; l < L; ++l) {
+        const uint32_t b = __float_as_uint(m[l]);
+        m[l] = __uint_as_float((l == arg ? o2 : o1) | ((sgn ^ b) & 0x80000000u));
+    }
+    return wave_soft_decision(mu, o1, o2, sgn, virt, arg);
+}
+
+// wave_lane_syndrome_ok with the lane's decisions f (bit r) XORed into the parities.  SEC picks the shift table of
+// argument struct A, which sits at offset 0 of the kernel's argument.
+template <int R, int L, int SEC, class A>
+__device__ __forceinline__ bool wave_lane_syndrome_ok_soft(const A& a, uint32_t hd, uint32_t sb, uint32_t fb,
+                                                           const WaveLane& ln)
+{
+    const int P = a.P;
+    const WaveTable S = wave_table<A, SEC>();
+    bool ok = true;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        uint32_t x = (fb >> r) & 1u;
+#pragma unroll
+        for (int l = 0; l < L; ++l) {
+            const uint32_t h = (r == 0 || l == 0) ? hd : (uint32_t)wave_rot_i((int)hd, ln, P - S[r * L + l]);
+            x ^= (h >> l) & 1u;
+        }
+        ok &= x == ((sb >> (2 * r)) & 3u);
+    }
+    return ok;
+}
+
+// The decisions f of the lane's checks of pair b out (live lanes; fo = the sector's array, m_s its checks per pair)
+template <int R, int SEC, class A>
+__device__ __forceinline__ void wave_store_flips(const A& a, uint8_t* __restrict__ fo, const WaveLane& ln, long long b,
+                                                 uint32_t fb)
+{
+    const int P = a.P;
+    const int m_s = SEC ? a.mZ : a.mX;
+    const int* D = SEC ? a.DZ : a.DX;
+    if (ln.live) {
+        uint8_t* f = fo + b * m_s;
+#pragma unroll
+        for (int r = 0; r < R; ++r) f[r * P + wave_wrap(ln.i + D[r], P)] = (uint8_t)((fb >> r) & 1u);
+    }
+}
+
 // Whether the parities of the lane's R checks over the decisions hd (variable view, bit l) equal their syndrome
 // entries; an entry other than 0 / 1 equals no parity
 template <int R, int L, int SEC, class A>
@@ -309,6 +450,19 @@ template <class A>
 inline int wave_launch(const char* who, const void* fn, A& a, hipStream_t stream)
 {
     const long long waves = (a.B + a.G - 1) / a.G;
+    if (waves > 0x7fffffffLL) return fail(QEC_ERR_ARG, std::string(who) + ": batch too large for one launch");
+    void* args[] = {&a};
+    (void)hipLaunchKernel(fn, dim3((unsigned)waves), dim3(64), args, 0, stream);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(QEC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(err));
+    return QEC_OK;
+}
+
+// wave_launch for an argument struct that wraps the shared fields (B pairs, G per wave)
+template <class A>
+inline int wave_launch_as(const char* who, const void* fn, A& a, long long B, int G, hipStream_t stream)
+{
+    const long long waves = (B + G - 1) / G;
     if (waves > 0x7fffffffLL) return fail(QEC_ERR_ARG, std::string(who) + ": batch too large for one launch");
     void* args[] = {&a};
     (void)hipLaunchKernel(fn, dim3((unsigned)waves), dim3(64), args, 0, stream);

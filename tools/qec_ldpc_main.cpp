@@ -54,6 +54,11 @@
 //   --relay-solutions S   the relay stops at the lightest of its first S solutions (1 .. 64, default 1); needs --relay
 //   --relay-wave 0|1   the kernels of relay decodes (QEC_OPT_RELAY_WAVE): 1 = the register-resident wave relay kernels
 //                      (the codes of --minsum-wave); needs --engine sparse, --bp-method minsum and --relay FILE
+//   --syndrome-priors FILE   noisy syndromes (qec_decoder_set_syndrome_priors): FILE holds two lines of decimal floats, the
+//                      numEqsX flip probabilities of the X checks' measured bits, then the numEqsZ of the Z checks';
+//                      needs --bp-method minsum; not with --relay or --osd.  --rng philox then flips the sampled
+//                      syndromes with these probabilities
+//   --syndrome-noise Q   the same with one value Q in [0, 1] for every check; not together with --syndrome-priors
 //   --pauli FILE       per-qubit Pauli channel (qec_decoder_set_pauli_channel): FILE holds three lines of n decimal
 //                      floats, pX, pY and pZ.  BP decodes under its marginals (and --correlated under its conditional
 //                      tables), the init file's p is not used, and --rng philox draws its errors from the channel.
@@ -107,7 +112,8 @@ int usage(const std::string& why)
                  " [--stop ref|fixed|syndrome] [--batch B] [--seed S] [--logical file|reference|degenerate]"
                  " [--osd 0 [--osd-order L] [--osd-iterations K] [--osd-score hamming|priors]] [--priors FILE]"
                  " [--correlated xz|zx] [--bp-schedule flooding|serial] [--bp-method product|minsum [--minsum-scale K] [--minsum-wave 0|1]"
-                 " [--relay FILE [--relay-solutions S] [--relay-wave 0|1]]] [--pauli FILE] initFile"
+                 " [--relay FILE [--relay-solutions S] [--relay-wave 0|1]]"
+                 " [--syndrome-priors FILE | --syndrome-noise Q]] [--pauli FILE] initFile"
               << std::endl;
     return 2;
 }
@@ -125,6 +131,26 @@ void read_priors(const std::string& path, int n, std::vector<float>& pX, std::ve
         while (ss >> v) out->push_back(v);
         if (!ss.eof() || (int)out->size() != n)
             throw std::string("--priors: each line of " + path + " needs n = " + std::to_string(n) + " decimal floats");
+    }
+}
+
+// --syndrome-priors FILE: two lines of decimal floats (mX for the X checks, then mZ for the Z checks)
+void read_syndrome_priors(const std::string& path, int mX, int mZ, std::vector<float>& qX, std::vector<float>& qZ)
+{
+    std::ifstream in(path);
+    if (!in.is_open()) throw std::string("--syndrome-priors: unable to open " + path);
+    std::string line;
+    for (int sec = 0; sec < 2; ++sec) {
+        std::vector<float>& out = sec ? qZ : qX;
+        const int m = sec ? mZ : mX;
+        if (!std::getline(in, line))
+            throw std::string("--syndrome-priors: " + path + " needs two lines of floats (the X checks, then the Z checks)");
+        std::stringstream ss(line);
+        float v;
+        while (ss >> v) out.push_back(v);
+        if (!ss.eof() || (int)out.size() != m)
+            throw std::string("--syndrome-priors: line " + std::to_string(sec + 1) + " of " + path + " needs " +
+                              std::to_string(m) + " decimal floats");
     }
 }
 
@@ -183,6 +209,9 @@ int main(int argc, char** argv)
     log << std::endl << std::ctime(&ts);
     std::vector<int> devices{0};
     std::string engine = "gpu", rng = "msvc", stopName = "ref", logical = "file", priorsFile, pauliFile, relayFile;
+    std::string synPriorsFile;
+    float synNoise = 0.0f;
+    bool synNoiseFlag = false;
     int relaySolutions = 1;
     bool relaySolutionsFlag = false;
     int correlated = 0, bpSchedule = 0, bpMethod = 0, minsumScale = 160;
@@ -274,6 +303,13 @@ int main(int argc, char** argv)
                 if (val != "0" && val != "1") return usage("--relay-wave: 0 or 1");
                 relayWave = val == "1" ? 1 : 0;
                 relayWaveFlag = true;
+            } else if (flag == "--syndrome-priors") {
+                synPriorsFile = val;
+            } else if (flag == "--syndrome-noise") {
+                size_t used = 0;
+                synNoise = std::stof(val, &used);
+                synNoiseFlag = true;
+                if (used != val.size() || !(synNoise >= 0.0f && synNoise <= 1.0f)) return usage("--syndrome-noise: a value in [0, 1]");
             } else if (flag == "--relay") {
                 relayFile = val;
             } else if (flag == "--relay-solutions") {
@@ -308,6 +344,11 @@ int main(int argc, char** argv)
     if (relaySolutionsFlag && relayFile.empty()) return usage("--relay-solutions needs --relay FILE");
     if (relayWaveFlag && (!bpMethod || engine != "sparse" || relayFile.empty()))
         return usage("--relay-wave needs --engine sparse, --bp-method minsum and --relay FILE");
+    const bool soft = synNoiseFlag || !synPriorsFile.empty();
+    if (synNoiseFlag && !synPriorsFile.empty()) return usage("--syndrome-noise and --syndrome-priors exclude each other");
+    if (soft && !bpMethod) return usage("--syndrome-priors / --syndrome-noise need --bp-method minsum");
+    if (soft && !relayFile.empty()) return usage("--syndrome-priors / --syndrome-noise and --relay exclude each other");
+    if (soft && osd) return usage("--syndrome-priors / --syndrome-noise and --osd exclude each other");
     if (!pauliFile.empty() && !priorsFile.empty()) return usage("--pauli and --priors exclude each other");
     if (osdScore == 1 && priorsFile.empty()) return usage("--osd-score priors needs --priors FILE");
     if (argc - a != 1 || devices.empty()) {
@@ -346,6 +387,9 @@ int main(int argc, char** argv)
         if (!pauliFile.empty()) read_pauli(pauliFile, code.n, pauli);
         std::vector<float> gammaX, gammaZ;
         const int relayLegs = relayFile.empty() ? 0 : read_relay(relayFile, code.n, gammaX, gammaZ);
+        std::vector<float> synX, synZ;
+        if (!synPriorsFile.empty()) read_syndrome_priors(synPriorsFile, code.numEqsX, code.numEqsZ, synX, synZ);
+        if (synNoiseFlag) { synX.assign(code.numEqsX, synNoise); synZ.assign(code.numEqsZ, synNoise); }
         if (rng == "philox") {
             std::unique_ptr<DecoderGPU> dp(engine == "sparse" ? new DecoderGPU(code, 0, QEC_ENGINE_SPARSE)
                                                                : new DecoderGPU(code, devices));
@@ -361,6 +405,7 @@ int main(int argc, char** argv)
             if (minsumWave) decoder.SetMinSumWave(minsumWave);
             if (relayLegs) decoder.SetRelay(gammaX, gammaZ, relayLegs, relaySolutions);
             if (relayWave) decoder.SetRelayWave(relayWave);
+            if (soft) decoder.SetSyndromePriors(synX, synZ);
             std::cout << "Engine: " << decoder.Describe() << std::endl;
             const int stop = stopName == "ref" ? QEC_STOP_REF : stopName == "fixed" ? QEC_STOP_FIXED : QEC_STOP_SYNDROME;
             std::stringstream fileName;
@@ -391,6 +436,7 @@ int main(int argc, char** argv)
             if (bpMethod) c->SetBpMethod(bpMethod, minsumScale);
             if (minsumSchedule) c->SetMinSumSchedule(minsumSchedule);
             if (relayLegs) c->SetRelay(gammaX, gammaZ, relayLegs, relaySolutions);
+            if (soft) c->SetSyndromePriors(synX, synZ);
             std::cout << "Engine: CPU (" << std::thread::hardware_concurrency() << " threads)" << std::endl;
         } else {
             DecoderGPU* g = engine == "sparse" ? new DecoderGPU(code, 0, QEC_ENGINE_SPARSE) : new DecoderGPU(code, devices);
@@ -406,6 +452,7 @@ int main(int argc, char** argv)
             if (minsumWave) g->SetMinSumWave(minsumWave);
             if (relayLegs) g->SetRelay(gammaX, gammaZ, relayLegs, relaySolutions);
             if (relayWave) g->SetRelayWave(relayWave);
+            if (soft) g->SetSyndromePriors(synX, synZ);
             std::cout << "Engine: " << g->Describe() << std::endl;
         }
         for (; w <= W; ++w) {
