@@ -20,13 +20,15 @@
 // Each edge is owned by exactly one thread in each pass, so in-place updates are
 // race-free; passes are separated by workgroup barriers.
 //
-// Two kernel entries, bp_sparse_kernel (regular codes) and bp_general_kernel (codes given by two matrices, any
-// degrees), run the same four decode bodies -- sp_flood_decode (the flooding schedule, scalar p' or PRIORS),
-// sp_corr_decode (CORR), sp_serial_decode (SERIAL) and sp_minsum_decode (MINSUM) -- each templated on GENERAL, which selects the table
-// sentinels, the packed syndrome byte and the update functions; everything around the updates (loops, stop tests,
-// post-processing, flags) is one text for both routes.  A third entry, bp_relay_kernel, runs sp_relay_decode (RELAY: the
-// min-sum body with a memory per variable and a chain of legs) for both routes under an argument block of its own.  The
-// plan keeps one table of kernels, by variant and stop rule.
+// One kernel entry, bp_sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, BODY>, under one argument block, SparseArgs (the
+// SOFT and RELAY bodies append their own fields to it: SoftArgs, RelayArgs): it
+// picks the workspace and calls the decode body that BODY names -- sp_flood_decode (the flooding schedule: kScalar with
+// p', kPriors), sp_corr_decode (kCorr), sp_serial_decode (kSerial), sp_minsum_decode (kMinSum, kSoftMinSum),
+// sp_relay_decode (kRelay: the min-sum body with a memory per variable and a chain of legs) and sp_layered_decode
+// (kLayered, kSoftLayered).  Every body is templated on GENERAL -- false for a regular code, true for a code given by two
+// matrices with any degrees -- which selects the table sentinels, the packed syndrome byte and the update functions;
+// everything around the updates (loops, stop tests, post-processing, flags) is one text for both routes.  The plan keeps
+// one table of kernels, by body and stop rule.
 //
 // Arithmetic is the same as the wave-circulant engine's (and so the reference's):
 // left folds in ascending neighbour order (prefix reuse only), IEEE fp32 with
@@ -37,6 +39,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <utility>
 #include <vector>
 
 #include "../../include/HostDeviceArray.h"
@@ -75,7 +78,41 @@ struct SparseArgs {
     const int32_t* layOrder;
     const int32_t* layOff;
     int LX, LZ;
+    // a general code (dc = D, dvX / dvZ = the column strides): mX + mZ degree bytes; null for a regular code
+    const uint8_t* chkDeg;
 };
+
+// The two bodies that need more than the block append their fields to it, at the offsets they always had: with the SOFT
+// and RELAY fields in SparseArgs itself the SOFT kernels' instruction streams moved, and they measured up to 3.9 % slower
+// on a small general code.
+struct SoftArgs : SparseArgs {  // SOFT kernels (qec_decoder_set_syndrome_priors)
+    const float* mu;         // mX + mZ channel LLRs of the measurement-error variables
+    uint8_t* fX;             // nullable: [B][mX] measurement decisions out
+    uint8_t* fZ;             // nullable: [B][mZ]
+};
+
+struct RelayArgs : SparseArgs {  // RELAY kernels (qec_decoder_set_relay)
+    const float* gamma;      // [legs][sector][n]
+    const int32_t* weight;   // null (w_v = 1), or sector X [n] then Z [n]: the handle's integer weight tables
+    uint8_t* relayWs;        // per workgroup: M [2n] floats, best [2n] bytes
+    long long relayStride;   // bytes per workgroup
+    int legs, solutions;
+};
+
+static_assert(sizeof(SparseArgs) == 192 && sizeof(SoftArgs) == 216 && sizeof(RelayArgs) == 232,
+              "the kernels' argument layouts: the block, then the body's own fields");
+
+// The decode bodies, as the entry's BODY parameter and as the rows of the plan's kernel table.  kPriors is the flooding
+// body's PRIORS form; CORR, SERIAL, MINSUM, RELAY and LAYERED take priors as a runtime branch.
+enum { kScalar = 0, kPriors = 1, kCorr = 2, kSerial = 3, kMinSum = 4, kRelay = 5, kLayered = 6, kSoftMinSum = 7,
+       kSoftLayered = 8, kVariants = 9 };
+
+// The argument block of a body
+template <int BODY> struct SparseArgsFor { using type = SparseArgs; };
+template <> struct SparseArgsFor<kRelay> { using type = RelayArgs; };
+template <> struct SparseArgsFor<kSoftMinSum> { using type = SoftArgs; };
+template <> struct SparseArgsFor<kSoftLayered> { using type = SoftArgs; };
+template <int BODY> using SparseArgsOf = typename SparseArgsFor<BODY>::type;
 
 constexpr int kSparseThreads = 256;
 
@@ -172,7 +209,7 @@ __device__ __forceinline__ bool sp_var(float* __restrict__ msg, const int32_t* _
 //   * the convergence test reads every slot: +0.0f is outside (0.01, 0.99), as a real hard message is.
 //   * the syndrome tests and the final hard decision walk the whole stride and select on the sentinel
 //     (an early exit would chain the table loads one behind the other).
-// For a regular code D = L and every stored value equals bp_sparse_kernel's.
+// For a regular code D = L and every stored value equals the regular route's.
 // The workgroup is the smallest of 64 / 128 / 256 threads that covers the wider pass, max(mX + mZ, 2n):
 // a small code then pays for one or two waves at every barrier instead of four.
 template <int MAXDC>
@@ -259,17 +296,12 @@ __device__ __forceinline__ bool sp_var_general(float* __restrict__ msg, const in
     return hd;
 }
 
-struct GeneralArgs {
-    SparseArgs s;            // dc = D, dvX / dvZ = the column strides
-    const uint8_t* chkDeg;   // mX + mZ degree bytes
-};
-
 extern __shared__ __attribute__((aligned(16))) uint8_t sp_lds[];
 
 // ---- pieces of the decode bodies ------------------------------------------------
-// Every body (flooding, CORR, SERIAL) is templated on GENERAL: false for bp_sparse_kernel's regular tables,
-// true for bp_general_kernel's padded ones.  sp_var_edges and sp_store_status serve all three bodies; the
-// others serve the flooding body alone: calling them from the CORR and SERIAL bodies, which spell the same
+// Every body is templated on GENERAL: false for a regular code's tables, true for a general code's padded
+// ones.  sp_var_edges and sp_store_status serve every body; the others serve the flooding body and the min-sum
+// family (MINSUM, RELAY, LAYERED), not CORR and SERIAL: calling them from those bodies, which spell the same
 // steps out, changed those kernels' code and measured up to 2.6 % slower (profiles/flood_merge_ab.json).
 
 // Syndromes in.  Regular: the entry as given -- the check update takes its truthiness, the syndrome tests compare
@@ -389,7 +421,7 @@ __device__ __forceinline__ void sp_any_inside(const float* msg, int E, int EX, b
 }
 
 template <int STOP, int MAXDC, int MAXDV, bool GENERAL, bool PRIORS>
-__device__ __forceinline__ void sp_flood_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws)
+__device__ __forceinline__ void sp_flood_decode(const SparseArgs& a, uint8_t* ws)
 {
     const int tid = threadIdx.x, nt = blockDim.x;
     const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
@@ -403,7 +435,7 @@ __device__ __forceinline__ void sp_flood_decode(const SparseArgs& a, const uint8
     const int N = a.maxIter < 0 ? 0 : a.maxIter;
 
     for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
-        sp_load_syndromes<GENERAL>(a, chkDeg, b, syn);
+        sp_load_syndromes<GENERAL>(a, a.chkDeg, b, syn);
         // InitVarNodes: every edge starts at p' (DecoderCPU.h:135-148, 265-267) or at its variable's prior, one
         // edge per thread.  The check table is read only where it is needed: for the prior's index and for a
         // general code's sentinel, which tells a real slot from an unused one (coalesced words that every
@@ -484,8 +516,9 @@ __device__ __forceinline__ void sp_flood_decode(const SparseArgs& a, const uint8
 // sp_check_general / sp_var_general (general: the exact no-op padding, unused slots +0.0f, a variable in no
 // check decides 0), so every fp32 rule of the file carries over; one owner per edge per pass, no atomics.
 template <int STOP, int MAXDC, int MAXDV, bool GENERAL>
-__device__ __forceinline__ void sp_corr_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws)
+__device__ __forceinline__ void sp_corr_decode(const SparseArgs& a, uint8_t* ws)
 {
+    const uint8_t* __restrict__ chkDeg = a.chkDeg;
     const int tid = threadIdx.x, nt = blockDim.x;
     const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
     const int E = m * dc;
@@ -650,8 +683,9 @@ __device__ __forceinline__ float sp_serial_fold(const float* __restrict__ msg, c
 }
 
 template <int STOP, int MAXDC, int MAXDV, bool GENERAL>
-__device__ __forceinline__ void sp_serial_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws)
+__device__ __forceinline__ void sp_serial_decode(const SparseArgs& a, uint8_t* ws)
 {
+    const uint8_t* __restrict__ chkDeg = a.chkDeg;
     const int tid = threadIdx.x, nt = blockDim.x;
     const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
     const int EX = mX * dc, E = m * dc;
@@ -780,9 +814,9 @@ __device__ __forceinline__ void sp_serial_decode(const SparseArgs& a, const uint
 // The flooding schedule over LLRs (> 0: the bit is 0): the message array holds the variable->check message of every
 // edge after a variable pass and the check->variable message after a check pass, as in the flooding body, with the
 // barriers where that body has them.  Only fp32 adds, one fp32 multiply by alpha = k / 256 and integer operations on
-// bit patterns occur, so every value is finite.  The argument block is SparseArgs as it stands, so that the other
-// kernels' code does not move: errorProbability carries the scalar channel LLR lambda(p'), prior (workgroup-uniform:
-// null or not) the 2n channel LLRs of the handle's priors, c0 the factor alpha.
+// bit patterns occur, so every value is finite.  The min-sum family reads three fields of the argument block its own
+// way: errorProbability carries the scalar channel LLR lambda(p'), prior (workgroup-uniform: null or not) the 2n
+// channel LLRs of the handle's priors, c0 the factor alpha.
 //   * check pass: thread per check, one pass over its row for the first minimum, the second minimum and the argmin
 //     of the magnitudes' bit patterns (compared as unsigned integers, capped by K = the pattern of 2^20) and the XOR
 //     of the sign bits with the syndrome bit; a second pass stores alpha * (second minimum where the slot is the
@@ -827,19 +861,15 @@ __device__ __forceinline__ void sp_minsum_check(float* __restrict__ m, int dc, u
     }
 }
 
-// ---- SOFT: min-sum under syndrome priors (qec_decoder_set_syndrome_priors; DESIGN.md section 2, "The soft-syndrome
-// form").  The SOFT instantiations of the MINSUM and LAYERED bodies; the others do not change.  Check c has one virtual
-// input mu[c], the channel LLR of its measurement-error variable, read from the handle's table (mX + mZ floats that every
-// workgroup shares).  The syndrome byte of the workspace holds the entry as 0, 1 or 2 = any other value in bits 0-1 and
-// the measurement decision f_c in bit 2 (a general code's degree is read from chkDeg instead): the thread that updates
-// check c rewrites the byte, the syndrome tests XOR the bit into the row's parity.  No further workspace.
-struct SoftArgs {
-    GeneralArgs g;           // chkDeg = nullptr for a regular code
-    const float* mu;         // mX + mZ channel LLRs of the measurement-error variables
-    uint8_t* fX;             // nullable: [B][mX] measurement decisions out
-    uint8_t* fZ;             // nullable: [B][mZ]
-};
-
+// SOFT: min-sum under syndrome priors (qec_decoder_set_syndrome_priors; DESIGN.md section 2, "The soft-syndrome form").
+// The SOFT instantiations of the MINSUM and LAYERED bodies; the others do not change.  Check c has one virtual input mu[c],
+// the channel LLR of its measurement-error variable, read from the handle's table (mX + mZ floats that every workgroup
+// shares).  The syndrome byte of the workspace holds the entry as 0, 1 or 2 = any other value in bits 0-1 and the measurement
+// decision f_c in bit 2 (a general code's degree is read from chkDeg instead): the thread that updates check c rewrites the
+// byte, the syndrome tests XOR the bit into the row's parity.  No further workspace.  The SOFT bodies keep helpers of their
+// own (sp_soft_load_syndromes, sp_soft_check, sp_soft_syndrome_fails) and their pointers as __restrict__ parameters: folded
+// into the plain helpers' SOFT forms, or read from the block, their kernels' instruction streams moved and a small general
+// code measured up to 3.9 % slower.
 __device__ __forceinline__ void sp_soft_load_syndromes(const SparseArgs& a, const float* __restrict__ mu, long long b,
                                                        uint8_t* syn)
 {
@@ -905,9 +935,23 @@ __device__ __forceinline__ void sp_soft_syndrome_fails(const SparseArgs& a, cons
     }
 }
 
+// Check c's update in place, from its row of slots and its syndrome byte; SOFT rewrites the byte with the new f_c.
+// dc is the caller's copy of the block's dc.
+template <bool GENERAL, bool SOFT>
+__device__ __forceinline__ void sp_minsum_check_row(const uint8_t* chkDeg, const float* mu, float* msg, uint8_t* syn, int c,
+                                                    int dc, float alpha)
+{
+    if constexpr (SOFT) {
+        const uint32_t sd = syn[c];
+        const bool f = sp_soft_check<GENERAL>(msg + (size_t)c * dc, dc, GENERAL ? (int)chkDeg[c] : dc, sd, mu[c], alpha);
+        syn[c] = (uint8_t)((sd & 3u) | (f ? 4u : 0u));
+    } else {
+        sp_minsum_check<GENERAL>(msg + (size_t)c * dc, dc, syn[c], alpha);
+    }
+}
+
 // The measurement decisions of syndrome pair b out, where requested
-__device__ __forceinline__ void sp_soft_store_flips(const SparseArgs& a, long long b, const uint8_t* syn, uint8_t* fX,
-                                                    uint8_t* fZ)
+__device__ __forceinline__ void sp_soft_store_flips(const SparseArgs& a, long long b, const uint8_t* syn, uint8_t* fX, uint8_t* fZ)
 {
     const int tid = threadIdx.x, nt = blockDim.x;
     const int mX = a.mX, mZ = a.mZ;
@@ -917,10 +961,12 @@ __device__ __forceinline__ void sp_soft_store_flips(const SparseArgs& a, long lo
         for (int c = tid; c < mZ; c += nt) fZ[b * mZ + c] = (syn[mX + c] >> 2) & 1u;
 }
 
-// One variable's update from its channel LLR; returns its decision (posterior < 0; a variable in no check decides 0)
+// One variable's update, the folds started from the bias `lam` (MINSUM: its channel LLR, RELAY: the leg's mix of that and
+// the memory, never -0.0f); returns the posterior and decides through `dec` (posterior < 0; a variable in no check
+// decides 0)
 template <int MAXDV, bool GENERAL>
-__device__ __forceinline__ bool sp_minsum_var(float* __restrict__ msg, const int32_t* __restrict__ ve, int dv, float lam,
-                                              bool last)
+__device__ __forceinline__ float sp_minsum_var(float* __restrict__ msg, const int32_t* __restrict__ ve, int dv, float lam,
+                                               bool last, bool& dec)
 {
     int idx[MAXDV];
     bool use[MAXDV];  // GENERAL: wave-uniform, some active lane has entry j
@@ -960,13 +1006,13 @@ __device__ __forceinline__ bool sp_minsum_var(float* __restrict__ msg, const int
                 post = post + r[j];
             }
     }
-    return idx[0] >= 0 && post < 0.0f;
+    dec = idx[0] >= 0 && post < 0.0f;
+    return post;
 }
 
-template <int STOP, int MAXDC, int MAXDV, bool GENERAL, bool SOFT = false>
+template <int STOP, int MAXDC, int MAXDV, bool GENERAL, bool SOFT>
 __device__ __forceinline__ void sp_minsum_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws,
-                                                 const float* __restrict__ mu = nullptr, uint8_t* fX = nullptr,
-                                                 uint8_t* fZ = nullptr)
+        const float* __restrict__ mu = nullptr, uint8_t* fX = nullptr, uint8_t* fZ = nullptr)
 {
     const int tid = threadIdx.x, nt = blockDim.x;
     const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
@@ -980,6 +1026,9 @@ __device__ __forceinline__ void sp_minsum_decode(const SparseArgs& a, const uint
     const bool tab = llr != nullptr;  // workgroup-uniform: per-variable channel LLRs or the scalar one
     const int N = a.maxIter < 0 ? 0 : a.maxIter;
 
+    // The inside test, the slot initialisation and the q_final export are spelled out here and again in sp_relay_decode:
+    // as shared helpers each of them moved the instruction streams of RELAY or MINSUM kernels that are otherwise the
+    // parent's ("tried, changed the streams").
     auto any_inside = [&](bool& bx, bool& bz) {
         for (int e = tid; e < E; e += nt) {
             const bool in = sp_minsum_inside(msg[e]);
@@ -988,8 +1037,7 @@ __device__ __forceinline__ void sp_minsum_decode(const SparseArgs& a, const uint
     };
 
     for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
-        if constexpr (SOFT) sp_soft_load_syndromes(a, mu, b, syn);
-        else sp_load_syndromes<GENERAL>(a, chkDeg, b, syn);
+        if constexpr (SOFT) sp_soft_load_syndromes(a, mu, b, syn); else sp_load_syndromes<GENERAL>(a, chkDeg, b, syn);
         for (int e = tid; e < E; e += nt) {
             const int v = (GENERAL || tab) ? a.chkVar[e] : 0;
             float x = __uint_as_float(kMinSumCap);  // an unused slot of a general code
@@ -1011,20 +1059,16 @@ __device__ __forceinline__ void sp_minsum_decode(const SparseArgs& a, const uint
             itZ += actZ;
             for (int c = tid; c < m; c += nt) {
                 if (c < mX ? !actX : !actZ) continue;
-                if constexpr (SOFT) {
-                    const uint32_t sd = syn[c];
-                    const bool f = sp_soft_check<GENERAL>(msg + (size_t)c * dc, dc, GENERAL ? (int)chkDeg[c] : dc, sd, mu[c], alpha);
-                    syn[c] = (uint8_t)((sd & 3u) | (f ? 4u : 0u));
-                } else {
-                    sp_minsum_check<GENERAL>(msg + (size_t)c * dc, dc, syn[c], alpha);
-                }
+                sp_minsum_check_row<GENERAL, SOFT>(chkDeg, mu, msg, syn, c, dc, alpha);
             }
             __syncthreads();
             for (int v = tid; v < 2 * n; v += nt) {
                 if (v >= n ? !actZ : !actX) continue;
                 int dv;
                 const int32_t* ve = sp_var_edges(a, v, dv);
-                hd[v] = sp_minsum_var<MAXDV, GENERAL>(msg, ve, dv, tab ? llr[v] : lam0, last);
+                bool h;
+                sp_minsum_var<MAXDV, GENERAL>(msg, ve, dv, tab ? llr[v] : lam0, last, h);
+                hd[v] = h;
             }
             __syncthreads();
             if (STOP == QEC_STOP_REF && it % 10 == 0) {
@@ -1035,8 +1079,7 @@ __device__ __forceinline__ void sp_minsum_decode(const SparseArgs& a, const uint
                 if (actZ && !anyz) actZ = false;
             } else if (STOP == QEC_STOP_SYNDROME) {
                 bool bx = false, bz = false;
-                if constexpr (SOFT) sp_soft_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
-                else sp_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
+                if constexpr (SOFT) sp_soft_syndrome_fails<GENERAL>(a, syn, hd, bx, bz); else sp_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
                 const bool badx = __syncthreads_or(bx), badz = __syncthreads_or(bz);
                 if (actX && !badx) actX = false;
                 if (actZ && !badz) actZ = false;
@@ -1051,12 +1094,8 @@ __device__ __forceinline__ void sp_minsum_decode(const SparseArgs& a, const uint
         }
         const bool convFailX = __syncthreads_or(bx), convFailZ = __syncthreads_or(bz);
         bool sx = false, sz = false;
-        if constexpr (SOFT) {
-            sp_soft_syndrome_fails<GENERAL>(a, syn, hd, sx, sz);
-            sp_soft_store_flips(a, b, syn, fX, fZ);
-        } else {
-            sp_syndrome_fails<GENERAL>(a, syn, hd, sx, sz);
-        }
+        if constexpr (SOFT) sp_soft_syndrome_fails<GENERAL>(a, syn, hd, sx, sz); else sp_syndrome_fails<GENERAL>(a, syn, hd, sx, sz);
+        if constexpr (SOFT) sp_soft_store_flips(a, b, syn, fX, fZ);
         const bool synFailX = __syncthreads_or(sx), synFailZ = __syncthreads_or(sz);
         if (a.q != nullptr)
             for (int e = tid; e < E; e += nt) a.q[b * E + e] = (!GENERAL || a.chkVar[e] >= 0) ? msg[e] : 0.0f;
@@ -1092,10 +1131,9 @@ __device__ __forceinline__ float sp_layered_fold(const float* __restrict__ msg, 
     return t;
 }
 
-template <int STOP, int MAXDC, int MAXDV, bool GENERAL, bool SOFT = false>
+template <int STOP, int MAXDC, int MAXDV, bool GENERAL, bool SOFT>
 __device__ __forceinline__ void sp_layered_decode(const SparseArgs& a, const uint8_t* __restrict__ chkDeg, uint8_t* ws,
-                                                  const float* __restrict__ mu = nullptr, uint8_t* fX = nullptr,
-                                                  uint8_t* fZ = nullptr)
+        const float* __restrict__ mu = nullptr, uint8_t* fX = nullptr, uint8_t* fZ = nullptr)
 {
     const int tid = threadIdx.x, nt = blockDim.x;
     const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
@@ -1127,8 +1165,7 @@ __device__ __forceinline__ void sp_layered_decode(const SparseArgs& a, const uin
     };
 
     for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
-        if constexpr (SOFT) sp_soft_load_syndromes(a, mu, b, syn);
-        else sp_load_syndromes<GENERAL>(a, chkDeg, b, syn);
+        if constexpr (SOFT) sp_soft_load_syndromes(a, mu, b, syn); else sp_load_syndromes<GENERAL>(a, chkDeg, b, syn);
         for (int e = tid; e < E; e += nt)
             msg[e] = (!GENERAL || a.chkVar[e] >= 0) ? 0.0f : __uint_as_float(kMinSumCap);
         __syncthreads();
@@ -1157,13 +1194,7 @@ __device__ __forceinline__ void sp_layered_decode(const SparseArgs& a, const uin
                 // the layer's checks, a thread per check: the row becomes the check's R
                 for (int i = tid; i < nx + nz; i += nt) {
                     const int c = a.layOrder[i < nx ? x0 + i : z0 + (i - nx)];
-                    if constexpr (SOFT) {
-                        const uint32_t sd = syn[c];
-                        const bool f = sp_soft_check<GENERAL>(msg + (size_t)c * dc, dc, GENERAL ? (int)chkDeg[c] : dc, sd, mu[c], alpha);
-                        syn[c] = (uint8_t)((sd & 3u) | (f ? 4u : 0u));
-                    } else {
-                        sp_minsum_check<GENERAL>(msg + (size_t)c * dc, dc, syn[c], alpha);
-                    }
+                    sp_minsum_check_row<GENERAL, SOFT>(chkDeg, mu, msg, syn, c, dc, alpha);
                 }
                 __syncthreads();
             }
@@ -1178,8 +1209,7 @@ __device__ __forceinline__ void sp_layered_decode(const SparseArgs& a, const uin
                 posterior(actX, actZ, bx, bz);
                 __syncthreads();
                 bx = bz = false;
-                if constexpr (SOFT) sp_soft_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
-                else sp_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
+                if constexpr (SOFT) sp_soft_syndrome_fails<GENERAL>(a, syn, hd, bx, bz); else sp_syndrome_fails<GENERAL>(a, syn, hd, bx, bz);
                 const bool badx = __syncthreads_or(bx), badz = __syncthreads_or(bz);
                 if (actX && !badx) actX = false;
                 if (actZ && !badz) actZ = false;
@@ -1194,12 +1224,8 @@ __device__ __forceinline__ void sp_layered_decode(const SparseArgs& a, const uin
             if (v >= n) a.eZ[b * n + (v - n)] = hd[v]; else a.eX[b * n + v] = hd[v];
         }
         bool sx = false, sz = false;
-        if constexpr (SOFT) {
-            sp_soft_syndrome_fails<GENERAL>(a, syn, hd, sx, sz);
-            sp_soft_store_flips(a, b, syn, fX, fZ);
-        } else {
-            sp_syndrome_fails<GENERAL>(a, syn, hd, sx, sz);
-        }
+        if constexpr (SOFT) sp_soft_syndrome_fails<GENERAL>(a, syn, hd, sx, sz); else sp_syndrome_fails<GENERAL>(a, syn, hd, sx, sz);
+        if constexpr (SOFT) sp_soft_store_flips(a, b, syn, fX, fZ);
         const bool synFailX = __syncthreads_or(sx), synFailZ = __syncthreads_or(sz);
         if (a.q != nullptr)
             for (int e = tid; e < E; e += nt) {
@@ -1222,10 +1248,9 @@ __device__ __forceinline__ void sp_layered_decode(const SparseArgs& a, const uin
 // The min-sum body with one fp32 memory M_v per variable and a chain of legs: each leg starts from channel-LLR slots and
 // the previous leg's posteriors in M, runs under the call's stop rule counted within the leg, and a leg whose final
 // decisions satisfy the syndrome is a solution; the sector ends at its S-th solution or after its last leg and returns
-// the lightest solution.  The check update is sp_minsum_check, the variable update sp_minsum_var's folds started from
-// the bias b = ((1 - g) lam + g M) + 0.0f (never -0.0f, as that function's padding needs).
-// The entry bp_relay_kernel has its own argument block: SparseArgs as the MINSUM kernels read it, a general code's
-// degree bytes, and the relay's tables, so that no field of the other kernels' blocks moves.  Workspace, grid and
+// the lightest solution.  The check update is sp_minsum_check_row, the variable update sp_minsum_var with its folds
+// started from the bias b = ((1 - g) lam + g M) + 0.0f (never -0.0f, as that function's padding needs).
+// The argument block is read as the MINSUM kernels read it, with the relay's own fields behind it (RelayArgs).  Workspace, grid and
 // workgroup are the scalar plan's; the extra state -- M (2n floats) and the best decisions (2n bytes) -- lives in the
 // workgroup's slice of a global region (relayWs), where entry v is read and written by v's own thread only (the same
 // thread in every pass, v = tid + k nt), so it needs no barrier of its own.
@@ -1236,74 +1261,17 @@ __device__ __forceinline__ void sp_layered_decode(const SparseArgs& a, const uin
 //     executed leg for the flags and the export;
 //   * the weight W of a solution is formed only with S > 1 (workgroup-uniform): per-thread sums of w_v over the set
 //     decision bytes, added into two static LDS words (integer adds: the order does not matter), no global atomics.
-struct RelayArgs {
-    SparseArgs s;            // as the MINSUM kernels read it (errorProbability = lambda(p'), prior = the LLRs, c0 = alpha)
-    const uint8_t* chkDeg;   // a general code's degree bytes (null: regular)
-    const float* gamma;      // [legs][sector][n]
-    const int32_t* weight;   // null (w_v = 1), or sector X [n] then Z [n]: the handle's integer weight tables
-    uint8_t* relayWs;        // per workgroup: M [2n] floats, best [2n] bytes
-    long long relayStride;   // bytes per workgroup
-    int legs, solutions;
-};
-
-// sp_minsum_var from the bias b; returns the posterior, decides through `dec`
-template <int MAXDV, bool GENERAL>
-__device__ __forceinline__ float sp_relay_var(float* __restrict__ msg, const int32_t* __restrict__ ve, int dv, float b,
-                                              bool last, bool& dec)
-{
-    int idx[MAXDV];
-    bool use[MAXDV];  // GENERAL: wave-uniform, some active lane has entry j
-    float r[MAXDV];
-#pragma unroll
-    for (int j = 0; j < MAXDV; ++j) {
-        idx[j] = -1;
-        if (j < dv) idx[j] = ve[j];
-        use[j] = GENERAL ? __builtin_amdgcn_ballot_w64(idx[j] >= 0) != 0 : j < dv;
-    }
-#pragma unroll
-    for (int j = 0; j < MAXDV; ++j)
-        if (use[j]) {
-            const bool real = idx[j] >= 0;
-            const float x = msg[real ? idx[j] : 0];  // a padded lane's value is dropped by the select
-            r[j] = real ? x : 0.0f;
-        }
-    float post = b;
-    if (last) {
-#pragma unroll
-        for (int k = 0; k < MAXDV; ++k)
-            if (use[k]) post = post + r[k];
-#pragma unroll
-        for (int j = 0; j < MAXDV; ++j)
-            if (use[j] && idx[j] >= 0) msg[idx[j]] = post;
-    } else {
-#pragma unroll
-        for (int j = 0; j < MAXDV; ++j)
-            if (use[j]) {
-                float t = post;  // b + r_0 + ... + r_{j-1}
-#pragma unroll
-                for (int k = j + 1; k < MAXDV; ++k)
-                    if (use[k]) t = t + r[k];
-                if (idx[j] >= 0) msg[idx[j]] = t;
-                post = post + r[j];
-            }
-    }
-    dec = idx[0] >= 0 && post < 0.0f;
-    return post;
-}
-
 template <int STOP, int MAXDC, int MAXDV, bool GENERAL>
-__device__ __forceinline__ void sp_relay_decode(const RelayArgs& ra, uint8_t* ws)
+__device__ __forceinline__ void sp_relay_decode(const RelayArgs& a, uint8_t* ws)
 {
     __shared__ uint32_t wsum[2];  // the weights of sector X's and sector Z's solution (S > 1)
-    const SparseArgs& a = ra.s;
-    const uint8_t* __restrict__ chkDeg = ra.chkDeg;
     const int tid = threadIdx.x, nt = blockDim.x;
     const int n = a.n, mX = a.mX, mZ = a.mZ, m = mX + mZ, dc = a.dc;
     const int EX = mX * dc, E = m * dc;
     float* msg = reinterpret_cast<float*>(ws);            // E floats
     uint8_t* syn = ws + (size_t)E * sizeof(float);        // m bytes: sX then sZ
     uint8_t* hd = syn + m;                                // 2n bytes: X then Z decisions
-    uint8_t* rws = ra.relayWs + (long long)blockIdx.x * ra.relayStride;
+    uint8_t* rws = a.relayWs + (long long)blockIdx.x * a.relayStride;
     float* mem = reinterpret_cast<float*>(rws);           // M: 2n floats, X then Z
     uint8_t* best = rws + (size_t)2 * n * sizeof(float);  // 2n bytes: the best solution's decisions
 
@@ -1311,7 +1279,7 @@ __device__ __forceinline__ void sp_relay_decode(const RelayArgs& ra, uint8_t* ws
     const float* llr = a.prior;
     const bool tab = llr != nullptr;  // workgroup-uniform: per-variable channel LLRs or the scalar one
     const int N = a.maxIter < 0 ? 0 : a.maxIter;
-    const int L = ra.legs, S = ra.solutions;
+    const int L = a.legs, S = a.solutions;
     const bool weigh = S > 1;
 
     // the slots of sector X (doX) / Z (doZ) at the start of a leg: the channel LLR of the slot's variable
@@ -1326,7 +1294,7 @@ __device__ __forceinline__ void sp_relay_decode(const RelayArgs& ra, uint8_t* ws
     };
 
     for (long long b = blockIdx.x; b < a.B; b += gridDim.x) {
-        sp_load_syndromes<GENERAL>(a, chkDeg, b, syn);
+        sp_load_syndromes<GENERAL>(a, a.chkDeg, b, syn);
         init_slots(true, true);
         for (int v = tid; v < 2 * n; v += nt) {  // leg 0: M = lambda; the decisions of N = 0
             int dv;
@@ -1349,7 +1317,7 @@ __device__ __forceinline__ void sp_relay_decode(const RelayArgs& ra, uint8_t* ws
                 its[1] += act[1];
                 for (int c = tid; c < m; c += nt) {
                     if (c < mX ? !act[0] : !act[1]) continue;
-                    sp_minsum_check<GENERAL>(msg + (size_t)c * dc, dc, syn[c], alpha);
+                    sp_minsum_check_row<GENERAL, false>(a.chkDeg, nullptr, msg, syn, c, dc, alpha);
                 }
                 __syncthreads();
                 for (int v = tid; v < 2 * n; v += nt) {
@@ -1358,14 +1326,14 @@ __device__ __forceinline__ void sp_relay_decode(const RelayArgs& ra, uint8_t* ws
                     int dv;
                     const int32_t* ve = sp_var_edges(a, v, dv);
                     const float lam = tab ? llr[v] : lam0;
-                    const float g = ra.gamma[((size_t)(z ? leg[1] : leg[0]) * 2 + z) * n + (z ? v - n : v)];
+                    const float g = a.gamma[((size_t)(z ? leg[1] : leg[0]) * 2 + z) * n + (z ? v - n : v)];
                     const float t0 = 1.0f - g;
                     const float t1 = t0 * lam;
                     const float t2 = g * mem[v];
                     float bias = t1 + t2;
                     bias = bias + 0.0f;  // -0.0f becomes +0.0f
                     bool h;
-                    mem[v] = sp_relay_var<MAXDV, GENERAL>(msg, ve, dv, bias, z ? lastZ : lastX, h);
+                    mem[v] = sp_minsum_var<MAXDV, GENERAL>(msg, ve, dv, bias, z ? lastZ : lastX, h);
                     hd[v] = h;
                 }
                 __syncthreads();
@@ -1414,7 +1382,7 @@ __device__ __forceinline__ void sp_relay_decode(const RelayArgs& ra, uint8_t* ws
                 for (int v = tid; v < 2 * n; v += nt) {
                     const bool z = v >= n;
                     if (!(z ? solved[1] : solved[0]) || !hd[v]) continue;
-                    const uint32_t w = ra.weight != nullptr ? (uint32_t)ra.weight[v] : 1u;
+                    const uint32_t w = a.weight != nullptr ? (uint32_t)a.weight[v] : 1u;
                     if (z) wz += w; else wx += w;
                 }
                 if (wx) atomicAdd(&wsum[0], wx);
@@ -1461,91 +1429,42 @@ __device__ __forceinline__ void sp_relay_decode(const RelayArgs& ra, uint8_t* ws
     }
 }
 
-// ---- the kernels ---------------------------------------------------------------
-// Both entries run the same bodies; they differ in GENERAL and in the degree bytes that a general code brings.
-template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false, bool SERIAL = false,
-          bool MINSUM = false>
-__global__ __launch_bounds__(kSparseThreads) void bp_sparse_kernel(const SparseArgs a)
+// ---- the kernel ----------------------------------------------------------------
+// The one entry: the workspace, and the body that BODY names.
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL, int BODY>
+__global__ __launch_bounds__(kSparseThreads) void bp_sparse_kernel(const SparseArgsOf<BODY> a)
 {
     uint8_t* ws = LDS ? sp_lds : a.scratch + (long long)blockIdx.x * a.ws_bytes;
-    if constexpr (MINSUM) sp_minsum_decode<STOP, MAXDC, MAXDV, false>(a, nullptr, ws);
-    else if constexpr (SERIAL) sp_serial_decode<STOP, MAXDC, MAXDV, false>(a, nullptr, ws);
-    else if constexpr (CORR) sp_corr_decode<STOP, MAXDC, MAXDV, false>(a, nullptr, ws);
-    else sp_flood_decode<STOP, MAXDC, MAXDV, false, PRIORS>(a, nullptr, ws);
-}
-
-template <int STOP, int MAXDC, int MAXDV, bool LDS, bool PRIORS = false, bool CORR = false, bool SERIAL = false,
-          bool MINSUM = false>
-__global__ __launch_bounds__(kSparseThreads) void bp_general_kernel(const GeneralArgs ga)
-{
-    uint8_t* ws = LDS ? sp_lds : ga.s.scratch + (long long)blockIdx.x * ga.s.ws_bytes;
-    if constexpr (MINSUM) sp_minsum_decode<STOP, MAXDC, MAXDV, true>(ga.s, ga.chkDeg, ws);
-    else if constexpr (SERIAL) sp_serial_decode<STOP, MAXDC, MAXDV, true>(ga.s, ga.chkDeg, ws);
-    else if constexpr (CORR) sp_corr_decode<STOP, MAXDC, MAXDV, true>(ga.s, ga.chkDeg, ws);
-    else sp_flood_decode<STOP, MAXDC, MAXDV, true, PRIORS>(ga.s, ga.chkDeg, ws);
-}
-
-// The relay's one entry for both routes (its argument block carries the degree bytes)
-template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL>
-__global__ __launch_bounds__(kSparseThreads) void bp_relay_kernel(const RelayArgs ra)
-{
-    uint8_t* ws = LDS ? sp_lds : ra.s.scratch + (long long)blockIdx.x * ra.s.ws_bytes;
-    sp_relay_decode<STOP, MAXDC, MAXDV, GENERAL>(ra, ws);
-}
-
-// Layered min-sum's one entry for both routes (a regular code brings no degree bytes)
-template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL>
-__global__ __launch_bounds__(kSparseThreads) void bp_layered_kernel(const GeneralArgs ga)
-{
-    uint8_t* ws = LDS ? sp_lds : ga.s.scratch + (long long)blockIdx.x * ga.s.ws_bytes;
-    sp_layered_decode<STOP, MAXDC, MAXDV, GENERAL>(ga.s, ga.chkDeg, ws);
-}
-
-// Min-sum under syndrome priors: one entry for both routes and both schedules (SoftArgs)
-template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL, bool LAYERED>
-__global__ __launch_bounds__(kSparseThreads) void bp_soft_kernel(const SoftArgs sa)
-{
-    const SparseArgs& a = sa.g.s;
-    uint8_t* ws = LDS ? sp_lds : a.scratch + (long long)blockIdx.x * a.ws_bytes;
-    if constexpr (LAYERED) sp_layered_decode<STOP, MAXDC, MAXDV, GENERAL, true>(a, sa.g.chkDeg, ws, sa.mu, sa.fX, sa.fZ);
-    else sp_minsum_decode<STOP, MAXDC, MAXDV, GENERAL, true>(a, sa.g.chkDeg, ws, sa.mu, sa.fX, sa.fZ);
+    if constexpr (BODY == kScalar || BODY == kPriors) sp_flood_decode<STOP, MAXDC, MAXDV, GENERAL, BODY == kPriors>(a, ws);
+    else if constexpr (BODY == kCorr) sp_corr_decode<STOP, MAXDC, MAXDV, GENERAL>(a, ws);
+    else if constexpr (BODY == kSerial) sp_serial_decode<STOP, MAXDC, MAXDV, GENERAL>(a, ws);
+    else if constexpr (BODY == kMinSum || BODY == kSoftMinSum)
+    {
+        if constexpr (BODY == kSoftMinSum) sp_minsum_decode<STOP, MAXDC, MAXDV, GENERAL, true>(a, a.chkDeg, ws, a.mu, a.fX, a.fZ);
+        else sp_minsum_decode<STOP, MAXDC, MAXDV, GENERAL, false>(a, a.chkDeg, ws);
+    }
+    else if constexpr (BODY == kRelay) sp_relay_decode<STOP, MAXDC, MAXDV, GENERAL>(a, ws);
+    else if constexpr (BODY == kSoftLayered) sp_layered_decode<STOP, MAXDC, MAXDV, GENERAL, true>(a, a.chkDeg, ws, a.mu, a.fX, a.fZ);
+    else sp_layered_decode<STOP, MAXDC, MAXDV, GENERAL, false>(a, a.chkDeg, ws);
 }
 
 // ---- plan ------------------------------------------------------------------
-// The kernels of one shape, by variant and stop rule.  SERIAL takes priors as a runtime branch, CORR, MINSUM, RELAY and
-// LAYERED too.
-enum { kScalar = 0, kPriors = 1, kCorr = 2, kSerial = 3, kMinSum = 4, kRelay = 5, kLayered = 6, kSoftMinSum = 7,
-       kSoftLayered = 8, kVariants = 9 };
+// The kernels of one shape, by body and stop rule.
 using SparseKernels = const void* [kVariants][3];
 
-template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL, bool PRIORS, bool CORR, bool SERIAL, bool MINSUM = false>
-static const void* sparse_kernel()
+template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL, int... BODY>
+static void sparse_kernels_of_stop(SparseKernels& fn, std::integer_sequence<int, BODY...>)
 {
-    if constexpr (GENERAL)
-        return reinterpret_cast<const void*>(&bp_general_kernel<STOP, MAXDC, MAXDV, LDS, PRIORS, CORR, SERIAL, MINSUM>);
-    else return reinterpret_cast<const void*>(&bp_sparse_kernel<STOP, MAXDC, MAXDV, LDS, PRIORS, CORR, SERIAL, MINSUM>);
-}
-
-template <int STOP, int MAXDC, int MAXDV, bool LDS, bool GENERAL>
-static void sparse_kernels_of_stop(SparseKernels& fn)
-{
-    fn[kScalar][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, false, false>();
-    fn[kPriors][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, true, false, false>();
-    fn[kCorr][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, true, false>();
-    fn[kSerial][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, false, true>();
-    fn[kMinSum][STOP] = sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false, false, false, true>();
-    fn[kRelay][STOP] = reinterpret_cast<const void*>(&bp_relay_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL>);
-    fn[kLayered][STOP] = reinterpret_cast<const void*>(&bp_layered_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL>);
-    fn[kSoftMinSum][STOP] = reinterpret_cast<const void*>(&bp_soft_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, false>);
-    fn[kSoftLayered][STOP] = reinterpret_cast<const void*>(&bp_soft_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, true>);
+    ((fn[BODY][STOP] = reinterpret_cast<const void*>(&bp_sparse_kernel<STOP, MAXDC, MAXDV, LDS, GENERAL, BODY>)), ...);
 }
 
 template <int MAXDC, int MAXDV, bool LDS, bool GENERAL>
 static void sparse_kernels(SparseKernels& fn)
 {
-    sparse_kernels_of_stop<QEC_STOP_REF, MAXDC, MAXDV, LDS, GENERAL>(fn);
-    sparse_kernels_of_stop<QEC_STOP_FIXED, MAXDC, MAXDV, LDS, GENERAL>(fn);
-    sparse_kernels_of_stop<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, GENERAL>(fn);
+    const std::make_integer_sequence<int, kVariants> bodies;
+    sparse_kernels_of_stop<QEC_STOP_REF, MAXDC, MAXDV, LDS, GENERAL>(fn, bodies);
+    sparse_kernels_of_stop<QEC_STOP_FIXED, MAXDC, MAXDV, LDS, GENERAL>(fn, bodies);
+    sparse_kernels_of_stop<QEC_STOP_SYNDROME, MAXDC, MAXDV, LDS, GENERAL>(fn, bodies);
 }
 
 template <int MAXDC, int MAXDV>
@@ -1561,7 +1480,7 @@ struct SparsePlan {
     long long ws_bytes = 0;
     int grid = 0;
     SparseKernels fn = {};
-    // a general code: bp_general_kernel, its degree bytes and its fitted workgroup size
+    // a general code: its degree bytes and its fitted workgroup size
     bool general = false;
     DeviceArray<uint8_t> chkDeg;
     int threads = kSparseThreads;
@@ -1779,40 +1698,24 @@ int launch_decode_sparse(void* plan, const SparseDecode& d, hipStream_t stream)
         a.prior = d.prior != nullptr ? d.llr : nullptr;
         a.c0 = (float)d.minsum / 256.0f;
     }
-    GeneralArgs ga{a, p->chkDeg.data()};
-    void* args[] = {p->general ? static_cast<void*>(&ga) : static_cast<void*>(&a)};  // the entry's one argument
+    a.chkDeg = p->general ? p->chkDeg.data() : nullptr;
     int variant = d.minsum ? kMinSum : d.serial ? kSerial : d.corr ? kCorr : d.prior ? kPriors : kScalar;
-    RelayArgs ra{};
     if (d.minsum && d.gamma != nullptr) {  // min-sum with relay tables: the RELAY kernels
         if (d.legs < 1 || d.solutions < 1 || p->relay_ws.data() == nullptr)
             return fail(QEC_ERR_ARG, "bp_sparse launch: the relay needs its tables and its workspace (qec_decoder_set_relay)");
-        ra.s = a;
-        ra.chkDeg = p->general ? p->chkDeg.data() : nullptr;
-        ra.gamma = d.gamma;
-        ra.weight = d.relay_weight;
-        ra.relayWs = p->relay_ws.data();
-        ra.relayStride = p->relay_stride;
-        ra.legs = d.legs;
-        ra.solutions = d.solutions;
-        args[0] = &ra;
         variant = kRelay;
     }
-    if (d.minsum && d.gamma == nullptr && d.layered) {  // plain min-sum under QEC_OPT_MINSUM_SCHEDULE = 1: the LAYERED kernels
-        args[0] = &ga;
+    if (d.minsum && d.gamma == nullptr && d.layered)  // plain min-sum under QEC_OPT_MINSUM_SCHEDULE = 1: the LAYERED kernels
         variant = kLayered;
-    }
-    SoftArgs sa{};
     if (d.mu != nullptr) {  // syndrome priors (qec_decoder_set_syndrome_priors): the SOFT kernels of plain min-sum
         if (!d.minsum || d.gamma != nullptr)
             return fail(QEC_ERR_UNSUPPORTED, "bp_sparse launch: syndrome priors are built for plain min-sum");
-        sa.g = ga;
-        if (!p->general) sa.g.chkDeg = nullptr;
-        sa.mu = d.mu;
-        sa.fX = d.fX;
-        sa.fZ = d.fZ;
-        args[0] = &sa;
         variant = d.layered ? kSoftLayered : kSoftMinSum;
     }
+    // the entry's one argument: the block, or the block with the body's own fields behind it (SparseArgsOf)
+    RelayArgs ra{a, d.gamma, d.relay_weight, p->relay_ws.data(), p->relay_stride, d.legs, d.solutions};
+    SoftArgs sa{a, d.mu, d.fX, d.fZ};
+    void* args[] = {variant == kRelay ? static_cast<void*>(&ra) : d.mu != nullptr ? static_cast<void*>(&sa) : static_cast<void*>(&a)};
     const unsigned grid = (unsigned)std::min<long long>(d.B, p->grid);
     (void)hipLaunchKernel(p->fn[variant][d.stop], dim3(grid), dim3(p->threads), args, p->lds ? (size_t)p->ws_bytes : 0, stream);
     hipError_t err = hipGetLastError();

@@ -1,5 +1,5 @@
-"""Per-qubit priors on the GPU: the PRIORS instantiations of bp_general_kernel (general codes) and
-bp_sparse_kernel (regular codes through engine="sparse") against the CPU engine and the numpy yardstick of
+"""Per-qubit priors on the GPU: the PRIORS instantiations of bp_sparse_kernel, GENERAL (general codes) and
+regular (regular codes through engine="sparse"), against the CPU engine and the numpy yardstick of
 test_priors.py, the independent sampler against its numpy restatement, and the Monte-Carlo pipeline with priors
 against a host recount."""
 import numpy as np
@@ -13,8 +13,8 @@ from test_priors import F32, VECTORS, code_of, independent, inputs, matrices, pr
 
 pytestmark = pytest.mark.gpu
 
-GENERAL = ("surf3", "hgp_ham", "ham_rep3+1")     # bp_general_kernel
-REGULAR_SPARSE = ("G13", "P7")                    # bp_sparse_kernel
+GENERAL = ("surf3", "hgp_ham", "ham_rep3+1")     # bp_sparse_kernel, GENERAL
+REGULAR_SPARSE = ("G13", "P7")                    # bp_sparse_kernel, regular
 _decoders = {}
 
 

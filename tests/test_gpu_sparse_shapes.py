@@ -77,7 +77,7 @@ def test_describe_confirms_the_predicted_instantiation(case):
         if name in LARGE_REGULAR:  # P > 64 has no wave-circulant kernel: auto is the sparse engine
             assert q.DecoderGPU(code, 0).describe() == d
     # the kernel behind that line, for every stop rule and both prior forms
-    kernel = "bp_general_kernel" if d.startswith("sparse-general") else "bp_sparse_kernel"
+    kernel = "general" if d.startswith("sparse-general") else "regular"
     mem = "hbm" if " hbm " in d else "lds"
     for pri in (False, True):
         for stop in STOPS:

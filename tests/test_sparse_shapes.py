@@ -1,5 +1,5 @@
 """Every instantiation of the sparse-graph BP kernels (bp_sparse.hip): the test codes that reach each of
-the 72 decode kernels -- bp_sparse_kernel / bp_general_kernel x (8,4) (16,8) (32,16) x LDS / HBM workspace x
+the 72 decode kernels -- bp_sparse_kernel's regular / general route x (8,4) (16,8) (32,16) x LDS / HBM workspace x
 scalar prior / PRIORS x 3 stop rules --, a restatement of sparse_plan_create's choice among them, the case
 table that tests/test_gpu_sparse_shapes.py runs on the device (asserted here to cover all 72), and the
 references those runs are held to, checked here against the CPU engine:
@@ -15,11 +15,11 @@ Every comparison is bit for bit (q_final as uint32 patterns, NaN matching NaN). 
 
 Which code runs which shape (each with the scalar p and with priors, under the three stop rules):
 
-  kernel             shape    LDS                                    HBM
-  bp_sparse_kernel   (8,4)    r3-3-6-13                              r3-3-6-1013 (164 112 B)
+  route              shape    LDS                                    HBM
+  regular            (8,4)    r3-3-6-13                              r3-3-6-1013 (164 112 B)
                      (16,8)   r4-5-10-7                              r4-5-10-467
                      (32,16)  r3-9-20-7, r2-12-6-13, r3-3-18-5       r3-9-20-163
-  bp_general_kernel  (8,4)    hgp_ham, r3-3-6-13                     hgp_ham*140 (186 768 B)
+  general            (8,4)    hgp_ham, r3-3-6-13                     hgp_ham*140 (186 768 B)
                      (16,8)   mid, r4-5-10-7                         mid*40 (169 648 B)
                      (32,16)  wide, dense32, tall, r3-9-20-7,        wide*15 (177 824 B)
                               r2-12-6-13, r3-3-18-5
@@ -140,8 +140,8 @@ def matrices(name):
 
 
 def code_of(name, route):
-    """route "graph": the generated regular code (bp_sparse_kernel); "general": the code from its two matrices
-    (bp_general_kernel)."""
+    """route "graph": the generated regular code (bp_sparse_kernel's regular route, GENERAL = false); "general": the
+    code from its two matrices (GENERAL = true)."""
     key = (name, route)
     if key not in _codes:
         if route == "graph":
@@ -153,7 +153,7 @@ def code_of(name, route):
 
 
 # ---- sparse_plan_create, restated -----------------------------------------------------------------------------
-KERNELS = ("bp_sparse_kernel", "bp_general_kernel")
+KERNELS = ("regular", "general")  # the route: bp_sparse_kernel<..., GENERAL = false / true, BODY>
 SHAPES = ((8, 4), (16, 8), (32, 16))
 ALL_INSTANCES = {(k, s, mem, pri, stop) for k in KERNELS for s in SHAPES for mem in ("lds", "hbm")
                  for pri in (False, True) for stop in STOPS}
@@ -249,7 +249,7 @@ def test_pinned_shapes(name):
         plan = plan_of(code, route == "general")
         assert plan["shape"] == shape
         assert plan["mem"] == ("lds" if is_lds((name, route)) else "hbm")
-        assert plan["kernel"] == ("bp_general_kernel" if route == "general" else "bp_sparse_kernel")
+        assert plan["kernel"] == ("general" if route == "general" else "regular")
         if route == "general":
             assert plan["threads"] == threads
         if name in WS_BYTES:

@@ -1,4 +1,4 @@
-"""Measurements of the sparse-general kernel (bp_sparse.hip, bp_general_kernel)
+"""Measurements of the sparse-general kernel (bp_sparse.hip, bp_sparse_kernel with GENERAL)
 -> profiles/sparse_general.json.
 
   decode  the general kernel against the regular sparse kernel on the same regular code, the two sides

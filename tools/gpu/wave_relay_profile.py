@@ -1,7 +1,8 @@
 """Measurements of the wave relay kernels (QEC_OPT_RELAY_WAVE) -> profiles/wave_relay.json.
 
 One sparse-engine handle per code under min-sum at scale 160 with relay tables (relay_gammas, seed 1 for sector X and 2
-for Z), option 0 (the sparse RELAY kernels, bp_relay_kernel) against option 1 (the wave kernels of bp_wave_relay.hip),
+for Z), option 0 (the sparse RELAY kernels, bp_sparse_kernel with BODY = kRelay) against option 1 (the wave kernels of
+bp_wave_relay.hip),
 alternating launches in one process; medians and each side's run-to-run spread (max - min over the repetitions).  The
 baseline is always the option-0 run.
 

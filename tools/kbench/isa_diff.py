@@ -2,10 +2,12 @@
 parent commit and of this tree:
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fno-slp-vectorize \
         --cuda-device-only -S -o new.s qec_ldpc_amd/csrc/bp_sparse.hip      (and the same in a checkout of the parent)
-  python tools/kbench/isa_diff.py parent.s new.s
+  python tools/kbench/isa_diff.py parent.s new.s [pairs.txt]
 For every kernel symbol of either listing: whether its instruction stream (the body between its label and its
-.Lfunc_end, comments and local label numbers aside) is the same in both, and the VGPR count, LDS bytes and scratch
-bytes of kernels that only the second listing has.  Exit status 1 if a kernel of both listings differs."""
+.Lfunc_end, comments and local label numbers aside) is the same in both; for a pair that differs, whether the opcode
+sequence (the first token of each instruction line) is the same, and the VGPR count, LDS bytes and scratch bytes of both
+sides; and those figures for kernels that only the second listing has.  pairs.txt, lines of `old-symbol new-symbol`,
+pairs kernels that were renamed between the listings.  Exit status 1 if a kernel of both listings differs."""
 import re
 import sys
 
@@ -31,8 +33,15 @@ def kernels(path):
     return out
 
 
+def opcodes(lines):
+    return [ln.split()[0] for ln in lines if not ln.endswith(":")]
+
+
 def main():
     a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    if len(sys.argv) > 3:  # renamed kernels: the first listing's kernels under their new names
+        new_name = dict(ln.split() for ln in open(sys.argv[3]) if ln.strip())
+        a = {new_name.get(k, k): v for k, v in a.items()}
     same = [k for k in a if k in b and a[k][0] == b[k][0]]
     differ = [k for k in a if k in b and a[k][0] != b[k][0]]
     gone = [k for k in a if k not in b]
@@ -40,7 +49,10 @@ def main():
     print("kernels in both listings: %d, identical instruction streams: %d, different: %d, only in the first: %d, "
           "only in the second: %d" % (len(same) + len(differ), len(same), len(differ), len(gone), len(new)))
     for k in differ:
-        print("DIFFERENT", k, len(a[k][0]), "->", len(b[k][0]), "instructions")
+        print("DIFFERENT %s %d -> %d instructions, opcode sequence %s, VGPRs %d -> %d, static LDS %d -> %d B, "
+              "scratch %d -> %d B" % (k, len(a[k][0]), len(b[k][0]),
+                                      "same" if opcodes(a[k][0]) == opcodes(b[k][0]) else "differs",
+                                      a[k][1], b[k][1], a[k][2], b[k][2], a[k][3], b[k][3]))
     for k in gone:
         print("GONE", k)
     for k in new:
