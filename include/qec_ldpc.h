@@ -438,13 +438,24 @@ int qec_decoder_device(const qec_decoder* dec);         /* HIP device ordinal (o
  *     honours it, the _dev ones read it at the call and allocate nothing (a captured graph keeps the kernels it
  *     captured); the OSD stage's soft decode runs the same schedule (its column key reads q_final, here the
  *     posterior).  The near-hard jump never fires.  A schedule for the QC codes: on the hypergraph product hgp_ham it
- *     leaves more syndromes unsatisfied than flooding min-sum does (README).  A group applies the value to every part. */
+ *     leaves more syndromes unsatisfied than flooding min-sum does (README).  A group applies the value to every part.
+ *   QEC_OPT_LIGHT_MEMO (default 1; fixed and reference stop, no q_final requested; the wave-circulant kernels of
+ *     one-syndrome-per-wave codes with generated shifts, i.e. P61): a sector whose syndrome is that of one qubit
+ *     error, or of two whose checks are disjoint, takes its outcome from a table instead of decoding.  The update
+ *     rules of a quasi-cyclic code do not depend on the lane, so the outcome of such a sector depends only on its
+ *     class (the column, or both columns and the lane difference); the decoder's own kernels decode one
+ *     representative per class once per key (p', N, stop rule), on the stream of the first call that uses the key,
+ *     without synchronising; an entry is used only where that decode returned exactly the generating qubits with
+ *     both flags clear.  The table and the fill's workspace (about 22 MB for P61) are allocated by
+ *     qec_decoder_create.  A call captured into a graph while its key is cold runs without the table.  Every
+ *     output bit identical either way; 0 decodes those sectors by BP (for measurement).  Each part of a group
+ *     holds its own table. */
 enum { QEC_OPT_HARD_PATHS = 1, QEC_OPT_CYCLE_JUMP = 2, QEC_OPT_SCHEDULE = 3, QEC_OPT_SECTOR_SPLIT = 4,
        QEC_OPT_PHASE_STATS = 5, QEC_OPT_TRIAGE = 6, QEC_OPT_LAST_PATH = 7, QEC_OPT_MC_DECODE_TIME = 8,
        QEC_OPT_OSD = 9, QEC_OPT_OSD_ITERATIONS = 10, QEC_OPT_OSD_SECTORS = 11, QEC_OPT_OSD_SWEEP = 12,
        QEC_OPT_OSD_ORDER = 13, QEC_OPT_OSD_CS_SECTORS = 14, QEC_OPT_NEAR_HARD_JUMP = 15, QEC_OPT_OSD_SCORE = 16,
        QEC_OPT_CORRELATED = 17, QEC_OPT_BP_SCHEDULE = 18, QEC_OPT_BP_METHOD = 19, QEC_OPT_MINSUM_SCALE = 20,
-       QEC_OPT_MINSUM_WAVE = 21, QEC_OPT_RELAY_WAVE = 22, QEC_OPT_MINSUM_SCHEDULE = 23 };
+       QEC_OPT_MINSUM_WAVE = 21, QEC_OPT_RELAY_WAVE = 22, QEC_OPT_MINSUM_SCHEDULE = 23, QEC_OPT_LIGHT_MEMO = 24 };
 enum {
     QEC_PATH_ORDERED = 1,          /* dispatch order pass (schedule.hip) */
     QEC_PATH_SECTOR_ORDER = 2,     /* ... in the per-sector form (each sector's waves by its own weight) */

@@ -30,7 +30,7 @@ OPTION = {"hard_paths": 1, "cycle_jump": 2, "schedule": 3, "sector_split": 4, "p
           "last_path": 7, "mc_decode_time": 8, "osd": 9, "osd_iterations": 10, "osd_sectors": 11,
           "osd_sweep": 12, "osd_order": 13, "osd_cs_sectors": 14, "near_hard": 15, "osd_score": 16,
           "correlated": 17, "bp_schedule": 18, "bp_method": 19, "minsum_scale": 20,
-          "minsum_wave": 21, "relay_wave": 22, "minsum_schedule": 23}
+          "minsum_wave": 21, "relay_wave": 22, "minsum_schedule": 23, "light_memo": 24}
 OPTIONS = OPTION
 # values of the "bp_schedule" option (QEC_OPT_BP_SCHEDULE)
 BP_SCHEDULE = {"flooding": 0, "serial": 1}

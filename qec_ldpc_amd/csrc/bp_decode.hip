@@ -36,6 +36,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "qec_device.h"
@@ -219,6 +220,9 @@ struct BpArgs {
     // zero-syndrome outcome of each sector under the fixed / reference stop (zero_outcome; 0: none):
     // kZsValid | decision bit | conv-fail << 1 | syndrome-fail << 2 | iterations << 8
     uint32_t zs[2];
+    // light-sector outcome table of this launch (light_memo below; null: the path is off): a key header, then
+    // per sector L one-error and L L P two-error entries of 16 bits (0: not memoised, else the iteration count)
+    const uint16_t* memo;
     int SX[kMaxRL], SZ[kMaxRL];  // rotation of block (r, l) between check and variable views
     int DX[kMaxR], DZ[kMaxR];    // check-view lane lambda holds check (r, (lambda + D[r]) mod P)
     int CX[kMaxL], CZ[kMaxL];    // var-view lane mu holds variable (l, (mu + C[l]) mod P)
@@ -1320,6 +1324,102 @@ __device__ __forceinline__ void emit_decisions(const BpArgs& a, const Lane& ln, 
     wave_sync();  // the next sector reuses the stage
 }
 
+// ---- light sectors by table (fixed / reference stop, one-group waves) -------------------------------
+// The update rules do not depend on the lane: every fold runs over r and l in one order on every lane and every
+// rotation is cyclic on the P lanes of the group.  So the decode of a syndrome shifted cyclically by d lanes is
+// the decode of the original shifted by d, bit for bit, and for one launch (p', N, stop rule) the outcome of a
+// sector whose syndrome is that of one qubit error (l, mu) depends on l alone, that of two errors (l1, mu1),
+// (l2, mu2) on (l1, l2, (mu2 - mu1) mod P): mu is the variable-view lane, variable (l, mu) sits in check
+// (r, lane (mu - S[r][l]) mod P) of the check view.  The decoder's own kernels decode one representative per
+// class once per launch key (launch_memo_fill) and a table entry holds the iteration count where that decode
+// returned exactly the generating qubits with both flags clear (0 otherwise, and for pairs that share a check).
+// A sector finds its class from ballots of its syndrome bits, on the scalar side: the variables all of whose R
+// checks are set (cand below, R - 1 rotated ballots ANDed per column); with weight w in {R, 2R} and exactly w / R
+// of them, a non-zero entry says that their check sets are disjoint, so the syndrome IS the class's, shifted.
+// The table's header carries its key, so a launch replayed from a graph against a table filled for another key
+// decodes by BP.  Off (BpArgs::memo null): final messages requested, the option, N < 2; compiled out of the
+// syndrome stop, list mode, multi-group waves, the runtime-shift variants and the instrumented kernels (which
+// count executed iterations, as they do for zero syndromes).
+constexpr int kMemoHeader = 8;  // 16-bit words in front of the entries: bits of p', N, stop (32 bits each), 0
+constexpr int memo_entries(int L, int P) { return L + L * L * P; }  // per sector
+template <int STOP, class SH, bool GO>
+constexpr bool kLightMemo()
+{
+    return !QEC_PHASE_STATS && !GO && STOP != QEC_STOP_SYNDROME && SH::kStatic && 2 * SH::kP > 64 && SH::kP < 64;
+}
+
+// The table of this launch, read from the kernel arguments at its use (as near_T: a pointer held across the
+// sector costs the fixed-stop kernels a scalar pair they do not have).
+__device__ __forceinline__ const uint32_t* memo_table(const BpArgs&)
+{
+    static_assert(offsetof(BpArgs, memo) % sizeof(uint64_t) == 0, "offsetof(BpArgs, memo)");
+    const __attribute__((address_space(4))) uint64_t* k =
+        (const __attribute__((address_space(4))) uint64_t*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return reinterpret_cast<const uint32_t*>(k[offsetof(BpArgs, memo) / sizeof(uint64_t)]);
+}
+
+// True: the sector was one of a memoised class and its outputs are written.
+template <int R, int L, int SEC, int STOP, class SH>
+__device__ __forceinline__ bool light_memo(const BpArgs& a, const Lane& ln, uint32_t b, bool in_range, float pp,
+                                           uint32_t sbits, int& iters_out, uint8_t* __restrict__ stage)
+{
+    constexpr int P = SH::kP, GB = kGroupBase<SH>();
+    constexpr unsigned long long kRing = (1ull << P) - 1ull;
+    // row r's syndrome bits over the ring (the idle lanes hold sbits = 0): bit i = check (r, lane i)
+    unsigned long long bal[R];
+    int w = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        bal[r] = __ballot(((sbits >> r) & 1u) != 0u) >> GB;
+        w += __popcll(bal[r]);
+    }
+    if (w != R && w != 2 * R) return false;
+    if (__ballot((sbits & kNonBinary) != 0u) != 0ull) return false;
+    // the table and its key are requested here and used after the candidate search, which hides their latency
+    const uint32_t* __restrict__ tab = memo_table(a);
+    if (tab == nullptr) return false;
+    const uint32_t keyP = tab[0], keyN = tab[1], keyStop = tab[2];
+    // cand: bit mu = every check of variable (l, mu) is set
+    int cnt = 0, la = 0, lb = 0, ma = 0, mb = 0;
+#pragma unroll
+    for (int l = 0; l < L; ++l) {
+        unsigned long long c = kRing;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int s = SH::template shift<SEC, L>(nullptr, r, l);
+            c &= s == 0 ? bal[r] : ((bal[r] << s) | (bal[r] >> (P - s)));
+        }
+        if (c != 0ull) {
+            const int k = __popcll(c), first = __ffsll((long long)c) - 1;
+            if (cnt == 0) {
+                la = l;
+                ma = first;
+                if (k > 1) {
+                    lb = l;
+                    mb = 63 - __clzll((long long)c);
+                }
+            } else if (cnt == 1) {
+                lb = l;
+                mb = first;
+            }
+            cnt += k;
+        }
+    }
+    if (cnt * R != w) return false;
+    if (keyP != __float_as_uint(pp) || keyN != (uint32_t)a.maxIter || keyStop != (uint32_t)STOP) return false;
+    const int d = mb - ma < 0 ? mb - ma + P : mb - ma;
+    const int e = kMemoHeader + SEC * memo_entries(L, P) + (cnt == 1 ? la : L + (la * L + lb) * P + d);
+    const uint32_t entry = (tab[e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
+    if (entry == 0u) return false;
+    const int i = lane_i<SH>(ln);
+    uint32_t hd = i == ma ? 1u << la : 0u;
+    if (cnt == 2 && i == mb) hd |= 1u << lb;
+    emit_decisions<L, SEC, SH>(a, ln, b, in_range, hd, stage);
+    iters_out = (int)entry;
+    return true;
+}
+
 // GO: list mode (the sector is known to go on past iteration 0, see iteration0)
 template <int R, int L, int SEC, int STOP, class SH, class TU, bool GO = false>
 __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_t b, bool in_range, float pp,
@@ -1360,6 +1460,10 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
             iters_out = (int)((zs >> 8) & 0xFFFFu);
             return;
         }
+    }
+    // One or two isolated qubit errors: the launch's outcome table (light_memo)
+    if constexpr (kLightMemo<STOP, SH, GO>()) {
+        if (light_memo<R, L, SEC, STOP, SH>(a, ln, b, in_range, pp, sbits, iters_out, stage)) return;
     }
     // InitVarNodes: every edge starts at p' (DecoderCPU.h:135-148, 265-267).  Only when iteration 0 is not
     // made by table (N < 2, wave-uniform): the table writes every register of every lane (below), so with it
@@ -1884,6 +1988,7 @@ struct Variant {
     // under the syndrome stop only from seq_syn_min_p on
     long long seq_min_batch[3] = {};
     float seq_syn_min_p = 0.0f;
+    bool light_memo = false;  // its fixed / reference-stop kernels take the light-sector table (kLightMemo)
 };
 
 // Both sectors' iteration-0 tables on the host, entry for entry what the device's table0_entry
@@ -1925,6 +2030,7 @@ static Variant make_variant(int P, int S, int T, const char* name)
     }
     v.min_waves_syn = TUL::kMinWavesSyn;  // the list launch's grid (launch_decode_list)
     v.list_wpb = waves_per_block<TUL>();
+    v.light_memo = kLightMemo<QEC_STOP_FIXED, SH, false>();
     return v;
 }
 // Tune<min waves per SIMD, relabel, zero-skip, short division, hard-message paths, sector split,
@@ -2092,7 +2198,7 @@ int launch_decode(const void* variant, const Code& c, const uint8_t* sX, const u
                   float errorProbability, int maxIter, int stop, uint8_t* eX, uint8_t* eZ, uint8_t* flags,
                   uint8_t* rec, int32_t* iters, float* q, int hardPaths, const int32_t* perm, int split,
                   uint32_t* merge, bool merge_zeroed, hipStream_t stream, int rec_stride, bool perm_sectors,
-                  hipEvent_t done)
+                  hipEvent_t done, const uint16_t* memo)
 {
     const Variant* v = static_cast<const Variant*>(variant);
     if (B <= 0) return QEC_OK;
@@ -2135,6 +2241,8 @@ int launch_decode(const void* variant, const Code& c, const uint8_t* sX, const u
     v->fill_tab0(2.0f / 3.0f * errorProbability, a.tab0);  // p' as the kernel forms it
     if (!phase)
         for (int sec = 0; sec < 2; ++sec) a.zs[sec] = v->zero_out[sec](2.0f / 3.0f * errorProbability, a.maxIter, stop);
+    // the light-sector table (light_memo), where the caller holds one for this launch's key
+    a.memo = !phase && v->light_memo && q == nullptr && stop != QEC_STOP_SYNDROME && a.maxIter >= 2 ? memo : nullptr;
     relabel(c.EX.data(), c.J, c.L, c.P, v->relabel, a.SX, a.DX, a.CX);
     relabel(c.EZ.data(), c.K, c.L, c.P, v->relabel, a.SZ, a.DZ, a.CZ);
     const int wavesPerBlock = v->waves_per_block;
@@ -2161,6 +2269,147 @@ int launch_decode(const void* variant, const Code& c, const uint8_t* sX, const u
 }
 
 bool decode_has_list(const void* variant) { return static_cast<const Variant*>(variant)->list != nullptr; }
+
+// ---- filling the light-sector table (light_memo) ------------------------------------------------
+// Row sec * E + e of the fill launch, E = memo_entries(L, P): the representative of class e of sector sec, i.e.
+// the syndrome of variable (e, 0) for e < L, else of variables (l1, 0) and (l2, d) with e - L = (l1 L + l2) P + d,
+// in sector sec and zero in the other.  One workgroup writes one row pair.
+struct MemoClass {
+    int sec, e, nv, l[2], mu[2];
+};
+__device__ __forceinline__ MemoClass memo_class(const BpArgs& a, int L, int row)
+{
+    const int E = memo_entries(L, a.P);
+    MemoClass k;
+    k.sec = row / E;
+    k.e = row - k.sec * E;
+    k.mu[0] = 0;
+    if (k.e < L) {
+        k.nv = 1;
+        k.l[0] = k.l[1] = k.e;
+        k.mu[1] = 0;
+    } else {
+        const int t = k.e - L;
+        k.nv = 2;
+        k.l[0] = t / (L * a.P);
+        k.l[1] = t / a.P % L;
+        k.mu[1] = t % a.P;
+    }
+    return k;
+}
+
+__global__ __launch_bounds__(64) void memo_synth_kernel(const BpArgs a, int L, uint8_t* __restrict__ sX,
+                                                        uint8_t* __restrict__ sZ)
+{
+    const int row = blockIdx.x;
+    uint8_t* rX = sX + (size_t)row * a.mX;
+    uint8_t* rZ = sZ + (size_t)row * a.mZ;
+    for (int c = threadIdx.x; c < a.mX; c += 64) rX[c] = 0;
+    for (int c = threadIdx.x; c < a.mZ; c += 64) rZ[c] = 0;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const MemoClass k = memo_class(a, L, row);
+    const int R = (k.sec ? a.mZ : a.mX) / a.P;
+    const int* S = k.sec ? a.SZ : a.SX;
+    const int* D = k.sec ? a.DZ : a.DX;
+    uint8_t* s = k.sec ? rZ : rX;
+    for (int v = 0; v < k.nv; ++v)
+        for (int r = 0; r < R; ++r) {
+            const int lane = ((k.mu[v] - S[r * L + k.l[v]]) % a.P + a.P) % a.P;  // check-view lane of the check
+            s[r * a.P + (lane + D[r]) % a.P] ^= 1;
+        }
+}
+
+// Entry of row's class: the iteration count if the decode returned exactly the generating qubits with the
+// sector's two flags clear and the representative's checks are disjoint (syndrome weight nv R), else 0.
+__global__ __launch_bounds__(64) void memo_check_kernel(const BpArgs a, int L, const uint8_t* __restrict__ sX,
+                                                        const uint8_t* __restrict__ sZ, const uint8_t* __restrict__ eX,
+                                                        const uint8_t* __restrict__ eZ, const uint8_t* __restrict__ flags,
+                                                        const int32_t* __restrict__ iters, uint16_t* __restrict__ table,
+                                                        uint32_t keyP, uint32_t keyN, uint32_t keyStop)
+{
+    const int row = blockIdx.x;
+    const MemoClass k = memo_class(a, L, row);
+    const int m = k.sec ? a.mZ : a.mX, R = m / a.P;
+    const int* C = k.sec ? a.CZ : a.CX;
+    const uint8_t* s = (k.sec ? sZ : sX) + (size_t)row * m;
+    const uint8_t* e = (k.sec ? eZ : eX) + (size_t)row * a.n;
+    int q[2];
+    for (int v = 0; v < 2; ++v) q[v] = k.l[v] * a.P + (k.mu[v] + C[k.l[v]]) % a.P;
+    int weight = 0, wrong = 0;
+    for (int c = threadIdx.x; c < m; c += 64) weight += s[c];
+    for (int j = threadIdx.x; j < a.n; j += 64) wrong += e[j] != (uint8_t)(j == q[0] || j == q[1]);
+    __shared__ int tot[2];
+    if (threadIdx.x == 0) tot[0] = tot[1] = 0;
+    __syncthreads();
+    atomicAdd(&tot[0], weight);
+    atomicAdd(&tot[1], wrong);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const int fail = k.sec ? (QEC_SYNDROME_FAIL_Z | QEC_CONVERGENCE_FAIL_Z) : (QEC_SYNDROME_FAIL_X | QEC_CONVERGENCE_FAIL_X);
+    const int it = iters[2 * row + k.sec];
+    const bool ok = tot[0] == k.nv * R && tot[1] == 0 && !(flags[row] & fail) && it >= 1 && it <= 0xFFFF;
+    table[kMemoHeader + row] = ok ? (uint16_t)it : (uint16_t)0;  // row = sec E + e
+    if (row == 0) {  // the key: read by light_memo, written with the entries
+        uint32_t* hdr = reinterpret_cast<uint32_t*>(table);
+        hdr[0] = keyP;
+        hdr[1] = keyN;
+        hdr[2] = keyStop;
+    }
+}
+
+static size_t memo_align(size_t x) { return (x + 255) / 256 * 256; }
+
+// Bytes of the table, 0 for a variant without the path; and of the fill launch's reserved workspace
+size_t memo_table_bytes(const void* variant, const Code& c)
+{
+    const Variant* v = static_cast<const Variant*>(variant);
+    if (!v->light_memo) return 0;
+    return memo_align((kMemoHeader + 2 * (size_t)memo_entries(c.L, c.P)) * sizeof(uint16_t));
+}
+size_t memo_workspace_bytes(const void* variant, const Code& c)
+{
+    if (!memo_table_bytes(variant, c)) return 0;
+    const size_t rows = 2 * (size_t)memo_entries(c.L, c.P);
+    return memo_align(rows * c.mX) + memo_align(rows * c.mZ) + 2 * memo_align(rows * c.n) + memo_align(rows) +
+           memo_align(2 * rows * sizeof(int32_t));
+}
+
+// Fills table for the key (p', N, stop) on stream: the representatives' syndromes, one ordinary one-launch decode
+// of them with the table path off, and the comparison that writes the entries and the key.  No synchronisation.
+int launch_memo_fill(const void* variant, const Code& c, float errorProbability, int maxIter, int stop, int hardPaths,
+                     uint16_t* table, uint8_t* ws, hipStream_t stream)
+{
+    const Variant* v = static_cast<const Variant*>(variant);
+    const size_t bytes = memo_table_bytes(variant, c);
+    if (!bytes) return fail(QEC_ERR_UNSUPPORTED, "bp_decode: no light-sector table for this code");
+    const size_t rows = 2 * (size_t)memo_entries(c.L, c.P);
+    uint8_t* sX = ws;
+    uint8_t* sZ = sX + memo_align(rows * c.mX);
+    uint8_t* eX = sZ + memo_align(rows * c.mZ);
+    uint8_t* eZ = eX + memo_align(rows * c.n);
+    uint8_t* flags = eZ + memo_align(rows * c.n);
+    int32_t* iters = reinterpret_cast<int32_t*>(flags + memo_align(rows));
+    if (hipMemsetAsync(table, 0, bytes, stream) != hipSuccess)
+        return fail(QEC_ERR_HIP, "bp_decode: light-sector table memset failed");
+    BpArgs a{};
+    a.P = c.P; a.n = c.n; a.mX = c.mX; a.mZ = c.mZ;
+    relabel(c.EX.data(), c.J, c.L, c.P, v->relabel, a.SX, a.DX, a.CX);
+    relabel(c.EZ.data(), c.K, c.L, c.P, v->relabel, a.SZ, a.DZ, a.CZ);
+    hipLaunchKernelGGL(memo_synth_kernel, dim3((unsigned)rows), dim3(64), 0, stream, a, c.L, sX, sZ);
+    int rc = launch_decode(variant, c, sX, sZ, false, (long long)rows, errorProbability, maxIter, stop, eX, eZ, flags,
+                           nullptr, iters, nullptr, hardPaths & ~QEC_HP_PHASE, nullptr, 0, nullptr, false, stream, 0, false,
+                           nullptr, nullptr);
+    if (rc) return rc;
+    const float pp = 2.0f / 3.0f * errorProbability;
+    uint32_t keyP;
+    memcpy(&keyP, &pp, sizeof keyP);
+    hipLaunchKernelGGL(memo_check_kernel, dim3((unsigned)rows), dim3(64), 0, stream, a, c.L, sX, sZ, eX, eZ, flags, iters,
+                       table, keyP, (uint32_t)(maxIter < 0 ? 0 : maxIter), (uint32_t)stop);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(QEC_ERR_HIP, std::string("bp_decode table fill: ") + hipGetErrorString(err));
+    return QEC_OK;
+}
 
 
 // Compute units of the current device (4 SIMDs each), cached per device (the list-mode grid).

@@ -28,7 +28,11 @@ int launch_decode(const void* variant, const Code& c, const uint8_t* sX, const u
                   float errorProbability, int maxIter, int stop, uint8_t* eX, uint8_t* eZ, uint8_t* flags,
                   uint8_t* rec, int32_t* iters, float* q, int hardPaths, const int32_t* perm, int split,
                   uint32_t* merge, bool merge_zeroed, hipStream_t stream, int rec_stride = 0, bool perm_sectors = false,
-                  hipEvent_t done = nullptr);
+                  hipEvent_t done = nullptr, const uint16_t* memo = nullptr);
+size_t memo_table_bytes(const void* variant, const Code& c);
+size_t memo_workspace_bytes(const void* variant, const Code& c);
+int launch_memo_fill(const void* variant, const Code& c, float errorProbability, int maxIter, int stop, int hardPaths,
+                     uint16_t* table, uint8_t* ws, hipStream_t stream);
 size_t schedule_workspace_bytes(long long B, int mX, int mZ);
 bool schedule_sector_order(long long B, bool sbits, int mX, int mZ);
 long long schedule_max_batch();
@@ -156,6 +160,14 @@ struct qec_decoder {
     int hard_paths = 1;             // QEC_OPT_HARD_PATHS
     int cycle_jump = 1;             // QEC_OPT_CYCLE_JUMP
     int near_hard = 1;              // QEC_OPT_NEAR_HARD_JUMP
+    // QEC_OPT_LIGHT_MEMO: sectors of one or two isolated qubit errors from a per-key outcome table (bp_decode.hip,
+    // light_memo).  The table and the fill launch's workspace are allocated at creation (variants with the path);
+    // memo_key = (bits of p', N, stop) of the table's content, filled on the stream of the first call with a new key
+    int light_memo = 1;
+    DeviceArray<uint16_t> memo_tab;
+    DeviceArray<uint8_t> memo_ws;
+    bool memo_valid = false;
+    uint32_t memo_key[3] = {0, 0, 0};
     int schedule = 1;               // QEC_OPT_SCHEDULE (0 off, 1 auto, 2 always, 3 / 4 always, local / one-launch order)
     int sector_split = 1;           // QEC_OPT_SECTOR_SPLIT (0 off, 1 auto, 2 split waves, 3 sector launches)
     int phase_stats = 0;            // QEC_OPT_PHASE_STATS
@@ -618,6 +630,10 @@ qec_decoder* qec_decoder_create_engine(const qec_code* h, int device, size_t max
         }
         // the counters, then the fused pipeline's list lengths: one memset zeroes both per call
         d->mcount.reserve(QEC_MC_NCOUNTERS_ALL + mc_count_u64());
+        if (d->variant && memo_table_bytes(d->variant, *d->code)) {
+            d->memo_tab.reserve(memo_table_bytes(d->variant, *d->code) / sizeof(uint16_t));
+            d->memo_ws.reserve(memo_workspace_bytes(d->variant, *d->code));
+        }
         if (d->variant) {
             d->gbar.reserve(2);
             hip_throw(hipMemset(d->gbar.data(), 0, 2 * sizeof(uint32_t)), "grid-barrier words");
@@ -769,6 +785,7 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
     case QEC_OPT_HARD_PATHS: d->hard_paths = value != 0; return QEC_OK;
     case QEC_OPT_CYCLE_JUMP: d->cycle_jump = value != 0; return QEC_OK;
     case QEC_OPT_NEAR_HARD_JUMP: d->near_hard = value != 0; return QEC_OK;
+    case QEC_OPT_LIGHT_MEMO: d->light_memo = value != 0; return QEC_OK;
     case QEC_OPT_SCHEDULE:
         if (value < 0 || value > 4) return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_SCHEDULE is 0 .. 4");
         d->schedule = value;
@@ -1272,6 +1289,7 @@ int qec_decoder_get_option(const qec_decoder* d, int option, int* value)
     case QEC_OPT_HARD_PATHS: *value = d->hard_paths; return QEC_OK;
     case QEC_OPT_CYCLE_JUMP: *value = d->cycle_jump; return QEC_OK;
     case QEC_OPT_NEAR_HARD_JUMP: *value = d->near_hard; return QEC_OK;
+    case QEC_OPT_LIGHT_MEMO: *value = d->light_memo; return QEC_OK;
     case QEC_OPT_SCHEDULE: *value = d->schedule; return QEC_OK;
     case QEC_OPT_SECTOR_SPLIT: *value = d->sector_split; return QEC_OK;
     case QEC_OPT_PHASE_STATS: *value = d->phase_stats; return QEC_OK;
@@ -1490,9 +1508,29 @@ int dispatch_decode(qec_decoder* d, const uint8_t* sX, const uint8_t* sZ, long l
         perm = pm;
         zeroed = split;
     }
+    // QEC_OPT_LIGHT_MEMO: the outcome table of this launch's key (p', N, stop).  A new key fills it first, on this
+    // stream, with the decoder's own kernels (no synchronisation); while the stream is being captured a cold key
+    // is not filled and the launch runs without the table.
+    const uint16_t* memo = nullptr;
+    const float pp = 2.0f / 3.0f * p;
+    if (d->light_memo && !d->phase_stats && d->memo_tab.capacity() > 0 && stop != QEC_STOP_SYNDROME && q == nullptr &&
+        maxIter >= 2 && maxIter <= 0xFFFF && pp > 0.0f && pp < 1.0f) {
+        uint32_t key[3] = {0, (uint32_t)maxIter, (uint32_t)stop};
+        std::memcpy(&key[0], &pp, sizeof(uint32_t));
+        if (d->memo_valid && std::memcmp(key, d->memo_key, sizeof key) == 0) {
+            memo = d->memo_tab.data();
+        } else if (!capturing(st)) {
+            d->memo_valid = false;
+            if ((rc = launch_memo_fill(d->variant, c, p, maxIter, stop, hp, d->memo_tab.data(), d->memo_ws.data(), st)))
+                return rc;
+            std::memcpy(d->memo_key, key, sizeof key);
+            d->memo_valid = true;
+            memo = d->memo_tab.data();
+        }
+    }
     rc = launch_decode(d->variant, c, sX, sZ, sbits, B, p, maxIter, stop, eX, eZ, flags, rec, iters, q, hp, perm,
                        split_opt, need_merge ? d->merge.data() : nullptr, zeroed, st, rec_stride, perm_sectors,
-                       ws_done(d, st));
+                       ws_done(d, st), memo);
     if (rc) return rc;
     d->last_path |= (perm ? QEC_PATH_ORDERED : 0) | (perm && perm_sectors ? QEC_PATH_SECTOR_ORDER : 0) |
                     (split ? QEC_PATH_SPLIT_WAVES : 0) | (need_merge && !split ? QEC_PATH_SECTOR_LAUNCHES : 0);

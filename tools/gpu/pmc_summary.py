@@ -39,7 +39,7 @@ def per_dispatch(d, kernel=KERNEL):
     """{counter: {kernel name: [value per dispatch]}} and each decode kernel's metadata.  A decode step
     may be several launches (the sector launches: an X kernel, then a Z kernel), so values are kept
     per kernel name and a step is the sum over the names of their per-dispatch averages."""
-    per, names, meta = {}, {}, {}
+    per, names, meta, grids = {}, {}, {}, {}
     for row in counter_rows(d):
         name = row.get("Kernel_Name", "")
         if kernel not in name:
@@ -47,13 +47,27 @@ def per_dispatch(d, kernel=KERNEL):
         key = (row["Dispatch_Id"], row["Counter_Name"])
         per[key] = per.get(key, 0.0) + float(row["Counter_Value"])
         names[row["Dispatch_Id"]] = name
+        grids[row["Dispatch_Id"]] = (name, row["Grid_Size"])
         meta[name] = {"vgpr": int(row["VGPR_Count"]), "sgpr": int(row["SGPR_Count"]),
                       "scratch_bytes_per_lane": int(row["Scratch_Size"]), "lds_bytes": int(row["LDS_Block_Size"]),
                       "workgroup": int(row["Workgroup_Size"])}
+    step = step_launches(list(grids.values()))
     vals = {}
     for (disp, counter), v in per.items():
-        vals.setdefault(counter, {}).setdefault(names[disp], []).append(v)
-    return vals, meta
+        if grids[disp] in step:
+            vals.setdefault(counter, {}).setdefault(names[disp], []).append(v)
+    return vals, {n: m for n, m in meta.items() if any(n == k[0] for k in step)}
+
+
+def step_launches(launches):
+    """The (kernel name, grid size) pairs that belong to a decode step: those dispatched as often as the most
+    frequent one.  A decode kernel launched fewer times is not part of a step (the one launch that fills the
+    light-sector table in the first call of a new key, QEC_OPT_LIGHT_MEMO)."""
+    count = {}
+    for k in launches:
+        count[k] = count.get(k, 0) + 1
+    top = max(count.values()) if count else 0
+    return {k for k, c in count.items() if c == top}
 
 
 def per_step(vals):
@@ -63,12 +77,15 @@ def per_step(vals):
 
 def trace_duration_ns(d, kernel=KERNEL):
     """Decode time per step: per kernel name the average duration, summed; and the dispatch count."""
-    durs = {}
+    rows = []
     for f in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
         with open(f) as fh:
-            for row in csv.DictReader(fh):
-                if kernel in row.get("Kernel_Name", ""):
-                    durs.setdefault(row["Kernel_Name"], []).append(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
+            rows += [row for row in csv.DictReader(fh) if kernel in row.get("Kernel_Name", "")]
+    step = step_launches([(row["Kernel_Name"], row["Grid_Size_X"]) for row in rows])
+    durs = {}
+    for row in rows:
+        if (row["Kernel_Name"], row["Grid_Size_X"]) in step:
+            durs.setdefault(row["Kernel_Name"], []).append(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
     if not durs:
         return None, 0
     return sum(sum(v) / len(v) for v in durs.values()), sum(len(v) for v in durs.values())
