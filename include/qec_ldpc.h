@@ -449,13 +449,22 @@ int qec_decoder_device(const qec_decoder* dec);         /* HIP device ordinal (o
  *     both flags clear.  The table and the fill's workspace (about 22 MB for P61) are allocated by
  *     qec_decoder_create.  A call captured into a graph while its key is cold runs without the table.  Every
  *     output bit identical either way; 0 decodes those sectors by BP (for measurement).  Each part of a group
- *     holds its own table. */
+ *     holds its own table.
+ *   QEC_OPT_NEAR_PROBE (default 1; needs QEC_OPT_NEAR_HARD_JUMP; the fixed- and reference-stop kernels of P61): the
+ *     soft iteration that could end a sector first tests the two folds t0, t1 of every outgoing message
+ *     q = t1 / (t0 + t1) instead of dividing (qec_near_probe): one at least 2 / eps0 times the other on every edge,
+ *     each variable's on one side, and those sides satisfy the syndrome.  That implies the jump's exact test with
+ *     the same sides, so the sector leaves without forming or returning a message; where
+ *     the probe fails the ordinary pass runs and its exact test decides, in the same iteration as before.  Every
+ *     output bit identical either way; 0 always takes the ordinary pass (for measurement).  The CPU engine keeps
+ *     the exact test. */
 enum { QEC_OPT_HARD_PATHS = 1, QEC_OPT_CYCLE_JUMP = 2, QEC_OPT_SCHEDULE = 3, QEC_OPT_SECTOR_SPLIT = 4,
        QEC_OPT_PHASE_STATS = 5, QEC_OPT_TRIAGE = 6, QEC_OPT_LAST_PATH = 7, QEC_OPT_MC_DECODE_TIME = 8,
        QEC_OPT_OSD = 9, QEC_OPT_OSD_ITERATIONS = 10, QEC_OPT_OSD_SECTORS = 11, QEC_OPT_OSD_SWEEP = 12,
        QEC_OPT_OSD_ORDER = 13, QEC_OPT_OSD_CS_SECTORS = 14, QEC_OPT_NEAR_HARD_JUMP = 15, QEC_OPT_OSD_SCORE = 16,
        QEC_OPT_CORRELATED = 17, QEC_OPT_BP_SCHEDULE = 18, QEC_OPT_BP_METHOD = 19, QEC_OPT_MINSUM_SCALE = 20,
-       QEC_OPT_MINSUM_WAVE = 21, QEC_OPT_RELAY_WAVE = 22, QEC_OPT_MINSUM_SCHEDULE = 23, QEC_OPT_LIGHT_MEMO = 24 };
+       QEC_OPT_MINSUM_WAVE = 21, QEC_OPT_RELAY_WAVE = 22, QEC_OPT_MINSUM_SCHEDULE = 23, QEC_OPT_LIGHT_MEMO = 24,
+       QEC_OPT_NEAR_PROBE = 25 };
 enum {
     QEC_PATH_ORDERED = 1,          /* dispatch order pass (schedule.hip) */
     QEC_PATH_SECTOR_ORDER = 2,     /* ... in the per-sector form (each sector's waves by its own weight) */
@@ -481,6 +490,13 @@ enum {
  * or 0 if there is none or p' is outside (0, 1/2] (the jump then never fires); *T = the bit pattern one below
  * the float eps0 (1 - eps0): bits(fma(-q, q, q)) <= T as unsigned integers implies q <= eps0 or q >= 1 - eps0. */
 int qec_near_hard_threshold(float pPrime, int R, int L, float* eps0, uint32_t* T);
+/* The near-hard probe's test of one outgoing message q = t1 / (t0 + t1) from its two folds, for eps0 a power of two
+ * in [2^-20, 2^-8] (else 0): returns 1 iff both bit patterns lie below 0x7F000000 (non-negative, no -0, below
+ * 2^127, no NaN) and differ by at least (k + 1) << 23, eps0 = 2^-k -- which implies that the larger fold is at
+ * least 2 / eps0 times the smaller, exactly that on normal floats -- and then *side (nullable) = 1 iff t1 > t0.  A
+ * pair that passes has q' = RN(t1 / RN(t0 + t1)) with bits(fma(-q', q', q')) <= T of qec_near_hard_threshold and
+ * (q' >= 0.5f) == *side. */
+int qec_near_probe(float t0, float t1, float eps0, int* side);
 int qec_decoder_set_option(qec_decoder* dec, int option, int value);
 int qec_decoder_get_option(const qec_decoder* dec, int option, int* value);
 /* Per-qubit error priors ("prior form"): biased noise, qubits of different quality,

@@ -30,7 +30,8 @@ OPTION = {"hard_paths": 1, "cycle_jump": 2, "schedule": 3, "sector_split": 4, "p
           "last_path": 7, "mc_decode_time": 8, "osd": 9, "osd_iterations": 10, "osd_sectors": 11,
           "osd_sweep": 12, "osd_order": 13, "osd_cs_sectors": 14, "near_hard": 15, "osd_score": 16,
           "correlated": 17, "bp_schedule": 18, "bp_method": 19, "minsum_scale": 20,
-          "minsum_wave": 21, "relay_wave": 22, "minsum_schedule": 23, "light_memo": 24}
+          "minsum_wave": 21, "relay_wave": 22, "minsum_schedule": 23, "light_memo": 24,
+          "near_probe": 25}
 OPTIONS = OPTION
 # values of the "bp_schedule" option (QEC_OPT_BP_SCHEDULE)
 BP_SCHEDULE = {"flooding": 0, "serial": 1}
@@ -55,7 +56,7 @@ EXPORTS = (
     "qec_decoder_create", "qec_decoder_create_engine", "qec_decoder_create_multi", "qec_decoder_create_multi_engine",
     "qec_decoder_destroy",
     "qec_decoder_num_parts", "qec_decoder_part", "qec_decoder_device", "qec_decoder_describe",
-    "qec_decoder_set_option", "qec_decoder_get_option", "qec_near_hard_threshold",
+    "qec_decoder_set_option", "qec_decoder_get_option", "qec_near_hard_threshold", "qec_near_probe",
     "qec_decoder_set_priors", "qec_decoder_get_priors", "qec_decoder_get_osd_weights", "qec_sample_independent_dev",
     "qec_correlated_priors", "qec_minsum_llr", "qec_decoder_get_minsum_llr", "qec_decoder_set_pauli_channel", "qec_decoder_get_pauli_channel",
     "qec_decoder_set_relay", "qec_decoder_get_relay",
@@ -162,6 +163,7 @@ def lib():
             "qec_decoder_set_option": (i, [vp, i, i]),
             "qec_decoder_get_option": (i, [vp, i, vp]),
             "qec_near_hard_threshold": (i, [f, i, i, vp, vp]),
+            "qec_near_probe": (i, [f, f, f, vp]),
             "qec_decoder_set_priors": (i, [vp, vp, vp]),
             "qec_decoder_get_priors": (i, [vp, vp, vp]),
             "qec_decoder_get_osd_weights": (i, [vp, vp, vp]),
@@ -223,6 +225,14 @@ def near_hard_threshold(p_prime, R, L):
     _check(lib().qec_near_hard_threshold(float(np.float32(p_prime)), int(R), int(L), ctypes.byref(eps0), ctypes.byref(T)),
            "qec_near_hard_threshold")
     return float(eps0.value), int(T.value)
+
+
+def near_probe(t0, t1, eps0):
+    """qec_near_probe: (passes, side) of the near-hard probe for the folds t0, t1 (float32) of one outgoing
+    message t1 / (t0 + t1); side = 1 iff t1 > t0."""
+    side = ctypes.c_int(0)
+    ok = lib().qec_near_probe(float(np.float32(t0)), float(np.float32(t1)), float(np.float32(eps0)), ctypes.byref(side))
+    return bool(ok), int(side.value)
 
 
 def correlated_priors(p):

@@ -87,6 +87,7 @@ struct Tune {
     static constexpr bool kFastDiv = FASTDIV_;  // the short division (div_short)
     static constexpr bool kSaturate = SATURATE_;  // the hard-message forms (check_pass_hard, var_pass)
     static constexpr bool kAgreeSyn = false;  // the syndrome stop takes the agreement test (kAgree): never
+    static constexpr bool kNearProbe = false;  // the division-free probe in front of near-tested var passes (var_probe)
     static constexpr int kSeqSynWavesX = kMinWavesSyn, kSeqSynWavesZ = kMinWavesSyn;  // sector launches, syndrome stop
 };
 
@@ -212,6 +213,9 @@ struct BpArgs {
     // near-hard jump (qec_near.h), per sector: the compare value T of this launch's
     // eps0; 0 = off (option off, final messages requested, syndrome stop, or no eps0 for this p')
     uint32_t nearT[2];
+    // near-hard probe (QEC_OPT_NEAR_PROBE, var_probe), per sector: near_probe_scale of this launch's eps0;
+    // 0 = off (the option, or nearT = 0)
+    uint32_t nearK[2];
     // lane-relabelled circulant tables (relabel(), qec_wave.h)
     // iteration-0 tables of both sectors computed on the host (launch_decode: the same operations,
     // so the same bits, as table0_entry on the device; each workgroup copies them to LDS, four entries
@@ -595,6 +599,15 @@ __device__ __forceinline__ uint32_t near_T(const BpArgs&)
     asm volatile("" : "+s"(k));
     return k[offsetof(BpArgs, nearT) / sizeof(uint32_t) + SEC];
 }
+// The probe's scale (BpArgs::nearK; 0 = off), read the same way.
+template <int SEC>
+__device__ __forceinline__ uint32_t near_K(const BpArgs&)
+{
+    const __attribute__((address_space(4))) uint32_t* k =
+        (const __attribute__((address_space(4))) uint32_t*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return k[offsetof(BpArgs, nearK) / sizeof(uint32_t) + SEC];
+}
 
 // VarNodeUpdate (DecoderCPU.h:188-229) for variables (l, i): gather the R incoming
 // check messages by forward rotation, update, scatter back by the inverse rotation.
@@ -812,6 +825,63 @@ __device__ __forceinline__ uint32_t var_pass(const BpArgs& a, float (&msg)[R][L]
     return hdmask;
 }
 
+// The near-hard probe (QEC_OPT_NEAR_PROBE; qec_near.h): the var-view half of C(eps0)
+// for the state a soft var pass that is not the last would produce, from the folds of its outputs alone.  The
+// gathers and the two left folds t0, t1 of every output are var_pass's (same operations, same order, scaled folds
+// included: num = t1, den = t0 + t1), column by column; no quotient is formed, nothing is rotated back and msg is
+// not written.
+// True: every output of every live lane has one fold at least 2 / eps0 times the other (K = near_K, the scale
+// on the bit patterns) and each variable's R outputs lie on one side; hd_near bit l = that side for variable
+// (l, .) of this lane (the variable view, as a decision mask).  var_pass's exact test then holds for that state
+// with the same sides.  False: after the first column group (one ballot, as var_pass's track) or at the end;
+// the caller runs var_pass on the untouched registers.
+template <int R, int L, int SEC, class SH, class TU, int CG>
+__device__ __forceinline__ bool var_probe(const BpArgs& a, const float (&msg)[R][L], const Lane& ln, float pp,
+                                          float one_minus_pp, uint32_t K, uint32_t& hd_near)
+{
+    static_assert(L % CG == 0, "column groups must tile the L columns");
+    constexpr bool kScalable = TU::kFastDiv && R - 1 <= 4;
+    const bool scaled = kScalable && a.scaled;
+    const float fold0 = scaled ? one_minus_pp * 0x1p32f : one_minus_pp, fold1 = scaled ? pp * 0x1p32f : pp;
+    const int* et = SH::template table<SEC>(a);
+    int32_t margin = 0x7FFFFFFF;  // the least of this lane's variables' (NearProbeVar::margin)
+    uint32_t top = 0, hd = 0;
+#pragma unroll
+    for (int l0 = 0; l0 < L; l0 += CG) {
+#pragma unroll
+        for (int c = 0; c < CG; ++c) {
+            const int l = l0 + c;
+            float gv[R];
+            // (without var_pass's kPipeline gathers ahead: msg stays live through the whole probe, and with the D
+            // columns in flight beside it every kernel spilled some hundred registers)
+#pragma unroll
+            for (int r = 0; r < R; ++r) gv[r] = rot<SH>(msg[r][l], ln, SH::template shift<SEC, L>(et, r, l));
+            float bv[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) bv[r] = 1.0f - gv[r];
+            NearProbeVar pv;
+            float pre0 = fold0, pre1 = fold1;
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                float t0 = pre0, t1 = pre1;
+#pragma unroll
+                for (int k = j + 1; k < R; ++k) { t0 = t0 * bv[k]; t1 = t1 * gv[k]; }
+                pv.add(__float_as_uint(t0), __float_as_uint(t1), top);
+                if (j + 1 < R) { pre0 = pre0 * bv[j]; pre1 = pre1 * gv[j]; }
+            }
+            margin = min(margin, pv.margin());
+            hd |= (uint32_t)pv.side() << l;
+            // (laundered: the bit is formed here; sunk to the mask's use behind the last ballot, the compiler
+            // kept every variable's extremes live to the end of the pass)
+            asm volatile("" : "+v"(hd));
+        }
+        if (l0 == 0 && !all_live_sh<SH>(margin >= (int32_t)K && top < kNearProbeTop, ln.live)) return false;
+        __builtin_amdgcn_sched_barrier(0);  // one column group at a time (var_pass)
+    }
+    hd_near = hd;
+    return all_live_sh<SH>(margin >= (int32_t)K && top < kNearProbeTop, ln.live);
+}
+
 // VarNodeUpdate on a hard sector whose R incoming messages agree for every variable (every
 // live lane): then each outgoing message q_j = P1 / (P0 + P1) is the common value (all 1:
 // p'/p' = 1; all 0: +0/(1-p') = +0; LAST or R >= 2, see var_pass), so the message sent back on
@@ -938,6 +1008,19 @@ constexpr bool kRow0Local()
 template <int L>
 constexpr bool kSkipSeen() { return L < 32; }
 
+// Whether a kernel carries the near-hard probe (var_probe): the variant's choice (Tune::kNearProbe), one-group
+// waves with compile-time shifts only -- there a probe that passes ends the wave's one sector at once, and the
+// post-processing's fast branch reads the probe's side mask; a wave of several groups can hold sectors that
+// stopped another way and takes the general branch, which reads messages -- and not the instrumented kernels.
+template <int STOP, class SH, class TU>
+constexpr bool kNearProbe()
+{
+    if constexpr (SH::kStatic)
+        return TU::kNearProbe && TU::kSaturate && !QEC_PHASE_STATS && STOP != QEC_STOP_SYNDROME && 2 * SH::kP > 64;
+    else
+        return false;
+}
+
 // One BP iteration; returns true if this group stops after it.
 // hard: every variable->check message of this sector is exactly +0 or 1.0 (wave-uniform).
 // agreed: set when the iteration took the agreement path (hard sector, every variable's inputs
@@ -947,10 +1030,12 @@ constexpr bool kSkipSeen() { return L < 32; }
 // near: the new state of every live lane's sector meets the near-hard criterion C(eps0) of this launch
 // (qec_near.h; fixed / reference stop, a soft pass that is not the last): every later state does too, so the
 // caller jumps to the sector's end (wave-uniform).
+// hd_near (out, kNearProbe kernels, when near comes out set): the sides h of that state, bit l = variable (l, .)
+// of this lane in the variable view.
 template <int R, int L, int SEC, int STOP, bool LAST, class SH, class TU>
 __device__ __forceinline__ bool iteration(const BpArgs& a, float (&msg)[R][L], uint32_t sbits, int n, Lane& ln,
                                           float pp, float one_minus_pp, bool& hard, bool& agreed, bool& vagree,
-                                          uint32_t& hd_out, uint32_t (&seen)[2], bool& near)
+                                          uint32_t& hd_out, uint32_t (&seen)[2], bool& near, uint32_t& hd_near)
 {
     const int P = SH::P(a);
     // launder the permute bases so their per-rotation selects are recomputed inside the
@@ -986,11 +1071,55 @@ __device__ __forceinline__ bool iteration(const BpArgs& a, float (&msg)[R][L], u
         constexpr bool kNear = TU::kSaturate && !LAST && STOP != QEC_STOP_SYNDROME;
         const bool from1 = kNear && near_T<SEC>(a) != 0u;
         const bool track = (LAST || n >= (from1 ? 1 : kTrackFrom)) && (a.hardPaths & QEC_HP_FORMS);
-        hdmask = var_pass<R, L, SEC, LAST, HD, SH, TU, CG, true, kNear>(a, msg, ln, pp, one_minus_pp, hard, vagree, track,
-                                                                        near);
-        // the messages are back in the check view (no deferred return under these stops)
-        if constexpr (kNear) {
-            if (near) near = all_live_sh<SH>(lane_parity_ok<R, L>(msg, sbits), ln.live);
+        // The probe first (var_probe), where this pass could end the sector: not at the reference stop's
+        // n % 10 == 0, whose convergence test reads the new messages.  When it passes wave-wide, H h = s is tested
+        // on its side mask (integer rotations of the packed bits, row 0 lane-local with the relabelling) and the
+        // sector leaves with msg still the check->variable messages: no division, no return rotation.  A probe
+        // or a syndrome that fails leaves the registers untouched for the ordinary pass below, whose exact test
+        // then decides as before (the probe implies it: a passing probe with H h != s fails there too).
+        bool probed = false;
+        if constexpr (kNear && kNearProbe<STOP, SH, TU>()) {
+            const uint32_t K = near_K<SEC>(a);
+            if (band(band(track, K != 0u), STOP != QEC_STOP_REF || n % 10 != 0)) {
+                uint32_t hdn = 0;
+                if (var_probe<R, L, SEC, SH, TU, CG>(a, msg, ln, pp, one_minus_pp, K, hdn)) {
+                    if constexpr (SH::kMaskSelect) asm volatile("" : "+v"(ln.b0), "+v"(ln.b1));
+                    probed = all_live_sh<SH>(lane_syndrome_ok<R, L, SEC, SH>(a, hdn, sbits, ln), ln.live);
+                    if (probed) {
+                        near = true;
+                        hd_near = hdn;
+                    }
+                }
+            }
+        }
+        if (!probed) {
+            // (laundered again: the pass's gathers are the probe's, and as common subexpressions the R L gathered
+            // values would stay live from a failed probe into the pass)
+            if constexpr (kNear && kNearProbe<STOP, SH, TU>() && SH::kMaskSelect) asm volatile("" : "+v"(ln.b0), "+v"(ln.b1));
+            if constexpr (kNear && kNearProbe<STOP, SH, TU>()) {
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+#pragma unroll
+                    for (int l = 0; l < L; ++l) asm volatile("" : "+v"(msg[r][l]));
+            }
+            hdmask = var_pass<R, L, SEC, LAST, HD, SH, TU, CG, true, kNear>(a, msg, ln, pp, one_minus_pp, hard, vagree,
+                                                                            track, near);
+            // the messages are back in the check view (no deferred return under these stops)
+            if constexpr (kNear) {
+                if (near) near = all_live_sh<SH>(lane_parity_ok<R, L>(msg, sbits), ln.live);
+                if constexpr (kNearProbe<STOP, SH, TU>()) {
+                    // the same mask for a sector that leaves through the exact test: each variable's side is row
+                    // 0's (decode_sector's fast branch)
+                    if (near) {
+                        const int* et = SH::template table<SEC>(a);
+                        uint32_t hdn = 0;
+#pragma unroll
+                        for (int l = 0; l < L; ++l)
+                            hdn |= (uint32_t)(rot<SH>(msg[0][l], ln, SH::template shift<SEC, L>(et, 0, l)) >= 0.5f) << l;
+                        hd_near = hdn;
+                    }
+                }
+            }
         }
     }
     if constexpr (STOP == QEC_STOP_REF) {
@@ -1493,6 +1622,10 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
     // near_done: this group left through the near-hard jump; its registers hold the soft state that met
     // C(eps0), not a hard one (group-uniform)
     bool near_done = false;
+    // kNearProbe kernels: the sides h of the state a near_done group left with (iteration).  Deliberately without
+    // an initial value -- it is read only behind near_done, which the jump sets after iteration wrote it: an
+    // initialised one is a register live around the whole iteration loop
+    uint32_t hd_near;
     int ph_soft = 0, ph_hard = 0, ph_agree = 0, ph_jump = 0;  // QEC_PHASE_STATS
     // syndrome stop rule: the hard decision of the last executed iteration and its syndrome test
     // (hd_valid: the current state is that iteration's output, i.e. not reached by a cycle jump).
@@ -1535,7 +1668,7 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
             ++it;
             const bool was_hard = hard;
             syn_last = iteration<R, L, SEC, STOP, false, SH, TU>(a, msg, sbits, n, ln, pp, one_minus_pp, hard, agreed,
-                                                                 vagree, hd_last, seen, near);
+                                                                 vagree, hd_last, seen, near, hd_near);
             hd_valid = true;
             if (syn_last) active = false;
             if constexpr (QEC_PHASE_STATS) { ph_soft += !was_hard; ph_hard += was_hard && !agreed; ph_agree += agreed; }
@@ -1584,7 +1717,7 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
         ++it;
         const bool was_hard = hard;
         syn_last = iteration<R, L, SEC, STOP, true, SH, TU>(a, msg, sbits, n, ln, pp, one_minus_pp, hard, agreed, vagree,
-                                                            hd_last, seen, near);
+                                                            hd_last, seen, near, hd_near);
         hd_valid = true;
         if constexpr (QEC_PHASE_STATS) { ph_soft += !was_hard; ph_hard += was_hard && !agreed; ph_agree += agreed; }
         st_agreed = vagree;
@@ -1604,9 +1737,15 @@ __device__ __forceinline__ void decode_sector(const BpArgs& a, Lane& ln, uint32_
         // A wave that also holds groups that stopped another way takes the general branch below, which gives a
         // near-exited group these same three results from its soft registers (never the agreeing branch, unless
         // that state is itself hard and agreeing: st_agreed is var_pass's word on it).
+        // With the probe (kNearProbe) the sides come as the mask iteration formed: a sector that left through
+        // var_probe holds check->variable messages in its registers, not that state.
+        if constexpr (kNearProbe<STOP, SH, TU>()) {
+            hdmask = hd_near;
+        } else {
 #pragma unroll
-        for (int l = 0; l < L; ++l)
-            hdmask |= (uint32_t)(rot<SH>(msg[0][l], ln, SH::template shift<SEC, L>(et, 0, l)) >= 0.5f) << l;
+            for (int l = 0; l < L; ++l)
+                hdmask |= (uint32_t)(rot<SH>(msg[0][l], ln, SH::template shift<SEC, L>(et, 0, l)) >= 0.5f) << l;
+        }
         conv = true;
         syn_ok = true;
     } else if (STOP == QEC_STOP_SYNDROME && all_live(hd_valid, in_range)) {
@@ -1895,7 +2034,10 @@ using KernelFn = void (*)(const BpArgs);
 // A distinct Tune type keeps the two units' kernels apart (same code, different symbols).
 // Sector launches (MODE 3 / 4, QEC_OPT_SECTOR_SPLIT = 3): X alone needs R L = 40 message registers, Z 50.
 using TuneP61 = Tune<5, true, false, true, true, false, true, 2, 1, 4, 1, false, 6, 5>;
-struct TuneP61MinReg : TuneP61 {};
+// ... and take the near-hard probe (kNearProbe): the eight fixed- / reference-stop kernels of that unit
+struct TuneP61MinReg : TuneP61 {
+    static constexpr bool kNearProbe = true;
+};
 using ShiftsP61 = GeneratedShifts<4, 5, 10, 61, 9, 49, TuneP61::kRelabel, TuneP61::kMaskSelect>;
 // P7: three columns per division guard (col_group): 0.075 vs 0.077 ms at configs[1] (65 536 @ 20), even
 // at 2^20 (profiles/r03/cmp_p7_65536_colgroups.txt, cmp_p7_2e20.txt)
@@ -2237,6 +2379,10 @@ int launch_decode(const void* variant, const Code& c, const uint8_t* sX, const u
     if ((hardPaths & QEC_HP_FORMS) && (hardPaths & QEC_HP_NEAR) && q == nullptr && stop != QEC_STOP_SYNDROME) {
         a.nearT[0] = near_hard_threshold(2.0f / 3.0f * errorProbability, c.J, c.L).T;
         a.nearT[1] = near_hard_threshold(2.0f / 3.0f * errorProbability, c.K, c.L).T;
+        if (hardPaths & QEC_HP_NEAR_PROBE) {
+            a.nearK[0] = near_probe_scale(near_hard_threshold(2.0f / 3.0f * errorProbability, c.J, c.L).eps0);
+            a.nearK[1] = near_probe_scale(near_hard_threshold(2.0f / 3.0f * errorProbability, c.K, c.L).eps0);
+        }
     }
     v->fill_tab0(2.0f / 3.0f * errorProbability, a.tab0);  // p' as the kernel forms it
     if (!phase)

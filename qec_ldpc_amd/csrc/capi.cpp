@@ -160,6 +160,7 @@ struct qec_decoder {
     int hard_paths = 1;             // QEC_OPT_HARD_PATHS
     int cycle_jump = 1;             // QEC_OPT_CYCLE_JUMP
     int near_hard = 1;              // QEC_OPT_NEAR_HARD_JUMP
+    int near_probe = 1;             // QEC_OPT_NEAR_PROBE: the jump's division-free probe (bp_decode.hip, var_probe)
     // QEC_OPT_LIGHT_MEMO: sectors of one or two isolated qubit errors from a per-key outcome table (bp_decode.hip,
     // light_memo).  The table and the fill launch's workspace are allocated at creation (variants with the path);
     // memo_key = (bits of p', N, stop) of the table's content, filled on the stream of the first call with a new key
@@ -748,6 +749,14 @@ int qec_near_hard_threshold(float pPrime, int R, int L, float* eps0, uint32_t* T
     return QEC_OK;
 }
 
+int qec_near_probe(float t0, float t1, float eps0, int* side)
+{
+    int s = 0;
+    const bool ok = near_probe(t0, t1, eps0, s);
+    if (side) *side = s;
+    return ok ? 1 : 0;
+}
+
 // QEC_OPT_MINSUM_WAVE and QEC_OPT_RELAY_WAVE (`name`): 0 or 1 into `field`; 1 on a single handle needs the sparse engine
 // and a code with wave kernels (`select`).  `what` names the rule ("min-sum", "relay"), `alone` what only the sparse
 // engine does with it.
@@ -785,6 +794,7 @@ int qec_decoder_set_option(qec_decoder* d, int option, int value)
     case QEC_OPT_HARD_PATHS: d->hard_paths = value != 0; return QEC_OK;
     case QEC_OPT_CYCLE_JUMP: d->cycle_jump = value != 0; return QEC_OK;
     case QEC_OPT_NEAR_HARD_JUMP: d->near_hard = value != 0; return QEC_OK;
+    case QEC_OPT_NEAR_PROBE: d->near_probe = value != 0; return QEC_OK;
     case QEC_OPT_LIGHT_MEMO: d->light_memo = value != 0; return QEC_OK;
     case QEC_OPT_SCHEDULE:
         if (value < 0 || value > 4) return fail(QEC_ERR_ARG, "qec_decoder_set_option: QEC_OPT_SCHEDULE is 0 .. 4");
@@ -1289,6 +1299,7 @@ int qec_decoder_get_option(const qec_decoder* d, int option, int* value)
     case QEC_OPT_HARD_PATHS: *value = d->hard_paths; return QEC_OK;
     case QEC_OPT_CYCLE_JUMP: *value = d->cycle_jump; return QEC_OK;
     case QEC_OPT_NEAR_HARD_JUMP: *value = d->near_hard; return QEC_OK;
+    case QEC_OPT_NEAR_PROBE: *value = d->near_probe; return QEC_OK;
     case QEC_OPT_LIGHT_MEMO: *value = d->light_memo; return QEC_OK;
     case QEC_OPT_SCHEDULE: *value = d->schedule; return QEC_OK;
     case QEC_OPT_SECTOR_SPLIT: *value = d->sector_split; return QEC_OK;
@@ -1350,7 +1361,7 @@ constexpr long long kSplitOrderedMinBatch = 1LL << 19;
 
 int hard_path_bits(const qec_decoder* d)
 {
-    return (d->hard_paths ? (QEC_HP_FORMS | (d->cycle_jump ? QEC_HP_CYCLE : 0) | (d->near_hard ? QEC_HP_NEAR : 0)) : 0) |
+    return (d->hard_paths ? (QEC_HP_FORMS | (d->cycle_jump ? QEC_HP_CYCLE : 0) | (d->near_hard ? QEC_HP_NEAR | (d->near_probe ? QEC_HP_NEAR_PROBE : 0) : 0)) : 0) |
            (d->phase_stats ? QEC_HP_PHASE : 0);
 }
 

@@ -9,9 +9,10 @@
 
 namespace qec {
 
-// BpArgs::hardPaths bits (from QEC_OPT_HARD_PATHS / QEC_OPT_CYCLE_JUMP / QEC_OPT_NEAR_HARD_JUMP)
+// BpArgs::hardPaths bits (from QEC_OPT_HARD_PATHS / QEC_OPT_CYCLE_JUMP / QEC_OPT_NEAR_HARD_JUMP / QEC_OPT_NEAR_PROBE)
 enum { QEC_HP_FORMS = 1, QEC_HP_CYCLE = 2, QEC_HP_PHASE = 4 /* launch the instrumented kernel */,
-       QEC_HP_NEAR = 8 /* the near-hard jump (qec_near.h); only with QEC_HP_FORMS */ };
+       QEC_HP_NEAR = 8 /* the near-hard jump (qec_near.h); only with QEC_HP_FORMS */,
+       QEC_HP_NEAR_PROBE = 16 /* its division-free probe (QEC_OPT_NEAR_PROBE); only with QEC_HP_NEAR */ };
 // dispatch-order method (schedule.hip, launch_schedule): the global counting sort, the one-launch
 // chunk-local order or the global sort in one launch with a software grid barrier (both measured
 // slower; experiments)

@@ -50,4 +50,75 @@ inline NearHard near_hard_threshold(float pp, int R, int L)
     return out;
 }
 
+// The near-hard probe (QEC_OPT_NEAR_PROBE): the var-view half of C(eps0) read from the
+// two folds t0, t1 of an outgoing message q = t1 / (t0 + t1) before any division is made.
+//
+// On the bit patterns b0, b1 of t0, t1: both below 0x7F000000 (non-negative -- -0 excluded --, finite, below
+// 2^127, no NaN) and |b1 - b0| >= K with K = near_probe_scale(eps0) = (k + 1) << 23 for eps0 = 2^-k.  For
+// non-negative floats the map b -> value is monotone and value(b + 2^23) >= 2 value(b) (equality for normal b;
+// a subnormal or zero b lands in the first normal binade, at value (2^23 + b) 2^-149 >= 2 b 2^-149), so
+// |b1 - b0| >= K implies max(t0, t1) >= (2 / eps0) min(t0, t1), max(t0, t1) > 0: the integer test is the
+// ratio test, exact on normal folds and stricter below them; two zeros fail (K > 0).
+//
+// Then q' = RN(t1 / RN(t0 + t1)) -- what the IEEE and the short division both return, for the 2^32-scaled
+// folds too (the same quotient) -- satisfies, with u = 2^-24 and RN monotone:
+//   t1 (2 / eps0) <= t0:  RN(t0 + t1) >= t0, so q' <= RN(t1 / t0) <= eps0 / 2, and
+//                         RN(q' - q' q') <= q' <= eps0 / 2 < eps0 (1 - eps0);
+//   t0 (2 / eps0) <= t1:  t1 <= RN(t0 + t1) <= t1 (1 + eps0 / 2)(1 + u) (the sum is normal and below 2^128), so
+//                         1 >= q' >= 1 - eps0 / 2 - 2 u >= 1 - (5 / 8) eps0 (eps0 >= 2^-20 = 16 u), and
+//                         RN(q' - q' q') <= RN(1 - q') <= (5 / 8) eps0 < eps0 (1 - eps0) (eps0 <= 2^-8).
+// In both cases fma(-q', q', q') is non-negative and its bits are <= T of near_hard_threshold, and
+// q' >= 0.5f exactly when t1 > t0: a probe that passes is a state var_pass's exact test passes, with the same
+// sides.  The fold length does not enter (any t0, t1 of that domain).
+inline uint32_t near_probe_scale(float eps0)
+{
+    int e = 0;
+    if (!(eps0 > 0.0f) || std::frexp(eps0, &e) != 0.5f) return 0u;  // eps0 = 2^(e - 1)
+    const int k = 1 - e;
+    return k >= 8 && k <= 20 ? (uint32_t)(k + 1) << 23 : 0u;
+}
+constexpr uint32_t kNearProbeTop = 0x7F000000u;  // every fold's bit pattern lies below it
+// One variable's R outputs, one at a time (NearProbeVar::add, the bit patterns of an output's folds), then the
+// largest K they pass on one common side of 0.5 (margin; <= 0 if none): min_j (b1_j - b0_j) when every output lies
+// above (side = 1), min_j (b0_j - b1_j) when below (side = 0) -- valid when top, which accumulates the unsigned
+// maximum of every pattern seen, stays below kNearProbeTop.  The variable passes iff margin >= K > 0 and
+// top < kNearProbeTop; the kernel keeps the minimum margin and the one top of a lane's variables and compares
+// once per ballot.
+#if defined(__HIPCC__)
+#define QEC_NEAR_HD __host__ __device__ __forceinline__
+#else
+#define QEC_NEAR_HD inline
+#endif
+struct NearProbeVar {
+    int32_t mn = 0x7FFFFFFF, mx = -0x7FFFFFFF - 1;  // extremes of b1_j - b0_j
+    QEC_NEAR_HD void add(uint32_t b0, uint32_t b1, uint32_t& top)
+    {
+        const int32_t d = (int32_t)(b1 - b0);
+        mn = d < mn ? d : mn;
+        mx = d > mx ? d : mx;
+        top = top > b0 ? top : b0;
+        top = top > b1 ? top : b1;
+    }
+    QEC_NEAR_HD int32_t margin() const
+    {
+        const int32_t neg = (int32_t)(0u - (uint32_t)mx);
+        return mn > neg ? mn : neg;
+    }
+    QEC_NEAR_HD bool side() const { return mn > 0; }
+};
+#undef QEC_NEAR_HD
+// One output.  side (out, when true): 1 iff t1 > t0, the side of 0.5 q' lies on.  eps0 not a power of two in
+// [2^-20, 2^-8]: false.
+inline bool near_probe(float t0, float t1, float eps0, int& side)
+{
+    uint32_t b0, b1, top = 0u;
+    std::memcpy(&b0, &t0, sizeof t0);
+    std::memcpy(&b1, &t1, sizeof t1);
+    const uint32_t K = near_probe_scale(eps0);
+    NearProbeVar v;
+    v.add(b0, b1, top);
+    side = v.side();
+    return K != 0u && top < kNearProbeTop && v.margin() >= (int32_t)K;
+}
+
 }  // namespace qec
